@@ -8,6 +8,8 @@ attention over a batch of `--clips` independent clips (synthetic, seeded), input
 A query row = one (frame, query) producing C=256 outputs; M-queries/s = clips*T*300 / step time / 1e6.
 
     python bench.py                       # 1 GPU, default K/W, prints ONE JSON line
+    python bench.py --dump-outputs DIR    # ... and writes what the last timed step computed to DIR/*.npy (seeded
+                                          # inputs: two builds compare output for output)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...          # no launcher: bench.py starts that very torchrun as a child (launch_ranks),
@@ -42,6 +44,8 @@ PYRAMIDS = {
 }
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achievable with a float4 copy)
 DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
+DUMP_BYTES = 48 << 20   # --dump-outputs: budget of all the .npy files together
+LEAF_NAMES = ("value", "loc_c", "aw_c", "loc_t", "aw_t")
 
 
 def parse_args():
@@ -87,7 +91,14 @@ def parse_args():
                     help="TEST ONLY: every rank uses cuda:0 (exercises the N-rank protocol -- rendezvous, barriers, max-over-ranks, "
                          "ranks_seen -- on a box with one GPU; RCCL refuses two ranks on one device, so it needs --dist-backend gloo; "
                          "the line says so and its value is not a scaling figure)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the forward output and the gradients of "
+                         "the five inputs, rank 0's) as DIR/<name>.npy in float32, at most %d MiB in all: an array above its share "
+                         "is written as a fixed, seeded sample of its elements (DIR/manifest.json says which)" % (DUMP_BYTES >> 20))
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def make_clip_batch(args, device, dtype, seed):
@@ -589,6 +600,38 @@ def launch_ranks(n, argv, script=None, check_devices=True, timeout=None):
     return 0
 
 
+def dump_outputs(directory, outs, grads):
+    """--dump-outputs: what one step handed back to its caller, as float32 DIR/<name>.npy -- `out` (the forward output; the
+    per-clip outputs concatenated in sharded mode) and grad_<leaf> for LEAF_NAMES (`grads` in that order, repeating per clip in
+    sharded mode).  An array with more elements than its share of DUMP_BYTES is written flattened as a stratified sample: its
+    flat index range cut into `share` equal runs, one element drawn from each by a generator seeded from the array's name, so
+    the same arguments sample the same positions on every run and every build.  DIR/manifest.json records shapes and samples."""
+    import zlib
+    cat = lambda xs: xs[0] if len(xs) == 1 else torch.cat(xs, 0)
+    arrays = {"out": cat(list(outs))}
+    for i, name in enumerate(LEAF_NAMES):
+        arrays["grad_" + name] = cat(list(grads[i::len(LEAF_NAMES)]))
+    share = DUMP_BYTES // 4 // len(arrays)
+    os.makedirs(directory, exist_ok=True)
+    manifest = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        n = t.numel()
+        entry = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "sampled": n > share}
+        if n > share:
+            seed = zlib.crc32(name.encode())
+            g = torch.Generator(device="cpu").manual_seed(seed)
+            bounds = torch.arange(share + 1, dtype=torch.int64) * n // share
+            idx = bounds[:-1] + (torch.rand(share, generator=g, dtype=torch.float64) * (bounds[1:] - bounds[:-1])).long()
+            t = t.reshape(-1)[idx.to(t.device)]
+            entry["sample"] = {"elements": share, "seed": seed,
+                               "method": "flat index range in %d equal runs, one uniform draw per run (float64 torch.rand)" % share}
+        np.save(os.path.join(directory, name + ".npy"), t.float().cpu().numpy())
+        manifest[name] = entry
+    with open(os.path.join(directory, "manifest.json"), "w") as f:
+        json.dump({"what": "the last timed step of bench.py " + " ".join(sys.argv[1:]), "arrays": manifest}, f, indent=1)
+
+
 def main():
     args = parse_args()
     if args.share_device and args.dist_backend != "gloo":
@@ -656,7 +699,7 @@ def main():
 
     def step():
         out = forward()
-        torch.autograd.grad(out, leaves, b["grad_out"])
+        return [out], torch.autograd.grad(out, leaves, b["grad_out"])
 
     if args.mode == "sharded":
         # Mode 2: the SAME `clips` clips on every rank (seed without rank), each split over the ranks:
@@ -686,7 +729,7 @@ def main():
             # communication stream while the next clip's kernels run)
             outs = cp.sharded_temporal_attention_batch([(sh["v"], sh["lc"], sh["ac"], sh["lt"], sh["at"]) for sh in shard],
                                                        T, S, b["shapes"], b["lsi"], b["ftab"], transport_dtype=transport)
-            torch.autograd.grad(outs, sh_leaves, sh_go)
+            return outs, torch.autograd.grad(outs, sh_leaves, sh_go)
 
     def barrier():
         if world > 1:
@@ -705,8 +748,13 @@ def main():
         step()
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    # --dump-outputs keeps what the LAST step returned (rank 0 only); every other step drops its results as it returns, so
+    # without the flag the loop allocates and frees exactly as it always did
+    keep_last = bool(args.dump_outputs) and rank == 0
+    for _ in range(args.steps - keep_last):
         step()
+    if keep_last:
+        last = step()
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -717,6 +765,9 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     rows_per_step = (1 if args.mode == "sharded" else world) * args.clips * T * q
     value = rows_per_step / (ms_per_step * 1e-3) / 1e6
+    if keep_last:
+        dump_outputs(args.dump_outputs, *last)
+        del last
 
     # ---- the same K steps on the layout devis_amd's own modules hand the op (value_proj writes one spare
     # head slot per pixel row, functions.project_value): reported beside the headline, never as `value`
