@@ -9,6 +9,7 @@ same Python surface::
 
 Arithmetic lives in hand-written HIP kernels behind the C ABI of ``include/msda.h``
 (``devis_amd/csrc/*.hip``, one translation unit per kernel family -> ``devis_amd/libmsda_hip.so``); the Python here is the host side.
+Under ``torch.compile`` and ``torch.export`` the same host code runs as the custom ops of :mod:`devis_amd.ops`.
 There is no CPU fallback: like the reference (``src/ms_deform_attn.h:38,60``) the operator raises on
 CPU tensors, and it raises if the HIP library cannot be loaded.
 """
@@ -16,9 +17,10 @@ from .functions import (MSDeformAttnFunction, MSDeformAttnTemporalFunction,  # n
                         ms_deform_attn_core_pytorch)
 from .modules import (MSDeformAttn, TemporalMSDeformAttnDecoder,  # noqa: F401
                       TemporalMSDeformAttnEncoder)
+from . import ops  # noqa: F401  (the operator as torch.library custom ops: torch.compile / torch.export)
 from .argument_builders import patch_transformer  # noqa: F401
 from .graphs import graphed, graph_stream, GraphedLayer  # noqa: F401
 from .tuning import tune  # noqa: F401
 
 __all__ = ["MSDeformAttnFunction", "MSDeformAttnTemporalFunction", "ms_deform_attn_core_pytorch",
-           "MSDeformAttn", "TemporalMSDeformAttnEncoder", "TemporalMSDeformAttnDecoder", "patch_transformer", "graphed", "graph_stream", "GraphedLayer", "tune"]
+           "MSDeformAttn", "TemporalMSDeformAttnEncoder", "TemporalMSDeformAttnDecoder", "ops", "patch_transformer", "graphed", "graph_stream", "GraphedLayer", "tune"]

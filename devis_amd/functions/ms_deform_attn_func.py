@@ -54,11 +54,63 @@ def _im2col_step(batch, im2col_step):
     return step
 
 
+def _forward(value, shapes, lsi, loc, aw, im2col_step, padding_mask=None):
+    """Host side of the forward (checks, output allocation, the reference's chunk loop): [N, Lq, M*D].  Shared by
+    :class:`MSDeformAttnFunction` and the custom op ``devis_amd::ms_deform_attn_forward`` (devis_amd/ops.py)."""
+    if padding_mask is not None:
+        _require(padding_mask.dtype == torch.bool and padding_mask.device == value.device and
+                 padding_mask.numel() == value.shape[0] * value.shape[1], "padding_mask must be a bool [N, S] tensor on value's device")
+    _check_inputs([("value", value), ("spatial_shapes", shapes), ("level_start_index", lsi),
+                   ("sampling_loc", loc), ("attn_weight", aw)])
+    _check_op_shapes(value, shapes, lsi, loc, aw)
+    N, S, M, D = value.shape
+    Lq = loc.shape[1]
+    output = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
+    if N > 0 and Lq > 0:
+        step = _im2col_step(N, im2col_step)
+        # the reference launches once per chunk of `step` batch rows (cu:61-75); result-neutral
+        for n in range(0, N, step):
+            _native.forward(value[n:n + step], shapes, lsi, loc[n:n + step], aw[n:n + step], output[n:n + step])
+    return output
+
+
+def _backward(value, shapes, lsi, loc, aw, grad_output, im2col_step, padding_mask=None):
+    """Host side of the backward: (grad_value in value's dtype, grad_loc, grad_aw).  ``padding_mask``: the bool mask
+    `value` was produced under; grad_value's masked rows come back zero."""
+    grad_output = grad_output.contiguous()
+    N = value.shape[0]
+    # all three are fully written by the library (ABI v4: no zeros_like as in cu:121; skipped points -> 0).  16-bit
+    # storage: grad_value comes back in the storage type where the library can write it so (ABI v10), else in fp32
+    live = N > 0 and loc.shape[1] > 0
+    step = _im2col_step(N, im2col_step) if live else 0
+    acc = _native.grad_value_dtype(value[:step], shapes, loc.shape[1], loc.shape[3], loc.shape[4], grad_out=grad_output) if live else value.dtype
+    grad_value = (torch.empty if live else torch.zeros)(value.shape, dtype=acc, device=value.device)
+    grad_loc = torch.empty_like(loc)
+    grad_aw = torch.empty_like(aw)
+    if live:
+        for n in range(0, N, step):
+            _native.backward(value[n:n + step], shapes, lsi, loc[n:n + step], aw[n:n + step],
+                             grad_output[n:n + step], grad_value[n:n + step],
+                             grad_loc[n:n + step], grad_aw[n:n + step])
+    if acc != value.dtype:
+        grad_value = grad_value.to(value.dtype)
+    if padding_mask is not None and grad_value.numel():
+        N, S, M, D = grad_value.shape
+        _native.mask_rows(grad_value.view(N * S, M * D), padding_mask.reshape(-1).contiguous(), M * D)
+    return grad_value, grad_loc, grad_aw
+
+
+def _ops():
+    from .. import ops
+    return ops
+
+
 class MSDeformAttnFunction(Function):
     """Same call contract as the reference (``ms_deform_attn_func.py:21-38``):
     ``apply(value[N,S,M,D], spatial_shapes[L,2] i64, level_start_index[L] i64,
     sampling_locations[N,Lq,M,L,P,2], attention_weights[N,Lq,M,L,P], im2col_step) -> [N,Lq,M*D]``;
-    gradients for arguments 0, 3 and 4 only; ``once_differentiable``."""
+    gradients for arguments 0, 3 and 4 only; ``once_differentiable``.  Under ``torch.compile`` / ``torch.export``
+    both directions are the custom ops of devis_amd/ops.py (same host code, same kernels)."""
 
     @staticmethod
     def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations,
@@ -66,27 +118,14 @@ class MSDeformAttnFunction(Function):
         # padding_mask (not in the reference's signature; used by MSDeformAttn only): the bool [N, S] mask `value`
         # was produced under.  The backward then zeroes the masked rows of ITS grad_value (the gradient of ref
         # ms_deform_attn.py:102-103's masked_fill) before returning it, and project_value's backward skips that pass.
-        ctx.padding_mask = None
-        if padding_mask is not None:
-            _require(padding_mask.dtype == torch.bool and padding_mask.device == value.device and
-                     padding_mask.numel() == value.shape[0] * value.shape[1], "padding_mask must be a bool [N, S] tensor on value's device")
-            ctx.padding_mask = padding_mask.reshape(-1).contiguous()
-        _check_inputs([("value", value), ("spatial_shapes", value_spatial_shapes),
-                       ("level_start_index", value_level_start_index),
-                       ("sampling_loc", sampling_locations), ("attn_weight", attention_weights)])
-        _check_op_shapes(value, value_spatial_shapes, value_level_start_index, sampling_locations,
-                         attention_weights)
-        N, S, M, D = value.shape
-        Lq = sampling_locations.shape[1]
         ctx.im2col_step = im2col_step
-        output = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
-        if N > 0 and Lq > 0:
-            step = _im2col_step(N, im2col_step)
-            # the reference launches once per chunk of `step` batch rows (cu:61-75); result-neutral
-            for n in range(0, N, step):
-                _native.forward(value[n:n + step], value_spatial_shapes, value_level_start_index,
-                                sampling_locations[n:n + step], attention_weights[n:n + step],
-                                output[n:n + step])
+        ctx.padding_mask = padding_mask
+        if torch.compiler.is_compiling():
+            output = _ops().ms_deform_attn_forward(value, value_spatial_shapes, value_level_start_index,
+                                                   sampling_locations, attention_weights, im2col_step, padding_mask)
+        else:
+            output = _forward(value, value_spatial_shapes, value_level_start_index, sampling_locations,
+                              attention_weights, im2col_step, padding_mask)
         ctx.save_for_backward(value, value_spatial_shapes, value_level_start_index,
                               sampling_locations, attention_weights)
         return output
@@ -95,29 +134,65 @@ class MSDeformAttnFunction(Function):
     @once_differentiable
     def backward(ctx, grad_output):
         value, shapes, lsi, loc, aw = ctx.saved_tensors
-        grad_output = grad_output.contiguous()
-        N = value.shape[0]
-        # all three are fully written by the library (ABI v4: no zeros_like as in cu:121; skipped points -> 0).  16-bit
-        # storage: grad_value comes back in the storage type where the library can write it so (ABI v10), else in fp32
-        live = N > 0 and loc.shape[1] > 0
-        step = _im2col_step(N, ctx.im2col_step) if live else 0
-        acc = _native.grad_value_dtype(value[:step], shapes, loc.shape[1], loc.shape[3], loc.shape[4], grad_out=grad_output) if live else value.dtype
-        grad_value = (torch.empty if live else torch.zeros)(value.shape, dtype=acc, device=value.device)
-        grad_loc = torch.empty_like(loc)
-        grad_aw = torch.empty_like(aw)
-        if live:
-            for n in range(0, N, step):
-                _native.backward(value[n:n + step], shapes, lsi, loc[n:n + step], aw[n:n + step],
-                                 grad_output[n:n + step], grad_value[n:n + step],
-                                 grad_loc[n:n + step], grad_aw[n:n + step])
-        if acc != value.dtype:
-            grad_value = grad_value.to(value.dtype)
-        if ctx.padding_mask is not None and grad_value.numel():
-            N, S, M, D = grad_value.shape
-            _native.mask_rows(grad_value.view(N * S, M * D), ctx.padding_mask, M * D)
+        if torch.compiler.is_compiling():
+            grad_value, grad_loc, grad_aw = _ops().ms_deform_attn_backward(value, shapes, lsi, loc, aw, grad_output,
+                                                                           ctx.im2col_step, ctx.padding_mask)
+        else:
+            grad_value, grad_loc, grad_aw = _backward(value, shapes, lsi, loc, aw, grad_output, ctx.im2col_step,
+                                                      ctx.padding_mask)
         # one gradient slot per forward argument INCLUDING the optional padding_mask: autograd accepts trailing None
         # gradients beyond the inputs apply() was given, so the 6-argument (reference) call works with the same tuple
         return grad_value, None, None, grad_loc, grad_aw, None, None
+
+
+def _check_temporal_shapes(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr,
+                           loc_temp, aw_temp, clips):
+    _check_op_shapes(value, spatial_shapes, level_start_index, loc_curr, aw_curr)
+    G, S, M, D = value.shape
+    L = spatial_shapes.shape[0]
+    Lq = loc_curr.shape[1]
+    _require(clips > 0 and G % clips == 0, "value.shape[0] must be clips * frames")
+    T = G // clips
+    _require(frame_table.dtype == torch.int32 and frame_table.dim() == 2 and
+             frame_table.shape[0] == T, "frame_table must be int32 [frames, window]")
+    W = frame_table.shape[1]
+    _require(W > 0, "frame_table needs at least one temporal slot")
+    _require(loc_temp.dim() == 6 and tuple(loc_temp.shape[:4]) == (G, Lq, M, W * L) and
+             loc_temp.shape[5] == 2, "loc_temp must be [G, Lq, M, window*L, Pt, 2]")
+    _require(tuple(aw_temp.shape) == tuple(loc_temp.shape[:5]), "aw_temp does not match loc_temp")
+    _require(loc_temp.dtype == loc_curr.dtype and aw_temp.dtype == loc_curr.dtype,
+             "current-frame and temporal sampling tensors must share one dtype")
+
+
+def _temporal_forward(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, loc_temp, aw_temp,
+                      clips):
+    _check_inputs([("value", value), ("spatial_shapes", spatial_shapes),
+                   ("level_start_index", level_start_index), ("frame_table", frame_table),
+                   ("loc_curr", loc_curr), ("aw_curr", aw_curr),
+                   ("loc_temp", loc_temp), ("aw_temp", aw_temp)])
+    _check_temporal_shapes(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, loc_temp,
+                           aw_temp, clips)
+    G, S, M, D = value.shape
+    out = torch.empty((G, loc_curr.shape[1], M * D), dtype=value.dtype, device=value.device)
+    _native.temporal_forward(value, spatial_shapes, level_start_index, frame_table, loc_curr,
+                             aw_curr, loc_temp, aw_temp, clips, out)
+    return out
+
+
+def _temporal_backward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_output, clips):
+    """(grad_value in value's dtype, grad_loc_c, grad_aw_c, grad_loc_t, grad_aw_t)."""
+    grad_output = grad_output.contiguous()
+    W = ftab.shape[1]
+    acc = _native.grad_value_dtype(value, shapes, loc_c.shape[1], loc_c.shape[3], loc_c.shape[4], clips=clips,
+                                   window=W, Pt=loc_t.shape[4], grad_out=grad_output)
+    grad_value = torch.empty(value.shape, dtype=acc, device=value.device)      # overwritten (ABI v4)
+    gloc_c, gaw_c = torch.empty_like(loc_c), torch.empty_like(aw_c)
+    gloc_t, gaw_t = torch.empty_like(loc_t), torch.empty_like(aw_t)
+    _native.temporal_backward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_output,
+                              clips, grad_value, gloc_c, gaw_c, gloc_t, gaw_t)
+    if acc != value.dtype:
+        grad_value = grad_value.to(value.dtype)
+    return grad_value, gloc_c, gaw_c, gloc_t, gaw_t
 
 
 class MSDeformAttnTemporalFunction(Function):
@@ -136,28 +211,8 @@ class MSDeformAttnTemporalFunction(Function):
     @staticmethod
     def forward(ctx, value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr,
                 loc_temp, aw_temp, clips):
-        _check_inputs([("value", value), ("spatial_shapes", spatial_shapes),
-                       ("level_start_index", level_start_index), ("frame_table", frame_table),
-                       ("loc_curr", loc_curr), ("aw_curr", aw_curr),
-                       ("loc_temp", loc_temp), ("aw_temp", aw_temp)])
-        _check_op_shapes(value, spatial_shapes, level_start_index, loc_curr, aw_curr)
-        G, S, M, D = value.shape
-        L = spatial_shapes.shape[0]
-        Lq = loc_curr.shape[1]
-        _require(clips > 0 and G % clips == 0, "value.shape[0] must be clips * frames")
-        T = G // clips
-        _require(frame_table.dtype == torch.int32 and frame_table.dim() == 2 and
-                 frame_table.shape[0] == T, "frame_table must be int32 [frames, window]")
-        W = frame_table.shape[1]
-        _require(W > 0, "frame_table needs at least one temporal slot")
-        _require(loc_temp.dim() == 6 and tuple(loc_temp.shape[:4]) == (G, Lq, M, W * L) and
-                 loc_temp.shape[5] == 2, "loc_temp must be [G, Lq, M, window*L, Pt, 2]")
-        _require(tuple(aw_temp.shape) == tuple(loc_temp.shape[:5]), "aw_temp does not match loc_temp")
-        _require(loc_temp.dtype == loc_curr.dtype and aw_temp.dtype == loc_curr.dtype,
-                 "current-frame and temporal sampling tensors must share one dtype")
-        out = torch.empty((G, Lq, M * D), dtype=value.dtype, device=value.device)
-        _native.temporal_forward(value, spatial_shapes, level_start_index, frame_table, loc_curr,
-                                 aw_curr, loc_temp, aw_temp, clips, out)
+        fn = _ops().temporal_forward if torch.compiler.is_compiling() else _temporal_forward
+        out = fn(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, loc_temp, aw_temp, clips)
         ctx.clips = clips
         ctx.save_for_backward(value, spatial_shapes, level_start_index, frame_table, loc_curr,
                               aw_curr, loc_temp, aw_temp)
@@ -166,18 +221,8 @@ class MSDeformAttnTemporalFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
-        value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t = ctx.saved_tensors
-        grad_output = grad_output.contiguous()
-        W = ftab.shape[1]
-        acc = _native.grad_value_dtype(value, shapes, loc_c.shape[1], loc_c.shape[3], loc_c.shape[4], clips=ctx.clips,
-                                       window=W, Pt=loc_t.shape[4], grad_out=grad_output)
-        grad_value = torch.empty(value.shape, dtype=acc, device=value.device)      # overwritten (ABI v4)
-        gloc_c, gaw_c = torch.empty_like(loc_c), torch.empty_like(aw_c)
-        gloc_t, gaw_t = torch.empty_like(loc_t), torch.empty_like(aw_t)
-        _native.temporal_backward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_output,
-                                  ctx.clips, grad_value, gloc_c, gaw_c, gloc_t, gaw_t)
-        if acc != value.dtype:
-            grad_value = grad_value.to(value.dtype)
+        fn = _ops().temporal_backward if torch.compiler.is_compiling() else _temporal_backward
+        grad_value, gloc_c, gaw_c, gloc_t, gaw_t = fn(*ctx.saved_tensors, grad_output, ctx.clips)
         return grad_value, None, None, None, gloc_c, gaw_c, gloc_t, gaw_t, None
 
 
@@ -320,6 +365,15 @@ def project_value(x, linear, n_heads, padding_mask=None, pad_heads=1, consumer_m
     rows where the mask is set (``MSDeformAttnFunction`` given the same ``padding_mask``), so the backward skips it."""
     if pad_heads <= 0 and padding_mask is None:
         return linear(x).view(x.shape[0], x.shape[1], n_heads, linear.out_features // n_heads)
+    if torch.compiler.is_compiling():
+        # traced: the Linear, the masked_fill of ref :102-103 and a copy into the padded layout -- the same `value` (numbers
+        # and strides) for the compiler to fuse; the out= GEMM into a padded buffer is an eager-only shortcut
+        N, S = x.shape[0], x.shape[1]
+        y = linear(x)
+        if padding_mask is not None:
+            y = y.masked_fill(padding_mask.reshape(N, S, 1), 0.0)
+        value = y.view(N, S, n_heads, linear.out_features // n_heads)
+        return torch.nn.functional.pad(value, (0, 0, 0, pad_heads))[:, :, :n_heads] if pad_heads > 0 else value
     weight, bias = linear.weight, linear.bias
     if x.is_cuda and torch.is_autocast_enabled("cuda"):
         # under torch.autocast an nn.Linear computes and returns the autocast dtype; the padded product (an out= GEMM autocast
@@ -361,6 +415,65 @@ def _sampling_dtype(raw_dtype, loc32):
     return torch.float32 if (loc32 and raw_dtype in (torch.bfloat16, torch.float16)) else raw_dtype
 
 
+def _ref_grad(gloc, off, ref, P):
+    # d loc / d ref: 1 on (x, y); boxes: d loc / d (w, h) = offsets / P * 0.5   (ref :112-121)
+    g = gloc.sum((1, 3))                                       # over heads and points -> [R, levels, 2]
+    if ref.shape[-1] == 2:
+        return g
+    return torch.cat((g, (gloc * (off.reshape(gloc.shape) / P * 0.5)).sum((1, 3))), -1)
+
+
+def _prep_forward(off_c, off_t, logit_c, logit_t, ref_c, ref_t, shapes, loc32=False):
+    """Host side of :class:`MSDeformPrepFunction`'s forward: ((loc_c, loc_t, aw_c, aw_t), (ref_c, ref_t, off_c, off_t) as
+    the backward reads them)."""
+    R, M, L, Pc, _ = off_c.shape
+    W = 0 if off_t is None else off_t.shape[2] // L
+    Pt = 1 if off_t is None else off_t.shape[3]
+    sdt = _sampling_dtype(off_c.dtype, loc32)
+    ref_c, ref_t = _check_prep_inputs(off_c, (("reference_points", ref_c), ("temporal reference_points", ref_t if W else None)), shapes, sdt)
+    _require(logit_c.dtype == off_c.dtype and logit_c.device == off_c.device, "offsets / logits must share dtype and device")
+    off_c, logit_c = off_c.contiguous(), logit_c.contiguous()
+    _require(tuple(ref_c.shape) == (R, L, ref_c.shape[-1]), "reference_points must be [rows, L, 2|4]")
+    if W:
+        _require(off_t.dtype == off_c.dtype and logit_t.dtype == off_c.dtype, "offsets / logits must share one dtype")
+        _require(tuple(ref_t.shape) == (R, W * L, ref_t.shape[-1]) and ref_t.shape[-1] == ref_c.shape[-1],
+                 "temporal reference_points must be [rows, window*L, 2|4]")
+        off_t, logit_t = off_t.contiguous(), logit_t.contiguous()
+    loc_c, aw_c = torch.empty_like(off_c, dtype=sdt), torch.empty((R, M, L, Pc), dtype=sdt, device=off_c.device)
+    loc_t = torch.empty_like(off_t, dtype=sdt) if W else None
+    aw_t = torch.empty((R, M, W * L, Pt), dtype=sdt, device=off_c.device) if W else None
+    _native.prep_forward(off_c, off_t, logit_c, logit_t, ref_c, ref_t, shapes, R, M, L, W, Pc, Pt,
+                         loc_c, loc_t, aw_c, aw_t)
+    return (loc_c, loc_t, aw_c, aw_t), (ref_c, ref_t, off_c, off_t)
+
+
+def _prep_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, ref_c, ref_t, shapes, off_c, off_t, ref_dtypes,
+                   need_ref_c, need_ref_t):
+    """Host side of :class:`MSDeformPrepFunction`'s backward (``ref_c`` / ``ref_t`` / ``off_c`` / ``off_t`` as
+    :func:`_prep_forward` returned them): (goff_c, goff_t, glogit_c, glogit_t, gref_c, gref_t)."""
+    R, M, L, Pc, _ = off_c.shape
+    W = 0 if off_t is None else off_t.shape[2] // L
+    Pt = 1 if off_t is None else off_t.shape[3]
+    zeros = lambda like: torch.zeros_like(like, dtype=aw_c.dtype)        # (the sampling-side dtype: see _sampling_dtype)
+    gloc_c = zeros(off_c) if gloc_c is None else gloc_c.contiguous()
+    gaw_c = zeros(aw_c) if gaw_c is None else gaw_c.contiguous()
+    if W:
+        gloc_t = zeros(off_t) if gloc_t is None else gloc_t.contiguous()
+        gaw_t = zeros(aw_t) if gaw_t is None else gaw_t.contiguous()
+    goff_c, glogit_c = torch.empty_like(off_c), torch.empty((R, M, L * Pc), dtype=off_c.dtype, device=off_c.device)
+    goff_t = torch.empty_like(off_t) if W else None
+    glogit_t = torch.empty((R, M, W * L * Pt), dtype=off_c.dtype, device=off_c.device) if W else None
+    _native.prep_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, ref_c, ref_t, shapes, R, M, L, W, Pc, Pt,
+                          goff_c, goff_t, glogit_c, glogit_t)
+    gref_c = _ref_grad(gloc_c, off_c, ref_c, Pc).to(ref_dtypes[0]) if need_ref_c else None
+    gref_t = _ref_grad(gloc_t, off_t, ref_t, Pt).to(ref_dtypes[1]) if (W and need_ref_t) else None
+    return goff_c, goff_t, glogit_c, glogit_t, gref_c, gref_t
+
+
+def _dtype_of(t):
+    return t.dtype if isinstance(t, torch.Tensor) else None
+
+
 class MSDeformPrepFunction(Function):
     """Joint softmax + sampling-location arithmetic of the (temporal) modules as one fused pass each way
     (include/msda.h msda_prep_forward/backward).
@@ -372,57 +485,83 @@ class MSDeformPrepFunction(Function):
 
     @staticmethod
     def forward(ctx, off_c, off_t, logit_c, logit_t, ref_c, ref_t, shapes, loc32=False):
-        R, M, L, Pc, _ = off_c.shape
-        W = 0 if off_t is None else off_t.shape[2] // L
-        Pt = 1 if off_t is None else off_t.shape[3]
-        ctx.ref_dtypes = (ref_c.dtype if isinstance(ref_c, torch.Tensor) else None,
-                          ref_t.dtype if isinstance(ref_t, torch.Tensor) else None)
-        sdt = _sampling_dtype(off_c.dtype, loc32)
-        ref_c, ref_t = _check_prep_inputs(off_c, (("reference_points", ref_c), ("temporal reference_points", ref_t if W else None)), shapes, sdt)
-        _require(logit_c.dtype == off_c.dtype and logit_c.device == off_c.device, "offsets / logits must share dtype and device")
-        off_c, logit_c = off_c.contiguous(), logit_c.contiguous()
-        _require(tuple(ref_c.shape) == (R, L, ref_c.shape[-1]), "reference_points must be [rows, L, 2|4]")
-        if W:
-            _require(off_t.dtype == off_c.dtype and logit_t.dtype == off_c.dtype, "offsets / logits must share one dtype")
-            _require(tuple(ref_t.shape) == (R, W * L, ref_t.shape[-1]) and ref_t.shape[-1] == ref_c.shape[-1],
-                     "temporal reference_points must be [rows, window*L, 2|4]")
-            off_t, logit_t = off_t.contiguous(), logit_t.contiguous()
-        loc_c, aw_c = torch.empty_like(off_c, dtype=sdt), torch.empty((R, M, L, Pc), dtype=sdt, device=off_c.device)
-        loc_t = torch.empty_like(off_t, dtype=sdt) if W else None
-        aw_t = torch.empty((R, M, W * L, Pt), dtype=sdt, device=off_c.device) if W else None
-        _native.prep_forward(off_c, off_t, logit_c, logit_t, ref_c, ref_t, shapes, R, M, L, W, Pc, Pt,
-                             loc_c, loc_t, aw_c, aw_t)
+        ctx.ref_dtypes = (_dtype_of(ref_c), _dtype_of(ref_t))
+        if torch.compiler.is_compiling():
+            ctx.loc32 = loc32
+            loc_c, loc_t, aw_c, aw_t = _ops().prep_forward(off_c, off_t, logit_c, logit_t, ref_c, ref_t, shapes, loc32)
+            if off_t is None:
+                loc_t = aw_t = None
+            ctx.save_for_backward(aw_c, aw_t, ref_c, ref_t, shapes, off_c, off_t)
+            return loc_c, loc_t, aw_c, aw_t
+        (loc_c, loc_t, aw_c, aw_t), (ref_c, ref_t, off_c, off_t) = _prep_forward(off_c, off_t, logit_c, logit_t,
+                                                                                   ref_c, ref_t, shapes, loc32)
         ctx.save_for_backward(aw_c, aw_t, ref_c, ref_t, shapes, off_c, off_t)
-        ctx.dims = (R, M, L, W, Pc, Pt)
         return loc_c, loc_t, aw_c, aw_t
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gloc_c, gloc_t, gaw_c, gaw_t):
+        if torch.compiler.is_compiling():
+            aw_c, aw_t, ref_c, ref_t, shapes, off_c, off_t = ctx.saved_tensors
+            goff_c, goff_t, glogit_c, glogit_t, gref_c, gref_t = _ops().prep_backward(
+                gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, off_c, off_t, ref_c, ref_t, shapes, ctx.loc32,
+                ctx.needs_input_grad[4], ctx.needs_input_grad[5])
+            if off_t is None:
+                goff_t = glogit_t = None
+            return (goff_c, goff_t, glogit_c, glogit_t, gref_c if ctx.needs_input_grad[4] else None,
+                    gref_t if (off_t is not None and ctx.needs_input_grad[5]) else None, None, None)
         aw_c, aw_t, ref_c, ref_t, shapes, off_c, off_t = ctx.saved_tensors
-        R, M, L, W, Pc, Pt = ctx.dims
-        zeros = lambda like: torch.zeros_like(like, dtype=aw_c.dtype)        # (the sampling-side dtype: see _sampling_dtype)
-        gloc_c = zeros(off_c) if gloc_c is None else gloc_c.contiguous()
-        gaw_c = zeros(aw_c) if gaw_c is None else gaw_c.contiguous()
-        if W:
-            gloc_t = zeros(off_t) if gloc_t is None else gloc_t.contiguous()
-            gaw_t = zeros(aw_t) if gaw_t is None else gaw_t.contiguous()
-        goff_c, glogit_c = torch.empty_like(off_c), torch.empty((R, M, L * Pc), dtype=off_c.dtype, device=off_c.device)
-        goff_t = torch.empty_like(off_t) if W else None
-        glogit_t = torch.empty((R, M, W * L * Pt), dtype=off_c.dtype, device=off_c.device) if W else None
-        _native.prep_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, ref_c, ref_t, shapes, R, M, L, W, Pc, Pt,
-                              goff_c, goff_t, glogit_c, glogit_t)
+        return _prep_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, ref_c, ref_t, shapes, off_c, off_t,
+                              ctx.ref_dtypes, ctx.needs_input_grad[4], ctx.needs_input_grad[5]) + (None, None)
 
-        def ref_grad(gloc, off, ref, P):
-            # d loc / d ref: 1 on (x, y); boxes: d loc / d (w, h) = offsets / P * 0.5   (ref :112-121)
-            g = gloc.sum((1, 3))                                       # over heads and points -> [R, levels, 2]
-            if ref.shape[-1] == 2:
-                return g
-            return torch.cat((g, (gloc * (off / P * 0.5)).sum((1, 3))), -1)
 
-        gref_c = ref_grad(gloc_c, off_c, ref_c, Pc).to(ctx.ref_dtypes[0]) if ctx.needs_input_grad[4] else None
-        gref_t = ref_grad(gloc_t, off_t, ref_t, Pt).to(ctx.ref_dtypes[1]) if (W and ctx.needs_input_grad[5]) else None
-        return goff_c, goff_t, glogit_c, glogit_t, gref_c, gref_t, None, None
+def _prep_fused_cols(M, L, W, Pc, Pt):
+    n = [M * L * Pc * 2, M * W * L * Pt * 2, M * L * Pc, M * W * L * Pt]
+    o = [0, n[0], n[0] + n[1], n[0] + n[1] + n[2]]
+    return [(a, a + b) for a, b in zip(o, n)]
+
+
+def _prep_fused_forward(y, ref_c, ref_t, shapes, M, L, W, Pc, Pt, loc32=False):
+    """Host side of :class:`MSDeformPrepFusedFunction`'s forward: ((loc_c, loc_t, aw_c, aw_t), (ref_c, ref_t, y) as the
+    backward reads them)."""
+    R = y.shape[0]
+    if y.stride(1) != 1:
+        y = y.contiguous()
+    cols = _prep_fused_cols(M, L, W, Pc, Pt)
+    assert y.shape[1] == cols[3][1]
+    v = [y[:, a:b] for a, b in cols]
+    sdt = _sampling_dtype(y.dtype, loc32)
+    ref_c, ref_t = _check_prep_inputs(y, (("reference_points", ref_c), ("temporal reference_points", ref_t if W else None)), shapes, sdt)
+    _require(tuple(ref_c.shape) == (R, L, ref_c.shape[-1]), "reference_points must be [rows, L, 2|4]")
+    if W:
+        _require(tuple(ref_t.shape) == (R, W * L, ref_t.shape[-1]) and ref_t.shape[-1] == ref_c.shape[-1],
+                 "temporal reference_points must be [rows, window*L, 2|4]")
+    loc_c = torch.empty((R, M, L, Pc, 2), dtype=sdt, device=y.device)
+    aw_c = torch.empty((R, M, L, Pc), dtype=sdt, device=y.device)
+    loc_t = torch.empty((R, M, W * L, Pt, 2), dtype=sdt, device=y.device) if W else None
+    aw_t = torch.empty((R, M, W * L, Pt), dtype=sdt, device=y.device) if W else None
+    _native.prep_forward(v[0], v[1] if W else None, v[2], v[3] if W else None, ref_c, ref_t, shapes, R, M, L, W,
+                         Pc, Pt if W else 1, loc_c, loc_t, aw_c, aw_t, ld=y.stride(0))
+    return (loc_c, loc_t, aw_c, aw_t), (ref_c, ref_t, y)
+
+
+def _prep_fused_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, ref_c, ref_t, shapes, y, M, L, W, Pc, Pt,
+                         ref_dtypes, need_ref_c, need_ref_t):
+    """Host side of :class:`MSDeformPrepFusedFunction`'s backward: (gy, gref_c, gref_t)."""
+    R = y.shape[0]
+    cols = _prep_fused_cols(M, L, W, Pc, Pt)
+    gloc_c = torch.zeros_like(aw_c).unsqueeze(-1).repeat(1, 1, 1, 1, 2) if gloc_c is None else gloc_c.contiguous()
+    gaw_c = torch.zeros_like(aw_c) if gaw_c is None else gaw_c.contiguous()
+    if W:
+        gloc_t = torch.zeros_like(aw_t).unsqueeze(-1).repeat(1, 1, 1, 1, 2) if gloc_t is None else gloc_t.contiguous()
+        gaw_t = torch.zeros_like(aw_t) if gaw_t is None else gaw_t.contiguous()
+    gy = torch.empty((R, y.shape[1]), dtype=y.dtype, device=y.device)
+    g = [gy[:, a:b] for a, b in cols]
+    _native.prep_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, ref_c, ref_t, shapes, R, M, L, W, Pc,
+                          Pt if W else 1, g[0], g[1] if W else None, g[2], g[3] if W else None, ld=gy.stride(0))
+    gref_c = _ref_grad(gloc_c, y[:, cols[0][0]:cols[0][1]], ref_c, Pc).to(ref_dtypes[0]) if need_ref_c else None
+    gref_t = _ref_grad(gloc_t, y[:, cols[1][0]:cols[1][1]], ref_t, Pt).to(ref_dtypes[1]) if (W and need_ref_t) else None
+    return gy, gref_c, gref_t
 
 
 class MSDeformPrepFusedFunction(Function):
@@ -432,61 +571,38 @@ class MSDeformPrepFusedFunction(Function):
     Linears' backward is one dgrad and one wgrad GEMM as well.  ``apply(y, ref_c, ref_t | None, shapes, M, L, W,
     Pc, Pt) -> (loc_c [R,M,L,Pc,2], loc_t, aw_c [R,M,L,Pc], aw_t)``."""
 
-    @staticmethod
-    def _cols(M, L, W, Pc, Pt):
-        n = [M * L * Pc * 2, M * W * L * Pt * 2, M * L * Pc, M * W * L * Pt]
-        o = [0, n[0], n[0] + n[1], n[0] + n[1] + n[2]]
-        return [(a, a + b) for a, b in zip(o, n)]
+    _cols = staticmethod(_prep_fused_cols)
 
     @staticmethod
     def forward(ctx, y, ref_c, ref_t, shapes, M, L, W, Pc, Pt, loc32=False):
-        R = y.shape[0]
-        if y.stride(1) != 1:
-            y = y.contiguous()
-        cols = MSDeformPrepFusedFunction._cols(M, L, W, Pc, Pt)
-        assert y.shape[1] == cols[3][1]
-        v = [y[:, a:b] for a, b in cols]
-        ctx.ref_dtypes = (ref_c.dtype if isinstance(ref_c, torch.Tensor) else None,
-                          ref_t.dtype if isinstance(ref_t, torch.Tensor) else None)
-        sdt = _sampling_dtype(y.dtype, loc32)
-        ref_c, ref_t = _check_prep_inputs(y, (("reference_points", ref_c), ("temporal reference_points", ref_t if W else None)), shapes, sdt)
-        _require(tuple(ref_c.shape) == (R, L, ref_c.shape[-1]), "reference_points must be [rows, L, 2|4]")
-        if W:
-            _require(tuple(ref_t.shape) == (R, W * L, ref_t.shape[-1]) and ref_t.shape[-1] == ref_c.shape[-1],
-                     "temporal reference_points must be [rows, window*L, 2|4]")
-        loc_c = torch.empty((R, M, L, Pc, 2), dtype=sdt, device=y.device)
-        aw_c = torch.empty((R, M, L, Pc), dtype=sdt, device=y.device)
-        loc_t = torch.empty((R, M, W * L, Pt, 2), dtype=sdt, device=y.device) if W else None
-        aw_t = torch.empty((R, M, W * L, Pt), dtype=sdt, device=y.device) if W else None
-        _native.prep_forward(v[0], v[1] if W else None, v[2], v[3] if W else None, ref_c, ref_t, shapes, R, M, L, W,
-                             Pc, Pt if W else 1, loc_c, loc_t, aw_c, aw_t, ld=y.stride(0))
+        ctx.ref_dtypes = (_dtype_of(ref_c), _dtype_of(ref_t))
+        ctx.dims = (M, L, W, Pc, Pt)
+        if torch.compiler.is_compiling():
+            ctx.loc32 = loc32
+            ref_t = ref_t if W else None
+            loc_c, loc_t, aw_c, aw_t = _ops().prep_fused_forward(y, ref_c, ref_t, shapes, M, L, W, Pc, Pt, loc32)
+            if not W:
+                loc_t = aw_t = None
+            ctx.save_for_backward(aw_c, aw_t, ref_c, ref_t, shapes, y)
+            return loc_c, loc_t, aw_c, aw_t
+        (loc_c, loc_t, aw_c, aw_t), (ref_c, ref_t, y) = _prep_fused_forward(y, ref_c, ref_t, shapes, M, L, W, Pc, Pt,
+                                                                            loc32)
         ctx.save_for_backward(aw_c, aw_t, ref_c, ref_t, shapes, y)
-        ctx.dims = (R, M, L, W, Pc, Pt)
         return loc_c, loc_t, aw_c, aw_t
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gloc_c, gloc_t, gaw_c, gaw_t):
+        M, L, W, Pc, Pt = ctx.dims
+        if torch.compiler.is_compiling():
+            aw_c, aw_t, ref_c, ref_t, shapes, y = ctx.saved_tensors
+            gy, gref_c, gref_t = _ops().prep_fused_backward(
+                gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, y, ref_c, ref_t, shapes, M, L, W, Pc, Pt, ctx.loc32,
+                ctx.needs_input_grad[1], bool(W) and ctx.needs_input_grad[2])
+            return (gy, gref_c if ctx.needs_input_grad[1] else None, gref_t if (W and ctx.needs_input_grad[2]) else None,
+                    None, None, None, None, None, None, None)
         aw_c, aw_t, ref_c, ref_t, shapes, y = ctx.saved_tensors
-        R, M, L, W, Pc, Pt = ctx.dims
-        cols = MSDeformPrepFusedFunction._cols(M, L, W, Pc, Pt)
-        gloc_c = torch.zeros_like(aw_c).unsqueeze(-1).repeat(1, 1, 1, 1, 2) if gloc_c is None else gloc_c.contiguous()
-        gaw_c = torch.zeros_like(aw_c) if gaw_c is None else gaw_c.contiguous()
-        if W:
-            gloc_t = torch.zeros_like(aw_t).unsqueeze(-1).repeat(1, 1, 1, 1, 2) if gloc_t is None else gloc_t.contiguous()
-            gaw_t = torch.zeros_like(aw_t) if gaw_t is None else gaw_t.contiguous()
-        gy = torch.empty((R, y.shape[1]), dtype=y.dtype, device=y.device)
-        g = [gy[:, a:b] for a, b in cols]
-        _native.prep_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, ref_c, ref_t, shapes, R, M, L, W, Pc,
-                              Pt if W else 1, g[0], g[1] if W else None, g[2], g[3] if W else None, ld=gy.stride(0))
-
-        def ref_grad(gloc, off2d, ref, P):
-            gsum = gloc.sum((1, 3))
-            if ref.shape[-1] == 2:
-                return gsum
-            off = off2d.reshape(gloc.shape)
-            return torch.cat((gsum, (gloc * (off / P * 0.5)).sum((1, 3))), -1)
-
-        gref_c = ref_grad(gloc_c, y[:, cols[0][0]:cols[0][1]], ref_c, Pc).to(ctx.ref_dtypes[0]) if ctx.needs_input_grad[1] else None
-        gref_t = ref_grad(gloc_t, y[:, cols[1][0]:cols[1][1]], ref_t, Pt).to(ctx.ref_dtypes[1]) if (W and ctx.needs_input_grad[2]) else None
+        gy, gref_c, gref_t = _prep_fused_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, ref_c, ref_t, shapes, y,
+                                                  M, L, W, Pc, Pt, ctx.ref_dtypes, ctx.needs_input_grad[1],
+                                                  ctx.needs_input_grad[2])
         return gy, gref_c, gref_t, None, None, None, None, None, None, None

@@ -20,6 +20,7 @@ from torch import nn
 from torch.nn.init import constant_, xavier_uniform_
 
 from .. import _native
+from .. import ops as _ops
 from ..functions import (MSDeformAttnFunction, MSDeformAttnTemporalFunction, MSDeformPrepFunction,
                          MSDeformPrepFusedFunction, project_value)
 
@@ -66,6 +67,9 @@ def _fused_linear_params(module, linears):
     and code that writes ``p.data`` of a live model calls ``module.invalidate_fused_params()``.  Under
     ``torch.inference_mode()`` nothing is cached (inference tensors could not be saved for a later backward)."""
     params = [q for lin in linears for q in (lin.weight, lin.bias)]
+    if torch.compiler.is_compiling():
+        # traced: the concatenation is part of the graph (the compiler may fuse it away; no Python cache in a graph)
+        return torch.cat([l.weight for l in linears]), torch.cat([l.bias for l in linears])
     if torch.is_grad_enabled() and any(q.requires_grad for q in params):
         return torch.cat([l.weight for l in linears]), torch.cat([l.bias for l in linears])
     if torch.is_inference_mode_enabled():
@@ -172,9 +176,12 @@ class MSDeformAttn(_FusedParamsCache, nn.Module):
         """
         N, Len_q, _ = query.shape
         N, Len_in, _ = input_flatten.shape
+        compiling = torch.compiler.is_compiling()
         # ref :96 (``assert (shapes[:, 0] * shapes[:, 1]).sum() == Len_in``: a device read per call there); here against the cached
         # host copy of the tensor -- one read per distinct ``spatial_shapes`` tensor, none inside a HIP-graph capture
-        hint = _native.shapes_hint(input_spatial_shapes) if input_spatial_shapes.is_cuda else input_spatial_shapes.reshape(-1).tolist()
+        # (under torch.compile / export the operator's custom op makes this check at run time: check_spatial_size)
+        hint = None if compiling else \
+            _native.shapes_hint(input_spatial_shapes) if input_spatial_shapes.is_cuda else input_spatial_shapes.reshape(-1).tolist()
         if hint is not None:
             assert sum(int(hint[2 * l]) * int(hint[2 * l + 1]) for l in range(len(hint) // 2)) == Len_in
         M, L, P = self.n_heads, self.n_levels, self.n_points
@@ -200,8 +207,12 @@ class MSDeformAttn(_FusedParamsCache, nn.Module):
             weights = weights.view(N, Len_q, M, L, P)
             locations = _locations(reference_points[:, :, None, :, None, :], offsets,
                                    _normalizer(input_spatial_shapes), P)
-        output = MSDeformAttnFunction.apply(value, input_spatial_shapes, input_level_start_index, locations.contiguous(),
-                                            weights.contiguous(), self.im2col_step, input_padding_mask)
+        if compiling:
+            output = _ops.ms_deform_attn_forward(value, input_spatial_shapes, input_level_start_index, locations.contiguous(),
+                                                 weights.contiguous(), self.im2col_step, input_padding_mask, True)
+        else:
+            output = MSDeformAttnFunction.apply(value, input_spatial_shapes, input_level_start_index, locations.contiguous(),
+                                                weights.contiguous(), self.im2col_step, input_padding_mask)
         output = self.output_proj(output)
         _flush_offset_checks(output)
         return output, None
@@ -305,7 +316,10 @@ def _capturing(t):
 
 
 def _flush_offset_checks(like):
-    """End of a temporal module's forward: raise for any range check whose verdict has reached the host by now (no wait)."""
+    """End of a temporal module's forward: raise for any range check whose verdict has reached the host by now (no wait).
+    Not in a traced graph: there the next ``frame_table`` op raises it."""
+    if torch.compiler.is_compiling():
+        return
     if like.is_cuda and torch.cuda.is_current_stream_capturing():
         return
     _FRAME_TABLES.flush()
@@ -428,7 +442,9 @@ class TemporalMSDeformAttnBase(_FusedParamsCache, nn.Module):
     @staticmethod
     def _frame_table(temporal_offsets, n_frames, device):
         """[T, W] absolute frame indices: frame_table[t] = temporal_offsets[t] + t (ref :339, :445); see
-        :meth:`_FrameTables.get`."""
+        :meth:`_FrameTables.get`; under torch.compile / export the ``frame_table`` custom op, which does the same at run time."""
+        if torch.compiler.is_compiling():
+            return _ops.frame_table(list(temporal_offsets), n_frames, torch.device(device))
         return _FRAME_TABLES.get(temporal_offsets, n_frames, device)
 
     def _attend(self, value, shapes, level_start, temporal_offsets, loc_curr, w_curr, loc_temp, w_temp):

@@ -1,0 +1,342 @@
+"""The operator as ``torch.library`` custom ops (namespace ``devis_amd``), for ``torch.compile`` and ``torch.export``.
+
+Eager code never dispatches through these: the autograd Functions of :mod:`devis_amd.functions` and the modules call the
+host code directly and switch to the ops only while ``torch.compiler.is_compiling()`` (Dynamo tracing, or export).  To the
+compiler each op is one opaque node whose implementation is that same host code -- the same checks, the same kernels
+through the C ABI, the same numbers -- and whose fake implementation gives shapes and dtypes only:
+
+=============================  ==========================================================================================
+``ms_deform_attn_forward``     ``MSDeformAttnFunction`` forward (the im2col chunk loop), + the module's ``sum(H*W) == S``
+``ms_deform_attn_backward``    ``MSDeformAttnFunction`` backward -> (grad_value, grad_loc, grad_aw)
+``temporal_forward/backward``  ``MSDeformAttnTemporalFunction``
+``prep_forward/backward``      ``MSDeformPrepFunction`` (no temporal part: ``loc_t`` / ``aw_t`` come back with 0 slots)
+``prep_fused_forward/backward``  ``MSDeformPrepFusedFunction``
+``frame_table``                the temporal modules' frame table ``[T, W]`` int32 (cache and deferred range checks)
+=============================  ==========================================================================================
+
+Everything that reads the host or keeps Python state -- the ``spatial_shapes`` host hint, the frame-table cache, the
+deferred verdicts of the temporal-offset range checks -- runs inside the implementations, at run time, never in a traced
+graph.  The implementations look ``_native`` and ``ms_deform_attn_func._check_inputs`` up at call time.  The forward ops
+carry their autograd formula (the backward op); a second derivative raises, as ``once_differentiable`` does in eager.
+Every op is tagged ``needs_fixed_stride_order``: Inductor hands over the strides eager would (e.g. the padded rows of
+``value``) instead of contiguous copies.
+
+When the package is imported a second time under another name (DeVIS's ``src.models.ops``), that copy registers its ops
+under a namespace of its own (``devis_amd_src_models_ops``), bound to its own ``_native``.
+"""
+import re
+from typing import List, Optional
+
+import torch
+from torch import Tensor
+
+from . import _native
+from .functions import ms_deform_attn_func as _F
+
+
+def _namespace():
+    pkg = __name__.rsplit(".", 1)[0]
+    base = "devis_amd" if pkg == "devis_amd" else "devis_amd_" + re.sub(r"\W", "_", pkg)
+    ns, k = base, 1
+    while hasattr(getattr(torch.ops, ns), "frame_table"):      # already taken (a re-import): the next free one
+        ns, k = "%s_%d" % (base, k), k + 1
+    return ns
+
+
+NAMESPACE = _namespace()
+_TAGS = (torch.Tag.needs_fixed_stride_order,)
+
+
+def _op(name):
+    return torch.library.custom_op("%s::%s" % (NAMESPACE, name), mutates_args=(), tags=_TAGS)
+
+
+def _empty(like, shape, dtype=None):
+    return torch.empty(shape, dtype=dtype or like.dtype, device=like.device)
+
+
+# ---- MSDeformAttnFunction ------------------------------------------------------------------------------------------
+
+@_op("ms_deform_attn_forward")
+def ms_deform_attn_forward(value: Tensor, spatial_shapes: Tensor, level_start_index: Tensor, sampling_loc: Tensor,
+                           attn_weight: Tensor, im2col_step: int, padding_mask: Optional[Tensor] = None,
+                           check_spatial_size: bool = False) -> Tensor:
+    """``MSDeformAttnFunction.forward``.  ``check_spatial_size``: assert ``sum(H*W) == value.shape[1]`` as
+    ``MSDeformAttn.forward`` does (ref ms_deform_attn.py:96), from the cached host copy of ``spatial_shapes``."""
+    if check_spatial_size:
+        hint = _native.shapes_hint(spatial_shapes) if spatial_shapes.is_cuda else spatial_shapes.reshape(-1).tolist()
+        if hint is not None:
+            assert sum(int(hint[2 * l]) * int(hint[2 * l + 1]) for l in range(len(hint) // 2)) == value.shape[1]
+    return _F._forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step, padding_mask)
+
+
+@ms_deform_attn_forward.register_fake
+def _(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step, padding_mask=None,
+      check_spatial_size=False):
+    if padding_mask is not None:
+        _F._require(padding_mask.dtype == torch.bool and padding_mask.numel() == value.shape[0] * value.shape[1],
+                    "padding_mask must be a bool [N, S] tensor on value's device")
+    _F._check_op_shapes(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
+    N, S, M, D = value.shape
+    Lq = sampling_loc.shape[1]
+    if N > 0 and Lq > 0:
+        _F._im2col_step(N, im2col_step)
+    return _empty(value, (N, Lq, M * D))
+
+
+@_op("ms_deform_attn_backward")
+def ms_deform_attn_backward(value: Tensor, spatial_shapes: Tensor, level_start_index: Tensor, sampling_loc: Tensor,
+                            attn_weight: Tensor, grad_output: Tensor, im2col_step: int,
+                            padding_mask: Optional[Tensor] = None) -> tuple[Tensor, Tensor, Tensor]:
+    """``MSDeformAttnFunction.backward``: (grad_value in value's dtype, grad_sampling_loc, grad_attn_weight)."""
+    # (eager checks these once, in the forward; here the compiler chose what arrives)
+    _F._check_inputs([("value", value), ("spatial_shapes", spatial_shapes), ("level_start_index", level_start_index),
+                      ("sampling_loc", sampling_loc), ("attn_weight", attn_weight)])
+    return _F._backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step,
+                        padding_mask)
+
+
+@ms_deform_attn_backward.register_fake
+def _(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step, padding_mask=None):
+    return _empty(value, value.shape), torch.empty_like(sampling_loc), torch.empty_like(attn_weight)
+
+
+def _setup_forward(ctx, inputs, output):
+    value, shapes, lsi, loc, aw, im2col_step, padding_mask = inputs[:7]
+    ctx.im2col_step = im2col_step
+    ctx.save_for_backward(value, shapes, lsi, loc, aw, padding_mask)
+
+
+def _backward_forward(ctx, grad_output):
+    value, shapes, lsi, loc, aw, padding_mask = ctx.saved_tensors
+    gv, gl, ga = ms_deform_attn_backward(value, shapes, lsi, loc, aw, grad_output, ctx.im2col_step, padding_mask)
+    return gv, None, None, gl, ga, None, None, None
+
+
+ms_deform_attn_forward.register_autograd(_backward_forward, setup_context=_setup_forward)
+
+
+# ---- MSDeformAttnTemporalFunction ----------------------------------------------------------------------------------
+
+@_op("temporal_forward")
+def temporal_forward(value: Tensor, spatial_shapes: Tensor, level_start_index: Tensor, frame_table: Tensor,
+                     loc_curr: Tensor, aw_curr: Tensor, loc_temp: Tensor, aw_temp: Tensor, clips: int) -> Tensor:
+    """``MSDeformAttnTemporalFunction.forward``: [clips*T, Lq, M*D]."""
+    return _F._temporal_forward(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, loc_temp,
+                                aw_temp, clips)
+
+
+@temporal_forward.register_fake
+def _(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, loc_temp, aw_temp, clips):
+    _F._check_temporal_shapes(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, loc_temp,
+                              aw_temp, clips)
+    G, S, M, D = value.shape
+    return _empty(value, (G, loc_curr.shape[1], M * D))
+
+
+@_op("temporal_backward")
+def temporal_backward(value: Tensor, spatial_shapes: Tensor, level_start_index: Tensor, frame_table: Tensor,
+                      loc_curr: Tensor, aw_curr: Tensor, loc_temp: Tensor, aw_temp: Tensor, grad_output: Tensor,
+                      clips: int) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """``MSDeformAttnTemporalFunction.backward``: (grad_value, grad_loc_curr, grad_aw_curr, grad_loc_temp, grad_aw_temp)."""
+    _F._check_inputs([("value", value), ("spatial_shapes", spatial_shapes), ("level_start_index", level_start_index),
+                      ("frame_table", frame_table), ("loc_curr", loc_curr), ("aw_curr", aw_curr), ("loc_temp", loc_temp),
+                      ("aw_temp", aw_temp)])
+    return _F._temporal_backward(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, loc_temp,
+                                 aw_temp, grad_output, clips)
+
+
+@temporal_backward.register_fake
+def _(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, loc_temp, aw_temp, grad_output, clips):
+    return (_empty(value, value.shape), torch.empty_like(loc_curr), torch.empty_like(aw_curr),
+            torch.empty_like(loc_temp), torch.empty_like(aw_temp))
+
+
+def _setup_temporal(ctx, inputs, output):
+    ctx.clips = inputs[8]
+    ctx.save_for_backward(*inputs[:8])
+
+
+def _backward_temporal(ctx, grad_output):
+    value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t = ctx.saved_tensors
+    gv, glc, gac, glt, gat = temporal_backward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_output, ctx.clips)
+    return gv, None, None, None, glc, gac, glt, gat, None
+
+
+temporal_forward.register_autograd(_backward_temporal, setup_context=_setup_temporal)
+
+
+# ---- MSDeformPrepFunction ------------------------------------------------------------------------------------------
+# Outputs that do not exist without a temporal part (loc_t, aw_t and their gradients) are tensors with 0 slots here:
+# a custom op returns tensors, not None.
+
+def _none_slot(t):
+    return t if t is not None and t.numel() else None
+
+
+def _prep_dims(off_c, off_t):
+    R, M, L, Pc, _ = off_c.shape
+    W = 0 if off_t is None else off_t.shape[2] // L
+    Pt = 1 if off_t is None else off_t.shape[3]
+    return R, M, L, W, Pc, Pt
+
+
+@_op("prep_forward")
+def prep_forward(off_c: Tensor, off_t: Optional[Tensor], logit_c: Tensor, logit_t: Optional[Tensor], ref_c: Tensor,
+                 ref_t: Optional[Tensor], spatial_shapes: Tensor, loc32: bool = False
+                 ) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``MSDeformPrepFunction.forward``: (loc_c, loc_t, aw_c, aw_t)."""
+    (loc_c, loc_t, aw_c, aw_t), _ = _F._prep_forward(off_c, off_t, logit_c, logit_t, ref_c, ref_t, spatial_shapes, loc32)
+    if loc_t is None:
+        loc_t, aw_t = _fake_prep_forward(off_c, off_t, logit_c, logit_t, ref_c, ref_t, spatial_shapes, loc32)[1::2]
+    return loc_c, loc_t, aw_c, aw_t
+
+
+@prep_forward.register_fake
+def _fake_prep_forward(off_c, off_t, logit_c, logit_t, ref_c, ref_t, spatial_shapes, loc32=False):
+    R, M, L, W, Pc, Pt = _prep_dims(off_c, off_t)
+    sdt = _F._sampling_dtype(off_c.dtype, loc32)
+    _F._require(logit_c.dtype == off_c.dtype, "offsets / logits must share dtype and device")
+    _F._require(tuple(ref_c.shape) == (R, L, ref_c.shape[-1]), "reference_points must be [rows, L, 2|4]")
+    return (_empty(off_c, off_c.shape, sdt), _empty(off_c, (R, M, W * L, Pt, 2), sdt),
+            _empty(off_c, (R, M, L, Pc), sdt), _empty(off_c, (R, M, W * L, Pt), sdt))
+
+
+@_op("prep_backward")
+def prep_backward(gloc_c: Optional[Tensor], gloc_t: Optional[Tensor], gaw_c: Optional[Tensor], gaw_t: Optional[Tensor],
+                  aw_c: Tensor, aw_t: Optional[Tensor], off_c: Tensor, off_t: Optional[Tensor], ref_c: Tensor,
+                  ref_t: Optional[Tensor], spatial_shapes: Tensor, loc32: bool = False, need_ref_c: bool = True,
+                  need_ref_t: bool = True) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """``MSDeformPrepFunction.backward`` from the forward's INPUTS (``off_*``, ``ref_*`` as given) and ``aw_*`` outputs:
+    (grad_off_c, grad_off_t, grad_logit_c, grad_logit_t, grad_ref_c, grad_ref_t); a reference-point gradient that is
+    not asked for (``need_ref_*``) comes back with 0 elements."""
+    off_t, aw_t = _none_slot(off_t), _none_slot(aw_t)
+    aw_c, aw_t = aw_c.contiguous(), None if aw_t is None else aw_t.contiguous()
+    ref_dtypes = (ref_c.dtype, None if ref_t is None else ref_t.dtype)
+    W = _prep_dims(off_c, off_t)[3]
+    sdt = aw_c.dtype
+    ref_c2, ref_t2 = _F._check_prep_inputs(off_c, (("reference_points", ref_c),
+                                                   ("temporal reference_points", ref_t if W else None)), spatial_shapes, sdt)
+    g = _F._prep_backward(_none_slot(gloc_c), _none_slot(gloc_t) if W else None, _none_slot(gaw_c),
+                          _none_slot(gaw_t) if W else None, aw_c, aw_t, ref_c2, ref_t2, spatial_shapes, off_c.contiguous(),
+                          None if off_t is None else off_t.contiguous(), ref_dtypes, need_ref_c, need_ref_t)
+    fake = _fake_prep_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, off_c, off_t, ref_c, ref_t, spatial_shapes,
+                               loc32, need_ref_c, need_ref_t)
+    return tuple(f if x is None else x for x, f in zip(g, fake))
+
+
+@prep_backward.register_fake
+def _fake_prep_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, off_c, off_t, ref_c, ref_t, spatial_shapes,
+                        loc32=False, need_ref_c=True, need_ref_t=True):
+    R, M, L, W, Pc, Pt = _prep_dims(off_c, off_t)
+    d = ref_c.shape[-1]
+    return (_empty(off_c, off_c.shape), _empty(off_c, (R, M, W * L, Pt, 2)), _empty(off_c, (R, M, L * Pc)),
+            _empty(off_c, (R, M, W * L * Pt)), _empty(ref_c, (R, L, d) if need_ref_c else (0,)),
+            _empty(ref_c if ref_t is None else ref_t, (R, W * L, d) if (W and need_ref_t) else (0,)))
+
+
+def _setup_prep(ctx, inputs, output):
+    off_c, off_t, logit_c, logit_t, ref_c, ref_t, shapes, loc32 = inputs
+    ctx.loc32 = loc32
+    ctx.save_for_backward(output[2], output[3], off_c, off_t, ref_c, ref_t, shapes)
+
+
+def _backward_prep(ctx, gloc_c, gloc_t, gaw_c, gaw_t):
+    aw_c, aw_t, off_c, off_t, ref_c, ref_t, shapes = ctx.saved_tensors
+    nc, nt = ctx.needs_input_grad[4], ctx.needs_input_grad[5] and ref_t is not None
+    goff_c, goff_t, glogit_c, glogit_t, gref_c, gref_t = prep_backward(
+        gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, off_c, off_t, ref_c, ref_t, shapes, ctx.loc32, nc, nt)
+    w = off_t is not None
+    return (goff_c, goff_t if w else None, glogit_c, glogit_t if w else None, gref_c if nc else None,
+            gref_t if (w and nt) else None, None, None)
+
+
+prep_forward.register_autograd(_backward_prep, setup_context=_setup_prep)
+
+
+# ---- MSDeformPrepFusedFunction -------------------------------------------------------------------------------------
+
+@_op("prep_fused_forward")
+def prep_fused_forward(y: Tensor, ref_c: Tensor, ref_t: Optional[Tensor], spatial_shapes: Tensor, M: int, L: int, W: int,
+                       Pc: int, Pt: int, loc32: bool = False) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``MSDeformPrepFusedFunction.forward``: (loc_c, loc_t, aw_c, aw_t)."""
+    (loc_c, loc_t, aw_c, aw_t), _ = _F._prep_fused_forward(y, ref_c, ref_t, spatial_shapes, M, L, W, Pc, Pt, loc32)
+    if not W:
+        loc_t, aw_t = _fake_prep_fused_forward(y, ref_c, ref_t, spatial_shapes, M, L, W, Pc, Pt, loc32)[1::2]
+    return loc_c, loc_t, aw_c, aw_t
+
+
+@prep_fused_forward.register_fake
+def _fake_prep_fused_forward(y, ref_c, ref_t, spatial_shapes, M, L, W, Pc, Pt, loc32=False):
+    R = y.shape[0]
+    cols = _F._prep_fused_cols(M, L, W, Pc, Pt)
+    _F._require(y.dim() == 2 and y.shape[1] == cols[3][1], "y must be [rows, %d]" % cols[3][1])
+    _F._require(tuple(ref_c.shape) == (R, L, ref_c.shape[-1]), "reference_points must be [rows, L, 2|4]")
+    sdt = _F._sampling_dtype(y.dtype, loc32)
+    return (_empty(y, (R, M, L, Pc, 2), sdt), _empty(y, (R, M, W * L, Pt, 2), sdt),
+            _empty(y, (R, M, L, Pc), sdt), _empty(y, (R, M, W * L, Pt), sdt))
+
+
+@_op("prep_fused_backward")
+def prep_fused_backward(gloc_c: Optional[Tensor], gloc_t: Optional[Tensor], gaw_c: Optional[Tensor],
+                        gaw_t: Optional[Tensor], aw_c: Tensor, aw_t: Optional[Tensor], y: Tensor, ref_c: Tensor,
+                        ref_t: Optional[Tensor], spatial_shapes: Tensor, M: int, L: int, W: int, Pc: int, Pt: int,
+                        loc32: bool = False, need_ref_c: bool = True, need_ref_t: bool = True
+                        ) -> tuple[Tensor, Tensor, Tensor]:
+    """``MSDeformPrepFusedFunction.backward`` from the forward's inputs and ``aw_*`` outputs: (grad_y, grad_ref_c,
+    grad_ref_t); a reference-point gradient that is not asked for comes back with 0 elements."""
+    if y.stride(1) != 1:
+        y = y.contiguous()
+    aw_c, aw_t = aw_c.contiguous(), None if aw_t is None else aw_t.contiguous()
+    ref_dtypes = (ref_c.dtype, None if ref_t is None else ref_t.dtype)
+    ref_c2, ref_t2 = _F._check_prep_inputs(y, (("reference_points", ref_c), ("temporal reference_points", ref_t if W else None)),
+                                           spatial_shapes, aw_c.dtype)
+    g = _F._prep_fused_backward(gloc_c, gloc_t if W else None, gaw_c, gaw_t if W else None, aw_c, aw_t if W else None,
+                                ref_c2, ref_t2, spatial_shapes, y, M, L, W, Pc, Pt, ref_dtypes, need_ref_c, need_ref_t)
+    fake = _fake_prep_fused_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, y, ref_c, ref_t, spatial_shapes, M, L, W,
+                                     Pc, Pt, loc32, need_ref_c, need_ref_t)
+    return tuple(f if x is None else x for x, f in zip(g, fake))
+
+
+@prep_fused_backward.register_fake
+def _fake_prep_fused_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, y, ref_c, ref_t, spatial_shapes, M, L, W, Pc, Pt,
+                              loc32=False, need_ref_c=True, need_ref_t=True):
+    R = y.shape[0]
+    d = ref_c.shape[-1]
+    return (_empty(y, (R, y.shape[1])), _empty(ref_c, (R, L, d) if need_ref_c else (0,)),
+            _empty(ref_c if ref_t is None else ref_t, (R, W * L, d) if (W and need_ref_t) else (0,)))
+
+
+def _setup_prep_fused(ctx, inputs, output):
+    y, ref_c, ref_t, shapes, M, L, W, Pc, Pt, loc32 = inputs
+    ctx.dims = (M, L, W, Pc, Pt, loc32)
+    ctx.save_for_backward(output[2], output[3], y, ref_c, ref_t, shapes)
+
+
+def _backward_prep_fused(ctx, gloc_c, gloc_t, gaw_c, gaw_t):
+    aw_c, aw_t, y, ref_c, ref_t, shapes = ctx.saved_tensors
+    M, L, W, Pc, Pt, loc32 = ctx.dims
+    nc, nt = ctx.needs_input_grad[1], bool(W) and ref_t is not None and ctx.needs_input_grad[2]
+    gy, gref_c, gref_t = prep_fused_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, y, ref_c, ref_t, shapes,
+                                             M, L, W, Pc, Pt, loc32, nc, nt)
+    return gy, gref_c if nc else None, gref_t if nt else None, None, None, None, None, None, None, None
+
+
+prep_fused_forward.register_autograd(_backward_prep_fused, setup_context=_setup_prep_fused)
+
+
+# ---- frame table ---------------------------------------------------------------------------------------------------
+
+@_op("frame_table")
+def frame_table(offsets: List[Tensor], n_frames: int, device: torch.device) -> Tensor:
+    """``TemporalMSDeformAttnBase._frame_table``: [T, W] int32 absolute frame ids on `device`.  Served from the frame-table
+    cache and range-checked as in eager (IndexError; a pending verdict of an earlier device-side check is raised here)."""
+    from .modules import ms_deform_attn as _mod
+    # a copy: the compiled graph owns the op's output (Inductor may reuse its memory), the cache keeps its own
+    return _mod._FRAME_TABLES.get(offsets, n_frames, torch.device(device)).clone()
+
+
+@frame_table.register_fake
+def _(offsets, n_frames, device):
+    _F._require(len(offsets) > 0, "frame_table needs the temporal offsets of at least one frame")
+    return torch.empty((n_frames, offsets[0].shape[0]), dtype=torch.int32, device=device)

@@ -10,6 +10,10 @@ Put it on the import path -- ``pip install .`` at the repository root installs i
 the same binding (host shape hints, 16-bit ``grad_value``, fused temporal entry points); this one keeps to what the
 reference's extension offers.
 
+Under ``torch.compile`` / ``torch.export`` the two functions dispatch to custom ops registered here (namespace
+``MultiScaleDeformableAttention``, so this file works without ``devis_amd``): the reference's own ``MSDeformAttnFunction`` then
+compiles without a graph break, and runs the same host code as in eager.
+
 The library is looked for, in this order: ``$MSDA_LIB``; ``libmsda_hip.so`` inside an importable ``devis_amd`` package
 (built on first use by ``devis_amd.build`` when hipcc is there); ``../devis_amd/libmsda_hip.so`` relative to this file (a
 source checkout).  There is no CPU fallback.
@@ -76,8 +80,7 @@ def _check_inputs(*tensors):                                 # ms_deform_attn_cu
             raise RuntimeError("%s must be a CUDA tensor" % name)
 
 
-def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step):
-    """``vision.cpp:14`` -> ``ms_deform_attn_cuda.cu:20-80``: [N, Lq, M*D]."""
+def _forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step):
     _check_inputs(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
     N, S, M, D = value.shape
     _, Lq, _, L, P, _ = sampling_loc.shape
@@ -93,8 +96,7 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     return out
 
 
-def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step):
-    """``vision.cpp:15`` -> ``ms_deform_attn_cuda.cu:83-153``: [grad_value, grad_sampling_loc, grad_attn_weight]."""
+def _backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step):
     grad_output = grad_output.contiguous()
     _check_inputs(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output)
     N, S, M, D = value.shape
@@ -114,3 +116,56 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
                                     step, S, M, D, L, Lq, P, gv[n:].data_ptr(), _DT[acc], gl[n:].data_ptr(),
                                     ga[n:].data_ptr(), ws.data_ptr(), nws, None, None, st))
     return [gv.to(value.dtype), gl, ga]
+
+
+# ---- torch.compile / torch.export: the two entry points as custom ops ---------------------------------------------------
+_is_compiling = getattr(getattr(torch, "compiler", None), "is_compiling", lambda: False)
+
+
+def _register_ops():
+    if not hasattr(getattr(torch, "library", None), "custom_op"):       # torch < 2.4: eager only
+        return None
+    ns, k = "MultiScaleDeformableAttention", 1
+    while hasattr(getattr(torch.ops, ns), "ms_deform_attn_forward"):   # this file imported again (another copy / a reload)
+        ns, k = "MultiScaleDeformableAttention_%d" % k, k + 1
+    tags = (torch.Tag.needs_fixed_stride_order,)
+
+    @torch.library.custom_op(ns + "::ms_deform_attn_forward", mutates_args=(), tags=tags)
+    def fwd(value: torch.Tensor, spatial_shapes: torch.Tensor, level_start_index: torch.Tensor, sampling_loc: torch.Tensor,
+            attn_weight: torch.Tensor, im2col_step: int) -> torch.Tensor:
+        return _forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step)
+
+    @fwd.register_fake
+    def _(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step):
+        N, S, M, D = value.shape
+        if N > 0:
+            _step(N, im2col_step)
+        return value.new_empty((N, sampling_loc.shape[1], M * D))
+
+    @torch.library.custom_op(ns + "::ms_deform_attn_backward", mutates_args=(), tags=tags)
+    def bwd(value: torch.Tensor, spatial_shapes: torch.Tensor, level_start_index: torch.Tensor, sampling_loc: torch.Tensor,
+            attn_weight: torch.Tensor, grad_output: torch.Tensor, im2col_step: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        return tuple(_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step))
+
+    @bwd.register_fake
+    def _(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step):
+        return value.new_empty(value.shape), torch.empty_like(sampling_loc), torch.empty_like(attn_weight)
+
+    return fwd, bwd
+
+
+_ops = _register_ops()
+
+
+def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step):
+    """``vision.cpp:14`` -> ``ms_deform_attn_cuda.cu:20-80``: [N, Lq, M*D]."""
+    if _ops is not None and _is_compiling():
+        return _ops[0](value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step)
+    return _forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step)
+
+
+def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step):
+    """``vision.cpp:15`` -> ``ms_deform_attn_cuda.cu:83-153``: [grad_value, grad_sampling_loc, grad_attn_weight]."""
+    if _ops is not None and _is_compiling():
+        return list(_ops[1](value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step))
+    return _backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step)
