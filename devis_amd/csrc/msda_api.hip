@@ -21,11 +21,7 @@ thread_local char g_route[512] = "";     // kernels launched by the last entry-p
 
 int check_launch(const char *what)
 {
-    size_t used = strlen(g_route);
-    if (MSDA_IS_TIMING_ONLY && used == 0) {       // a library with timing-only kernels compiled in says so in every route
-        snprintf(g_route, sizeof(g_route), "TIMING-ONLY BUILD (results are wrong by construction)");
-        used = strlen(g_route);
-    }
+    const size_t used = strlen(g_route);
     if (used + 3 < sizeof(g_route)) snprintf(g_route + used, sizeof(g_route) - used, "%s%s", used ? "; " : "", what);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -54,7 +50,6 @@ struct Knobs {
     int fwd_rs = -1, fwd_rs_nt = 0;     // resident-slab forward: -1 auto, 0 off, 1 force; tiles per wave (0 = auto)
     int bwd_rs = -1, bwd_rs_tpw = 0;    // resident-slab gather pass: -1 auto, 0 off, 1 force; tiles per wave (0 = auto)
     int fwd_tile_waves = -1;            // forward tile kernel: waves per tile (-1 auto)
-    int fwd_rs_body = -1;               // resident-slab forward: slot body compiled for a slab from level 1 / 2 (-1: the rule in launch_fast)
     int bwd_rs_fsplit = -1;             // gather pass with one source frame per workgroup: parts per (clip, head, frame); -1 auto, 0 off
     int fwd_win = -1, bwd_win = -1;     // resident-window kernels (encoder-shaped calls): -1 auto, 0 off, 1 force
     int win_min_halo = 5;               // narrowest halo a window plan may have; one staging phase is preferred from here on (5 holds
@@ -63,16 +58,12 @@ struct Knobs {
     int bwd_phases = 3;                 // 1 = gather pass only, 2 = scatter pass only, 3 = both
     int bwd_cull = 1;                   // 0: no culling structure, 2: (min, max) intervals instead of per-point records
     int bwd_all_records = 0;            // measurement: the gather pass leaves records for every level (a later scatter-only call may walk them)
-    int bwd_summary = 1;                // 64-query block summaries for long candidate ranges
     int scatter_lds_kb = 144, scatter_dbg = 0;
     int scatter_own = -1;               // owner-computes scatter: -1 auto, 0 off (the LDS-atomic scatter instead)
     int scatter_mfma = -1;              // matrix-pipe scatter of the coarse levels (msda_mfma.hip): -1 auto, 0 off, 1 wherever it applies
     int scatter_part = 0;               // measurement: 1 = only the owner-computes kernel of a scatter that runs both, 2 = only the matrix-pipe kernel
-    int scatter_own_levels = -1;        // measurement: the owner-computes scatter handles only the first n levels (grad_value of the others is NOT computed)
     int force_generic = 0;
-    int gv_storage = 1;                 // 0: msda_grad_value_dtype always answers the arithmetic type (A/B measurements)
     int dbg = 0;
-    int hooks = 0;                      // MSDA_ENABLE_HOOKS=1 was set when the knobs were read
     unsigned forced = 0;                // route knobs that were SET in the environment (kForce* bits), whatever their value: a knob
                                         // forced to its default (MSDA_FWD_RS=-1 for a rules-only A/B run) still wins over a pin
 };
@@ -97,7 +88,6 @@ void load_knobs()
 {
     Knobs k;
     if (env_int("MSDA_ENABLE_HOOKS", 0) == 1) {
-        k.hooks = 1;
         k.forced = (env_set("MSDA_FWD_RS") ? kForceFwdRs : 0u) | (env_set("MSDA_FWD_RS_NT") ? kForceFwdRsNt : 0u) |
                    (env_set("MSDA_FWD_WIN") ? kForceFwdWin : 0u) | (env_set("MSDA_FWD_TILE_WAVES") ? kForceFwdTileWaves : 0u) |
                    (env_set("MSDA_BWD_RS") ? kForceBwdRs : 0u) | (env_set("MSDA_BWD_RS_TPW") ? kForceBwdRsTpw : 0u) |
@@ -107,7 +97,6 @@ void load_knobs()
         k.bwd_rs = env_int("MSDA_BWD_RS", k.bwd_rs); k.bwd_rs_tpw = env_int("MSDA_BWD_RS_TPW", k.bwd_rs_tpw);
         k.bwd_rs_fsplit = env_int("MSDA_BWD_RS_FSPLIT", k.bwd_rs_fsplit);
         k.fwd_tile_waves = env_int("MSDA_FWD_TILE_WAVES", k.fwd_tile_waves);
-        k.fwd_rs_body = env_int("MSDA_FWD_RS_BODY", k.fwd_rs_body);
         k.fwd_win = env_int("MSDA_FWD_WIN", k.fwd_win); k.bwd_win = env_int("MSDA_BWD_WIN", k.bwd_win);
         k.win_min_halo = env_int("MSDA_WIN_MIN_HALO", k.win_min_halo);
         const char *mode = getenv("MSDA_BWD_MODE");
@@ -115,15 +104,12 @@ void load_knobs()
         k.bwd_phases = env_int("MSDA_BWD_PHASES", k.bwd_phases);
         k.bwd_cull = env_int("MSDA_BWD_CULL", k.bwd_cull);
         k.bwd_all_records = env_int("MSDA_BWD_ALL_RECORDS", k.bwd_all_records);
-        k.bwd_summary = env_int("MSDA_BWD_SUMMARY", k.bwd_summary);
         k.scatter_lds_kb = env_int("MSDA_SCATTER_LDS_KB", k.scatter_lds_kb);
         k.scatter_dbg = env_int("MSDA_SCATTER_DBG", k.scatter_dbg);
         k.scatter_own = env_int("MSDA_SCATTER_OWN", k.scatter_own);
-        k.scatter_own_levels = env_int("MSDA_SCATTER_OWN_LEVELS", k.scatter_own_levels);
         k.scatter_mfma = env_int("MSDA_SCATTER_MFMA", k.scatter_mfma);
         k.scatter_part = env_int("MSDA_SCATTER_PART", k.scatter_part);
         k.force_generic = env_int("MSDA_FORCE_GENERIC", 0) == 1;
-        k.gv_storage = env_int("MSDA_GV_STORAGE", k.gv_storage);
         k.dbg = env_int("MSDA_DBG", 0);
     }
     g_knobs = k;
@@ -484,7 +470,7 @@ bool win_plan_cached(const Params &p, int esz, bool force, WinPlan &w)
 bool storage_typed_grad_value_ok(int dtype, const Params &p)
 {
     if (storage_dtype(dtype) != MSDA_BF16 && storage_dtype(dtype) != MSDA_F16) return false;
-    if (knobs().force_generic || knobs().bwd_cull == 2 || !knobs().gv_storage) return false;
+    if (knobs().force_generic || knobs().bwd_cull == 2) return false;
     if (!owner_scatter_applicable(p, 2) || !p.shapes_host) return false;
     for (int l = 0; l < p.L; ++l)
         if (p.shapes_host[2 * l + 1] > kOwnPix || p.shapes_host[2 * l + 1] <= 0) return false;
@@ -547,8 +533,7 @@ int launch_fast(int dtype, const Params &p, bool bwd, hipStream_t stream)
                 // fp32, one tile per wave, slab from level 2 on: the software-pipelined slot body of that instantiation spills 31 VGPRs
                 // and its plain loop (the kernel compiled for a level-1 slab falls back to it) is 16-27 % faster on the SwinL pyramid
                 // (decoder call, 4 / 16 / 32 clips: 0.175 -> 0.137, 0.644 -> 0.540, 1.178 -> 0.973 ms; 800x1333: the same)
-                int body_l0 = (esz == 4 && nt == 1 && l0_host >= 2) ? 1 : l0_host;
-                if (knobs().fwd_rs_body == 1 || knobs().fwd_rs_body == 2) body_l0 = knobs().fwd_rs_body;     // (A/B measurements)
+                const int body_l0 = (esz == 4 && nt == 1 && l0_host >= 2) ? 1 : l0_host;
                 return launch_fwd_rs(dtype, nt, body_l0, p, parts, (unsigned)(clips * p.M * parts), stream);
             }
         }
@@ -588,7 +573,7 @@ int launch_fast(int dtype, const Params &p, bool bwd, hipStream_t stream)
         const long long clip_rows = (long long)p.frames * p.Lq;
         const bool mfma_fits = clip_rows * p.M * p.D * esz < 0x7fffffffLL &&
                                clip_rows * p.M * std::max((long long)p.LA * p.PA, (long long)p.LB * p.PB) * 2 * lesz < 0x7fffffffLL;
-        if (knobs().scatter_mfma != 0 && mfma_fits && p.shapes_host && p.Lq >= 16 && p.L >= 2 && !(knobs().scatter_own_levels >= 0 && knobs().scatter_own_levels < p.L)) {
+        if (knobs().scatter_mfma != 0 && mfma_fits && p.shapes_host && p.Lq >= 16 && p.L >= 2) {
             long long px = 0;
             for (int l = p.L - 1; l >= 1 && l >= p.L - 2; --l) {
                 const long long hw = p.shapes_host[2 * l] * p.shapes_host[2 * l + 1];
@@ -716,7 +701,6 @@ int launch_fast(int dtype, const Params &p, bool bwd, hipStream_t stream)
             if (rc) return rc;
         }
         Params pg = p;
-        if (knobs().scatter_own_levels >= 0 && knobs().scatter_own_levels < p.L) pg.own_levels = knobs().scatter_own_levels;     // (measurement only: wrong results)
         if (l0 < p.L) pg.own_levels = l0;
         pg.rec_mask = rec_mask;
         if (!(mfma_tiles && knobs().scatter_part == 2))
@@ -758,9 +742,6 @@ bool fast_path_takes(int dtype, const Params &p, bool bwd)
 int run(int dtype, const Params &p_in, bool bwd, hipStream_t stream)
 {
     if (dtype < MSDA_F32 || dtype > MSDA_F16_LOC32) return fail(MSDA_ERR_DTYPE, "msda: unknown dtype code%s");
-    if (MSDA_IS_TIMING_ONLY && !knobs().hooks)
-        return fail(MSDA_ERR_ARG, "msda: this library is a TIMING-ONLY build (kernels that skip work: wrong results); it runs only "
-                                  "with MSDA_ENABLE_HOOKS=1%s");
     Params p = p_in;
     p.own_levels = p.L;
     p.rec_mask = ~0u;
@@ -844,7 +825,7 @@ void attach_workspace(Params &p, void *workspace, long long bytes, int batch, in
     if (p.workspace && bytes >= workspace_need(batch, num_query, num_heads, vl) && knobs().bwd_cull != 0) {
         p.bbox = reinterpret_cast<int *>(p.workspace) + MSDA_BWD_WORKSPACE_BYTES / 4;
         // block summaries only pay for long candidate ranges (and index (group, head, level) rows with 32 bits)
-        if (num_query >= 2048 && (long long)batch * num_heads * vl < 0x7fffffffLL && knobs().bwd_summary != 0)
+        if (num_query >= 2048 && (long long)batch * num_heads * vl < 0x7fffffffLL)
             p.bsum = p.bbox + workspace_table_bytes(batch, num_query, num_heads, vl) / 4;
     }
 }
@@ -869,7 +850,7 @@ int msda_version(void) { return MSDA_ABI_VERSION; }
 
 const char *msda_build_info(void)
 {
-    return MSDA_IS_TIMING_ONLY ? "abi=13 arch=gfx950 timing_only=1" : "abi=13 arch=gfx950 timing_only=0";
+    return "abi=13 arch=gfx950";
 }
 
 void msda_reload_knobs(void) { load_knobs(); }

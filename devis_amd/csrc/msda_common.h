@@ -20,22 +20,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-// Timing-only experiment macros (MSDA_RS_EXP, MSDA_WIN_EXP, MSDA_MFMA_EXP: kernels that skip part of their work and return WRONG RESULTS, used to
-// measure floors -- profiles/NEGATIVE_RESULTS.md) may only be compiled into a library that says what it is: the build must also
-// define MSDA_TIMING_ONLY_BUILD, which makes msda_build_info() / msda_last_route() announce it and every entry point refuse to
-// run unless MSDA_ENABLE_HOOKS=1 (msda_api.hip).  A stray -D alone does not compile.
-#if defined(MSDA_RS_EXP) || defined(MSDA_WIN_EXP) || defined(MSDA_MFMA_EXP) || defined(MSDA_MFMA_TRACE)
-#  if !defined(MSDA_TIMING_ONLY_BUILD)
-#    error "MSDA_RS_EXP / MSDA_WIN_EXP / MSDA_MFMA_EXP produce wrong results by construction: also pass -DMSDA_TIMING_ONLY_BUILD (the library then refuses to run without MSDA_ENABLE_HOOKS=1 and labels its routes)"
-#  endif
-#endif
-#if defined(MSDA_TIMING_ONLY_BUILD)
-#  define MSDA_IS_TIMING_ONLY 1
-#else
-#  define MSDA_IS_TIMING_ONLY 0
-#endif
-
-
 #include "msda.h"
 
 // No implicit FMA contraction anywhere in the library: HIP's __fmul_rn / __fsub_rn are plain `*` / `-` unless
@@ -398,36 +382,19 @@ __device__ __forceinline__ void load_xy(const f16_t *loc2, float &x, float &y)
 constexpr int kRowSlots = kPch + 1;         // tile kernels: 16-byte record slots per row (odd: LDS banks)
 constexpr int kTileMaxWaves = 8;            // forward tile kernel: waves of one workgroup that share a tile (small calls)
 // owner-computes scatter
-#ifndef MSDA_OWN_THREADS
-#define MSDA_OWN_THREADS 1024
-#endif
-#ifndef MSDA_OWN_SLOTS
-#define MSDA_OWN_SLOTS 4
-#endif
-constexpr int kOwnThreads = MSDA_OWN_THREADS;       // (512: two workgroups per CU out of phase with each other)
+constexpr int kOwnThreads = 1024;                   // (512: two workgroups per CU out of phase with each other)
 constexpr int kOwnQuads = kOwnThreads / 4;
-constexpr int kOwnSlots = MSDA_OWN_SLOTS;           // pixels per owner quad
+constexpr int kOwnSlots = 4;                        // pixels per owner quad
 constexpr int kOwnPix = kOwnQuads * kOwnSlots;      // pixels per band
 // resident-slab kernels
-#ifndef MSDA_RS_THREADS
-#define MSDA_RS_THREADS 1024        // (512: 8 waves with a 256-VGPR budget each -- measured slower)
-#endif
-constexpr int kRsThreads = MSDA_RS_THREADS, kRsWaves = kRsThreads / kWave;
+constexpr int kRsThreads = 1024, kRsWaves = kRsThreads / kWave;     // (512: 8 waves with a 256-VGPR budget each -- measured slower)
 constexpr int kRsRows = kWave / 4;       // rows per wave tile: one quad per row
 constexpr int kRsSlack = 1024;          // bytes: the last LDS-DMA piece may overrun the slab's pixels
-#ifndef MSDA_RS_MAXFRAMES
-#define MSDA_RS_MAXFRAMES 32
-#endif
-#ifndef MSDA_RS_LDS_BYTES
-#define MSDA_RS_LDS_BYTES (160 * 1024)  // (experiments: 80 KiB with MSDA_RS_THREADS=512, MSDA_RS_MIN_WAVES=4, MSDA_RS_MAXFRAMES=8 = two workgroups per CU on 16-bit slabs)
-#endif
-#ifndef MSDA_RS_MIN_WAVES
-#define MSDA_RS_MIN_WAVES 1
-#endif
-constexpr int kRsMaxFrames = MSDA_RS_MAXFRAMES;        // frames x frames slot masks live in LDS
+constexpr int kRsLdsBytes = 160 * 1024;
+constexpr int kRsMaxFrames = 32;        // frames x frames slot masks live in LDS
 constexpr int kRsRowB = 128;            // bytes of one pixel of one head in a 4-byte type (D = 32); 64 in a 2-byte type
 constexpr int kRsTailBytes = kRsRowB + kRsMaxFrames * kRsMaxFrames * 4 + 4 * kSlabMaxLevels * 4 + 16;   // after the slab
-constexpr int kRsSlabBytes = ((MSDA_RS_LDS_BYTES - 256 - kRsTailBytes) / 128) * 128;
+constexpr int kRsSlabBytes = ((kRsLdsBytes - 256 - kRsTailBytes) / 128) * 128;
 
 // ---- resident-window kernels (msda_win.hip): encoder-shaped calls, where query i IS pixel i of the pyramid and samples round
 // its own position.  A workgroup owns the queries of one spatial TILE (By x Bx level-0 pixels and the pixels of the other

@@ -32,24 +32,6 @@
 #include "msda_common.h"
 #include <algorithm>
 
-#ifndef MSDA_MFMA_TB
-#define MSDA_MFMA_TB 2      // pixel tiles whose operands are read together (experiment builds: see profiles/r06_logs)
-#endif
-// Timing-only build (-DMSDA_MFMA_TRACE beside -DMSDA_TIMING_ONLY_BUILD; scripts/mfma_trace.py): cycle stamps at the phase boundaries
-// of an item; every wave leaves its per-phase sums in the first pixels of its frame's LEVEL-0 grad_value (run with MSDA_SCATTER_PART=2).
-#if defined(MSDA_MFMA_TRACE)
-#define MSDA_TR(k) { __builtin_amdgcn_sched_barrier(0); const unsigned long long tr_now = __builtin_readcyclecounter(); \
-                     tr[k] += (unsigned)(tr_now - tr_t); tr_t = tr_now; __builtin_amdgcn_sched_barrier(0); }
-#else
-#define MSDA_TR(k)
-#endif
-#ifndef MSDA_MFMA_RED
-#define MSDA_MFMA_RED 2     // accumulator rows a wave sums at a time in the reduction
-#endif
-#ifndef MSDA_MFMA_SB
-#define MSDA_MFMA_SB 1      // scheduling barrier behind every batch of tiles (bounds the live operand registers)
-#endif
-
 namespace msda {
 namespace {
 
@@ -96,7 +78,7 @@ msda_bwd_value_mfma_kernel(const Params p, int l0)
     using V = typename X::V;
     constexpr int D = 32, NP = mfma_rows(MT), kTile = mfma_tile_bytes(MT), kPhase = mfma_phase_tiles(MT), kLds = mfma_lds_bytes(MT, NW);
     constexpr bool kSplitG = sizeof(T) == 4;
-    constexpr int kRedRows = MSDA_MFMA_RED;
+    constexpr int kRedRows = 2;      // accumulator rows a wave sums at a time in the reduction
     extern __shared__ __attribute__((aligned(256))) unsigned char lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     unsigned char *Ahi = lds + wave * (2 * kTile), *Alo = Ahi + kTile;
@@ -138,10 +120,6 @@ msda_bwd_value_mfma_kernel(const Params p, int l0)
 
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
         const int m = item % p.M, gf = item / p.M, f = gf % p.frames, clip = gf / p.frames;
-#if defined(MSDA_MFMA_TRACE)
-        unsigned tr[16] = {};
-        unsigned long long tr_t = __builtin_readcyclecounter();
-#endif
         // the tiles are zero before any wave writes a cell (first item, and after every reduction, which borrows them)
         for (int i = tid * 16; i < kLds; i += NW * 64 * 16) *reinterpret_cast<u32x4 *>(lds + i) = u32x4{0u, 0u, 0u, 0u};
         // sources reading frame f: lane s of every wave holds source s (-1 = the frame's own current-frame points, else t * window
@@ -248,13 +226,7 @@ msda_bwd_value_mfma_kernel(const Params p, int l0)
         enter_source(cur);
         Raw raw;
         issue(cur, raw);
-        MSDA_TR(0)
         for (int st = wave; st < nsteps; st += NW) {
-#if defined(MSDA_MFMA_TRACE)
-            asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
-            MSDA_TR(1)
-            ++tr[15];
-#endif
             const bool act = g >= 16 * cur.j - min(16 * cur.j, p.Lq - 16) && pt < cur.points;
             // ---- this step's values out of the load registers: the B operand G[k = 8 kh + j][n], the points
             V bhi, blo;
@@ -272,12 +244,7 @@ msda_bwd_value_mfma_kernel(const Params p, int l0)
 #pragma unroll
             for (int li = 0; li < NL; ++li) { xs[li] = raw.x[li]; ys[li] = raw.y[li]; as[li] = raw.a[li]; }
             advance(cur);
-#if defined(MSDA_MFMA_EXP) && (MSDA_MFMA_EXP & 4)        // timing only: no loads inside the loop (every step reuses the first one's)
-            asm volatile("" : "+v"(raw.x[0]), "+v"(raw.y[0]), "+v"(raw.a[0]));
-#else
             issue(cur, raw);                                  // the next step's loads fly under this step's work
-#endif
-            MSDA_TR(2)
             unsigned cells[NL][4];
 #pragma unroll
             for (int li = 0; li < NL; ++li) {
@@ -295,11 +262,7 @@ msda_bwd_value_mfma_kernel(const Params p, int l0)
                     const float th0 = tent(quad_bcast<J>(h_im) - r0f) * quad_bcast<J>(a), th1 = tent(quad_bcast<J>(h_im) - r1f) * quad_bcast<J>(a); \
                     const float tw0 = tent(quad_bcast<J>(w_im) - c0f), tw1 = tent(quad_bcast<J>(w_im) - c1f); \
                     t00 = fmaf(th0, tw0, t00); t01 = fmaf(th0, tw1, t01); t10 = fmaf(th1, tw0, t10); t11 = fmaf(th1, tw1, t11); }
-#if defined(MSDA_MFMA_EXP) && (MSDA_MFMA_EXP & 16)       // timing only: one point of the quad instead of four
-                MSDA_MERGE(0)
-#else
                 MSDA_MERGE(0) MSDA_MERGE(1) MSDA_MERGE(2) MSDA_MERGE(3)
-#endif
 #undef MSDA_MERGE
                 // ---- cells; corners outside the map (cuh:56-78) and skipped points go to the trash row
                 const bool rv0 = inr && (unsigned)hl < (unsigned)H[li], rv1 = inr && (unsigned)(hl + 1) < (unsigned)H[li];
@@ -317,20 +280,15 @@ msda_bwd_value_mfma_kernel(const Params p, int l0)
                     const E2 hi = {(E)tt[c], (E)tt[c + 1]};
                     const E2 lo = {(E)(tt[c] - (float)hi[0]), (E)(tt[c + 1] - (float)hi[1])};
                     const unsigned hb = __builtin_bit_cast(unsigned, hi), lb = __builtin_bit_cast(unsigned, lo);
-#if defined(MSDA_MFMA_EXP) && (MSDA_MFMA_EXP & 8)        // timing only: the cells are computed and not written
-                    asm volatile("" : : "v"(cells[li][c]), "v"(cells[li][c + 1]), "v"(hb), "v"(lb));
-#else
                     asm volatile("ds_write_b16 %0, %1" : : "v"(cells[li][c]), "v"(hb) : "memory");
                     asm volatile("ds_write_b16_d16_hi %0, %1" : : "v"(cells[li][c + 1]), "v"(hb) : "memory");
                     asm volatile("ds_write_b16 %0, %1 offset:%2" : : "v"(cells[li][c]), "v"(lb), "n"(kTile) : "memory");
                     asm volatile("ds_write_b16_d16_hi %0, %1 offset:%2" : : "v"(cells[li][c + 1]), "v"(lb), "n"(kTile) : "memory");
-#endif
                 }
             }
             // ---- the products, two pixel tiles at a time, the next pair's operands read under this pair's instructions (the LDS
             // operations of one wave complete in order: these reads see the cells written above)
-            MSDA_TR(3)
-            constexpr int TB = MSDA_MFMA_TB < MT ? MSDA_MFMA_TB : MT, NB = (MT + TB - 1) / TB;
+            constexpr int TB = MT < 2 ? MT : 2, NB = (MT + TB - 1) / TB;     // TB pixel tiles whose operands are read together
             V fh[2][TB], fl[2][TB];
             auto read_pair = [&](int b, V (&h)[TB], V (&l)[TB]) {
 #pragma unroll
@@ -344,11 +302,6 @@ msda_bwd_value_mfma_kernel(const Params p, int l0)
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
                 if (b + 1 < NB) read_pair(b + 1, fh[(b + 1) & 1], fl[(b + 1) & 1]);
-#if defined(MSDA_MFMA_EXP) && (MSDA_MFMA_EXP & 1)        // timing only: one product instead of the 20-30 (the operands still read)
-                if (b == 0) acc[0] = mma(fh[0][0], bhi, acc[0]);
-#pragma unroll
-                for (int u = 0; u < TB; ++u) if (b * TB + u < MT) { acc[b * TB + u][0] += (float)fh[b & 1][u][0] + (float)fl[b & 1][u][0] + (float)blo[0]; }
-#else
 #pragma unroll
                 for (int u = 0; u < TB; ++u) if (b * TB + u < MT) acc[b * TB + u] = mma(fh[b & 1][u], bhi, acc[b * TB + u]);
 #pragma unroll
@@ -357,47 +310,31 @@ msda_bwd_value_mfma_kernel(const Params p, int l0)
 #pragma unroll
                     for (int u = 0; u < TB; ++u) if (b * TB + u < MT) acc[b * TB + u] = mma(fh[b & 1][u], blo, acc[b * TB + u]);
                 }
-#endif
-#if MSDA_MFMA_SB
-                __builtin_amdgcn_sched_barrier(0);
-#endif
+                __builtin_amdgcn_sched_barrier(0);         // behind every batch of tiles: bounds the live operand registers
             }
-            MSDA_TR(4)
             // ---- cells back to zero
             const unsigned zero = 0u;
 #pragma unroll
             for (int li = 0; li < NL; ++li)
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-#if defined(MSDA_MFMA_EXP) && (MSDA_MFMA_EXP & 8)
-                    asm volatile("" : : "v"(cells[li][c]), "v"(zero));
-#else
                     asm volatile("ds_write_b16 %0, %1" : : "v"(cells[li][c]), "v"(zero) : "memory");
                     asm volatile("ds_write_b16 %0, %1 offset:%2" : : "v"(cells[li][c]), "v"(zero), "n"(kTile) : "memory");
-#endif
                 }
-            MSDA_TR(5)
         }
         asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory");
-#if defined(MSDA_MFMA_TRACE)
-        __syncthreads();
-        MSDA_TR(6)
-#endif
 
         // ---- the waves' accumulators -> one, through the LDS, kPhase tiles at a time
         GV *gmap = static_cast<GV *>(p.grad_value) + ((long long)gf * p.S + lsi0) * MD + m * D;
 #pragma unroll
         for (int ph = 0; ph * kPhase < MT; ++ph) {
             __syncthreads();
-            MSDA_TR(7)
 #pragma unroll
             for (int t = 0; t < kPhase; ++t)
                 if (ph * kPhase + t < MT)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) red[((wave * kPhase + t) * 16 + r) * 64 + lane] = acc[ph * kPhase + t][r];
-            MSDA_TR(8)
             __syncthreads();
-            MSDA_TR(9)
             // the phase's nt x 16 accumulator rows (64 lanes each) dealt over ALL the waves -- 2 nt consecutive rows of one tile per
             // wave -- and summed kRedRows rows at a time (8 LDS loads in flight per row), the partial sums added in wave order
             static_assert(NW == 8 && MT % 2 == 0 && kPhase % 2 == 0, "a wave's rows: a multiple of four inside one tile");
@@ -425,19 +362,8 @@ msda_bwd_value_mfma_kernel(const Params p, int l0)
                 }
                 __builtin_amdgcn_sched_barrier(0);          // (without it every batch's loads are hoisted to the top: 64 registers more)
             }
-            MSDA_TR(10)
         }
         __syncthreads();                                    // the reduction buffer is the tiles: zeroed again at the top
-#if defined(MSDA_MFMA_TRACE)
-        MSDA_TR(11)
-        if (lane < 16) {
-            unsigned v = 0;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) v = lane == k ? tr[k] : v;
-            float *t0 = reinterpret_cast<float *>(p.grad_value) + ((long long)gf * p.S + wave) * MD + m * D + lane;
-            *t0 = __uint_as_float(v);
-        }
-#endif
     }
 }
 

@@ -25,56 +25,12 @@ namespace {
 //   * a corner outside the map reads a zero row kept in LDS (slab levels) or an out-of-range buffer offset
 //     (other levels: buffer loads return 0 without touching memory), so a non-finite value at an unrelated
 //     pixel can never leak into a row that does not sample it.
-#ifndef MSDA_RS_PAIR
-#define MSDA_RS_PAIR 1       // forward: the two LDS corners of a pair are requested together, then consumed (0: one after the other).
-                             // Same speed on every shape (round 4, same box: 0.375 / 0.376 ms fp32, 0.282 / 0.282 bf16), but the
-                             // production 16-bit kernel (4 tiles per wave) no longer spills VGPRs (6 -> 0; profiles/r04_resource_usage.txt)
-#endif
-#ifndef MSDA_RS_PREFETCH
-#define MSDA_RS_PREFETCH 0   // forward, one tile per wave: the first slot's points of a frame loaded into registers early -- 1: behind the
-                             // slab's LDS-DMA (round 4: slower, loads return in order and the slab wait inherits their HBM latency),
-                             // 2: BEFORE the barrier that frees the previous slab, so that they fly while the wave waits for the slowest
-                             // wave of the frame before and land ahead of the DMA pieces (round 5)
-#endif
-#ifndef MSDA_RS_PIPE
-#define MSDA_RS_PIPE 1       // software-pipelined level-0 corners (0: the plain group loop only; A/B builds)
-#endif
 #include "msda_rs_common.inc"
-
-// Timeline probe (-DMSDA_RS_TRACE, experimental builds only; scripts/rs_trace.py): lane 0 of one wave of the first 8 workgroups
-// stamps the shader clock at phase boundaries of the forward.
-#ifdef MSDA_RS_TRACE
-constexpr int kRsTraceLen = 4096;
-__device__ unsigned long long g_rs_trace[8][kRsTraceLen];
-__device__ int g_rs_trace_n[8];
-#define MSDA_RTR(id) do { if (tr_on && tr_n < kRsTraceLen) g_rs_trace[blockIdx.x][tr_n++] = ((unsigned long long)__builtin_readcyclecounter() << 8) | (unsigned)(id); } while (0)
-#else
-#define MSDA_RTR(id) do { } while (0)
-#endif
-
-// Static issue priority by wave index: the waves of a workgroup share their SIMD's issue slots by priority, then AGE, so the
-// last-dispatched waves of a 16-wave workgroup lose every arbitration and set the time of each frame's barrier (timeline probe,
-// profiles/r04_logs/rs_trace_*.txt: the last wave's slots took twice as long as wave 1's).  MSDA_RS_PRIO = 1: priority 0..3 by
-// quarter of the workgroup, youngest highest.
-#ifndef MSDA_RS_PRIO
-#define MSDA_RS_PRIO 0
-#endif
-__device__ __forceinline__ void rs_wave_priority(int wave)
-{
-#if MSDA_RS_PRIO
-    const int q = wave * 4 / kRsWaves;
-    if (q == 1) __builtin_amdgcn_s_setprio(1);
-    else if (q == 2) __builtin_amdgcn_s_setprio(2);
-    else if (q == 3) __builtin_amdgcn_s_setprio(3);
-#else
-    (void)wave;
-#endif
-}
 
 // levels >= l0 of source frame f (head m) -> LDS slab, 16 bytes per lane by LDS-DMA (8 lanes per pixel)
 template <typename T>
 __device__ __forceinline__ void rs_stage_slab(const Params &p, T *slab, int clip, int m, int f, int px0, int npx,
-                                              int wave, int lane, bool wait = true)
+                                              int wave, int lane)
 {
     constexpr int GL = rs_row_bytes<T>() / 16, D = 32;
     constexpr int PXW = kWave / GL;                 // pixels per LDS-DMA wave instruction
@@ -88,7 +44,7 @@ __device__ __forceinline__ void rs_stage_slab(const Params &p, T *slab, int clip
         (void)gp;
 #endif
     }
-    if (wait) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // The shared front of the resident-slab kernels: LDS carve, level tables, slot masks, tile geometry.
@@ -141,7 +97,7 @@ __device__ __forceinline__ RsShared rs_setup(const Params &p, unsigned char *lds
 //     lane R's eight values to the quad (v_add_u32_dpp with the lane's slice offset, v_mov_b32_dpp).  Round 2 derived
 //     each corner in the lane of the same number with six DPP-operand instructions per step and then broadcast all four:
 //     16.5 VALU instructions per corner, now 7 (forward 0.430 -> 0.369 ms on the bench workload, same box).
-//   * ABLATIONS (timing-only builds, MSDA_RS_EXP, profiles/r03_logs): without the level-0 (memory) corners the kernel takes
+//   * ABLATIONS (profiles/r03_logs): without the level-0 (memory) corners the kernel takes
 //     0.154 ms, without the slab (LDS) corners 0.377 ms = the time of the full kernel then (0.374): the LDS / VALU side is
 //     completely hidden behind the level-0 gathers, i.e. behind the rate at which a CU's vector-memory path returns
 //     scattered 128-byte lines that miss the L1 (86 k lines per CU and launch; 31 M L2 read requests per launch, 34 % of
@@ -149,7 +105,7 @@ __device__ __forceinline__ RsShared rs_setup(const Params &p, unsigned char *lds
 //     (1 tile per wave 0.345 ms against 0.374 with 2), which the host's choice of `parts` optimises; (b) PAIRS of memory
 //     corners software-pipelined under the LDS pairs of the same slot (0.374 -> 0.337 ms; PL0 below).  What does not:
 //     4-8 level-0 loads in flight per lane across whole LDS steps (0.380), non-temporal point loads, 512-thread
-//     workgroups with a 256-VGPR budget (-DMSDA_RS_THREADS=512: 0.342 at 4 tiles per wave = the 1024-thread kernel;
+//     workgroups with a 256-VGPR budget (512 threads: 0.342 at 4 tiles per wave = the 1024-thread kernel;
 //     gather pass 0.46 against 0.435).
 struct RsRec { int a[4]; float w[4]; };      // this lane's point: byte address (without the lane's slice offset) and weight of corners 0..3
 
@@ -204,12 +160,11 @@ __device__ __forceinline__ RsRec rs_records(float x, float y, float a, int lvl, 
 
 // T = storage type of value / out, TL = of sampling_loc / attn_weight (T, or float with a 16-bit T)
 template <typename T, typename TL, int NT, int PL0>       // PL0: the first slab level the software-pipelined slot body is compiled for (1 or 2)
-__global__ void __launch_bounds__(kRsThreads, MSDA_RS_MIN_WAVES)
+__global__ void __launch_bounds__(kRsThreads, 1)
 msda_fwd_rs_kernel(const Params p, int slab_bytes, int parts)
 {
     constexpr int RPW = kRsRows, D = 32, ROWB = rs_row_bytes<T>(), ROWSH = ROWB == 128 ? 7 : 6;
     constexpr bool kHalf = sizeof(T) == 2;
-    constexpr bool kPrefetch = MSDA_RS_PREFETCH != 0 && NT == 1;      // (more accumulator sets: the carried points spill)
     extern __shared__ __attribute__((aligned(128))) unsigned char lds_raw[];       // (no static LDS: the slab starts at 0)
     const int tid = threadIdx.x, lane = tid % kWave;
     const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
@@ -254,79 +209,11 @@ msda_fwd_rs_kernel(const Params p, int slab_bytes, int parts)
     for (int k = 0; k < NT; ++k)
 #pragma unroll
         for (int c = 0; c < 8; ++c) acc[k][c] = 0.f;
-#ifdef MSDA_RS_TRACE
-    const bool tr_on = blockIdx.x < 8 && tid == (blockIdx.x < 4 ? 64 : kRsThreads - 64);
-    int tr_n = 0;
-#endif
-    rs_wave_priority(wave);
-    MSDA_RTR(9);                    // prologue done
 
     for (int f = 0; f < p.frames; ++f) {
-#if MSDA_RS_PREFETCH != 2
         __syncthreads();                                   // every wave is done with the previous slab
-        MSDA_RTR(1);                // barrier: previous slab free
-#endif
-#if MSDA_RS_PREFETCH
-        // The points of this wave's FIRST (tile, slot) of the frame are requested behind the slab's LDS-DMA and land while it does
-        // (the timeline of round 4: 2.6 k of a frame's 24.8 k clocks were these loads, exposed in every wave at once after the
-        // barrier).  Everything that reads LDS -- the slot mask -- comes before the DMA is issued: hipcc puts an s_waitcnt vmcnt(0)
-        // in front of any LDS access it sees while an LDS-DMA is in flight.
-        RawPoints<TL> pre;
-        int pre_sl = -2;                                   // the slot the prefetched points belong to (-2: none)
-        int64_t pre_idx0 = 0;
-        if (kPrefetch && my_tiles > 0 && p.wide_loads) {
-            int t0, q00;
-            tile_of(0, t0, q00);
-            const unsigned todo0 = __builtin_amdgcn_readfirstlane(sh.mask[t0 * p.frames + f]);
-            if (todo0) {
-                const int sl0 = (int)__builtin_ctz(todo0) - 1, P0 = sl0 < 0 ? p.PA : p.PB;
-                if (P0 == 4 && (sl0 < 0 ? p.LA : L) * P0 == 16) {
-                    const int64_t row0 = (((int64_t)clip * p.frames + t0) * p.Lq + q00 + j) * p.M + m;
-                    pre_idx0 = row0 * ((sl0 < 0 ? p.LA : p.LB) * P0) + (sl0 < 0 ? 0 : sl0 * L * P0);
-                    pre_sl = sl0;
-                }
-            }
-        }
-#endif
-#if MSDA_RS_PREFETCH == 2
-        if (pre_sl != -2) {
-            int t0, q00;
-            tile_of(0, t0, q00);
-            pre = issue_slot_points<TL>(static_cast<const TL *>(pre_sl < 0 ? p.locA : p.locB), static_cast<const TL *>(pre_sl < 0 ? p.awA : p.awB),
-                                        pre_idx0, cor, j < min(RPW, p.Lq - q00));
-        }
-        __syncthreads();                                   // every wave is done with the previous slab (the points fly meanwhile)
-        MSDA_RTR(1);                // barrier: previous slab free
-#endif
-#if !defined(MSDA_RS_EXP) || MSDA_RS_EXP != 3
-        if (l0 < L) rs_stage_slab<T>(p, slab, clip, m, f, sh.px0, sh.npx, wave, lane, !kPrefetch);
-#endif
-#if MSDA_RS_PREFETCH == 1
-        if (pre_sl != -2) {
-            int t0, q00;
-            tile_of(0, t0, q00);
-            pre = issue_slot_points<TL>(static_cast<const TL *>(pre_sl < 0 ? p.locA : p.locB), static_cast<const TL *>(pre_sl < 0 ? p.awA : p.awB),
-                                        pre_idx0, cor, j < min(RPW, p.Lq - q00));
-        }
-#endif
-#if MSDA_RS_PREFETCH
-        if (kPrefetch) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-        MSDA_RTR(2);                // slab pieces issued and landed
+        if (l0 < L) rs_stage_slab<T>(p, slab, clip, m, f, sh.px0, sh.npx, wave, lane);
         __syncthreads();
-        MSDA_RTR(3);                // barrier: slab complete
-#if MSDA_RS_PREFETCH
-        // (xs / ys / as are carried into the tile loop: the first (tile, slot) it runs is the one the points were requested for --
-        // tile 0 has work in this frame, or nothing was requested -- and every later slot loads its own at its head)
-        float xs[4], ys[4], as[4];
-        bool have_points = false;
-        if (pre_sl != -2) {
-            int t0, q00;
-            tile_of(0, t0, q00);
-            finish_slot_points<TL>(pre, cor, j < min(RPW, p.Lq - q00), xs, ys, as);
-            have_points = true;
-        }
-#endif
         const int fS = f * p.S;
 #pragma unroll 1
         for (int k = 0; k < my_tiles; ++k) {
@@ -345,20 +232,8 @@ msda_fwd_rs_kernel(const Params p, int slab_bytes, int parts)
                 }
             });
             // one corner: the lane's 8 channels of the row at byte address A, times W
-            auto corner = [&](auto Sc, int A, float W) {      // (A by value: the experiments below may change it)
+            auto corner = [&](auto Sc, int A, float W) {
                 constexpr bool SLAB = decltype(Sc)::value;
-#if defined(MSDA_RS_EXP)          // timing experiments (wrong results; 1 / 2 / 6 live in rs_issue_row: no memory / LDS / any corner reads),
-                                  // 4 = memory corners read one 16-byte slice instead of two, 5 = ... from one 32 KiB window
-#if defined(__HIP_DEVICE_COMPILE__)
-                if constexpr (!SLAB && MSDA_RS_EXP == 4) {
-                    const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(rsrc, A, 0, 0);
-                    wacc[0] = fmaf(W, __uint_as_float(q.x), wacc[0]); wacc[1] = fmaf(W, __uint_as_float(q.y), wacc[1]);
-                    wacc[2] = fmaf(W, __uint_as_float(q.z), wacc[2]); wacc[3] = fmaf(W, __uint_as_float(q.w), wacc[3]);
-                    return;
-                }
-#endif
-                if constexpr (!SLAB && MSDA_RS_EXP == 5) A &= 0x7fff;
-#endif
 #if defined(__HIP_DEVICE_COMPILE__)
                 const RsRaw<T> raw = rs_issue_row<T, SLAB>(rsrc, A, delta2);
                 rs_fma_row<T>(raw, W, wacc);
@@ -386,15 +261,8 @@ msda_fwd_rs_kernel(const Params p, int slab_bytes, int parts)
                 const unsigned invP = (65536u + (unsigned)P - 1u) / (unsigned)P;      // kk / P for kk * P < 2^16
                 const int first_slab_pt = l0 * P;              // points of levels >= l0 read the slab
                 const bool wide = p.wide_loads && P == 4 && npts == 16;           // (uniform) see load_slot_points
-#if MSDA_RS_PREFETCH
-                if (wide && !have_points) load_slot_points<TL>(loc, aw, idx0, cor, live, xs, ys, as);
-                have_points = false;
-#else
                 float xs[4], ys[4], as[4];
                 if (wide) load_slot_points<TL>(loc, aw, idx0, cor, live, xs, ys, as);
-#endif
-                MSDA_RTR(4);        // slot: points loaded (first use waits)
-#if MSDA_RS_PIPE
                 if (wide && l0 == PL0) {
                     // 4 levels x 4 points, levels < l0 outside the slab.  Work units are corner PAIRS: 8 * l0 memory pairs (4
                     // buffer loads each) ride along the 8 * (4 - l0) LDS pairs -- one memory pair is consumed, and the next
@@ -433,8 +301,8 @@ msda_fwd_rs_kernel(const Params p, int slab_bytes, int parts)
                             static_for<8>([&](auto Hc) {
                                 constexpr int R = decltype(Hc)::value / 2, S0 = 2 * (decltype(Hc)::value % 2);
                                 constexpr int HS = (GL - L0) * 8 + decltype(Hc)::value;      // LDS pair index
-#if MSDA_RS_PAIR
-                                {   // both corners of the pair requested before either is consumed
+                                {   // both corners of the pair requested before either is consumed (against one after the
+                                    // other: same speed, but the 16-bit kernel at 4 tiles per wave no longer spills VGPRs)
                                     const int A0 = quad_bcast<R>(rl.a[S0]) + off1, A1 = quad_bcast<R>(rl.a[S0 + 1]) + off1;
                                     const float W0 = quad_bcast<R>(rl.w[S0]), W1 = quad_bcast<R>(rl.w[S0 + 1]);
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -445,10 +313,6 @@ msda_fwd_rs_kernel(const Params p, int slab_bytes, int parts)
 #endif
                                     asm volatile("" ::: "memory");
                                 }
-#else
-                                corner(std::true_type{}, quad_bcast<R>(rl.a[S0]) + off1, quad_bcast<R>(rl.w[S0]));
-                                corner(std::true_type{}, quad_bcast<R>(rl.a[S0 + 1]) + off1, quad_bcast<R>(rl.w[S0 + 1]));
-#endif
                                 if constexpr ((HS + 1) % PERIOD == 0) {
                                     constexpr int J = (HS + 1) / PERIOD - 1;
                                     consume(std::integral_constant<int, J>{});
@@ -459,7 +323,6 @@ msda_fwd_rs_kernel(const Params p, int slab_bytes, int parts)
                     };
                     pipelined(std::integral_constant<int, PL0>{});
                 } else
-#endif
                 {
 #pragma unroll 1
                     for (int g0 = 0; g0 < npts; g0 += 4) {
@@ -487,7 +350,6 @@ msda_fwd_rs_kernel(const Params p, int slab_bytes, int parts)
                     }
                 }
             }
-            MSDA_RTR(5);            // tile done for this frame
             static_for<NT>([&](auto Kc) {
                 constexpr int K = decltype(Kc)::value;
                 if (k == K) {
@@ -497,7 +359,6 @@ msda_fwd_rs_kernel(const Params p, int slab_bytes, int parts)
             });
         }
     }
-    MSDA_RTR(6);
     static_for<NT>([&](auto Kc) {
         constexpr int K = decltype(Kc)::value;
         if (K >= my_tiles) return;
@@ -515,9 +376,6 @@ msda_fwd_rs_kernel(const Params p, int slab_bytes, int parts)
             }
         }
     });
-#ifdef MSDA_RS_TRACE
-    if (tr_on) g_rs_trace_n[blockIdx.x] = tr_n;
-#endif
 }
 
 // Backward gather pass (grad_loc / grad_attn) on the resident slab: same workgroup / tile / quad geometry as
@@ -528,7 +386,7 @@ msda_fwd_rs_kernel(const Params p, int slab_bytes, int parts)
 // stores its (grad_x, grad_y, grad_attn) directly: the 4 points of a group are 32 + 16 contiguous bytes per row.
 // Also leaves the per-point culling records (top tap row as int16) the scatter pass reads.
 template <typename T, typename TL, int PL0>      // T: value / grad_out, TL: sampling_loc / attn_weight and their gradients
-__global__ void __launch_bounds__(kRsThreads, MSDA_RS_MIN_WAVES)
+__global__ void __launch_bounds__(kRsThreads, 1)
 msda_bwd_rs_kernel(const Params p, int slab_bytes, int parts, int frame_split)
 {
     constexpr int RPW = kRsRows, D = 32, ROWB = rs_row_bytes<T>(), ROWSH = ROWB == 128 ? 7 : 6;
@@ -568,7 +426,6 @@ msda_bwd_rs_kernel(const Params p, int slab_bytes, int parts, int frame_split)
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(vbase), 0, (int)vbytes, 0x00020000);
 #endif
     const bool records = p.bbox != nullptr;        // per-point culling records (host: only with cull_points)
-    rs_wave_priority(wave);
 
     for (int f = frame_split ? f_only : 0; f < (frame_split ? f_only + 1 : p.frames); ++f) {
         __syncthreads();                                   // every wave is done with the previous slab
@@ -633,7 +490,6 @@ msda_bwd_rs_kernel(const Params p, int slab_bytes, int parts, int frame_split)
                     gx = (float)pt.W * g_w * pt.a; gy = (float)pt.H * g_h * pt.a;
                 };
                 bool done = false;
-#if MSDA_RS_PIPE
                 if (wide && wide_ld && l0 == PL0) {
                     // 4 levels x 4 points, levels < l0 outside the slab: their 8 * l0 corner PAIRS (4 buffer loads each) ride along
                     // the 8 * (4 - l0) LDS pairs, one consumed -- and the next issued -- after every third (l0 = 1) or every
@@ -709,7 +565,6 @@ msda_bwd_rs_kernel(const Params p, int slab_bytes, int parts, int frame_split)
                     for (int G = 0; G < L0; ++G) finish(gm[G], km[G], wx[G], wy[G], wa[G]);
                     done = true;
                 }
-#endif
 #pragma unroll 1
                 for (int g0 = 0; g0 < (done ? 0 : npts); g0 += 4) {
                     const int kk = g0 + cor;
@@ -867,12 +722,3 @@ int launch_bwd_rs(int dtype, int first_slab_level, const Params &p, int parts, u
 }
 
 }  // namespace msda
-
-#ifdef MSDA_RS_TRACE
-extern "C" int msda_debug_trace_rs(unsigned long long *dst, int *counts)
-{
-    if (hipMemcpyFromSymbol(dst, HIP_SYMBOL(msda::g_rs_trace), sizeof(unsigned long long) * 8 * msda::kRsTraceLen) != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(counts, HIP_SYMBOL(msda::g_rs_trace_n), sizeof(int) * 8) != hipSuccess) return -2;
-    return msda::kRsTraceLen;
-}
-#endif

@@ -15,14 +15,6 @@ __device__ __forceinline__ RsRaw<T> rs_issue_row(__amdgpu_buffer_rsrc_t rsrc, in
 {
     typedef __attribute__((address_space(3))) const u32x4 *lds_u4;
     RsRaw<T> r;
-#if defined(MSDA_RS_EXP)      // timing-only builds (wrong results): 2 = slab (LDS) corners not read, 1 = memory corners not read, 6 = neither;
-                              // the consumers' FMAs / dots stay (profiles/NEGATIVE_RESULTS.md R5-5)
-    if constexpr ((SLAB && (MSDA_RS_EXP == 2 || MSDA_RS_EXP == 6)) || (!SLAB && (MSDA_RS_EXP == 1 || MSDA_RS_EXP == 6))) {
-        r.q[0] = u32x4{(unsigned)a, 1u, 2u, 3u};
-        if constexpr (sizeof(T) == 4) r.q[1] = u32x4{(unsigned)delta2, 5u, 6u, 7u};
-        return r;
-    }
-#endif
     if constexpr (SLAB) {
         r.q[0] = *(lds_u4)(uintptr_t)(unsigned)a;
         if constexpr (sizeof(T) == 4) r.q[1] = *(lds_u4)(uintptr_t)(unsigned)(a + delta2);
@@ -37,9 +29,6 @@ __device__ __forceinline__ RsRaw<T> rs_issue_row(__amdgpu_buffer_rsrc_t rsrc, in
 // f16) and accumulates in fp32 -- the same single-rounded fma(w, float(h), acc) as a v_cvt_f32_f16 followed by an FMA, in ONE
 // instruction instead of two (round 5: the f16 kernels issued 8 conversions + 4 packed FMAs per 8 channels; bf16 has no such
 // instruction on gfx950 -- v_fma_mix_f32_bf16 does not assemble, v_dot2_f32_bf16 would round the weight).
-#ifndef MSDA_F16_MIX
-#define MSDA_F16_MIX 1
-#endif
 __device__ __forceinline__ float fma_mix_lo(float w, unsigned packed, float acc)
 {
     asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel_hi:[0,1,0]" : "+v"(acc) : "v"(w), "v"(packed));
@@ -54,7 +43,6 @@ __device__ __forceinline__ float fma_mix_hi(float w, unsigned packed, float acc)
 template <typename T>
 __device__ __forceinline__ void rs_fma_row(const RsRaw<T> &r, float w, float (&acc)[8])
 {
-#if MSDA_F16_MIX
     if constexpr (std::is_same<T, f16_t>::value) {
         const unsigned q[4] = {r.q[0].x, r.q[0].y, r.q[0].z, r.q[0].w};
 #pragma unroll
@@ -64,7 +52,6 @@ __device__ __forceinline__ void rs_fma_row(const RsRaw<T> &r, float w, float (&a
         }
         return;
     }
-#endif
     float v[8];
     if constexpr (sizeof(T) == 4) {
         v[0] = __uint_as_float(r.q[0].x); v[1] = __uint_as_float(r.q[0].y); v[2] = __uint_as_float(r.q[0].z); v[3] = __uint_as_float(r.q[0].w);
@@ -72,20 +59,14 @@ __device__ __forceinline__ void rs_fma_row(const RsRaw<T> &r, float w, float (&a
     } else {
         unpack_raw(static_cast<const T *>(nullptr), r.q[0], v);
     }
-#if defined(MSDA_SCALAR_FMA) && MSDA_SCALAR_FMA      // (A/B: eight v_fma_f32 instead of the four v_pk_fma_f32 hipcc forms)
-#pragma unroll
-    for (int c = 0; c < 8; ++c) asm("v_fma_f32 %0, %1, %2, %0" : "+v"(acc[c]) : "v"(w), "v"(v[c]));
-#else
 #pragma unroll
     for (int c = 0; c < 8; ++c) acc[c] = fmaf(w, v[c], acc[c]);
-#endif
 }
 
 // <g, row> over the lane's 8 channels
 template <typename T>
 __device__ __forceinline__ float rs_dot_row(const RsRaw<T> &r, const float (&g)[8])
 {
-#if MSDA_F16_MIX
     if constexpr (std::is_same<T, f16_t>::value) {
         const unsigned q[4] = {r.q[0].x, r.q[0].y, r.q[0].z, r.q[0].w};
         // (the first product as an FMA onto +0: the cvt + v_mul of the generic path rounds the same product once, too)
@@ -98,7 +79,6 @@ __device__ __forceinline__ float rs_dot_row(const RsRaw<T> &r, const float (&g)[
         }
         return acc;
     }
-#endif
     float v[8];
     if constexpr (sizeof(T) == 4) {
         v[0] = __uint_as_float(r.q[0].x); v[1] = __uint_as_float(r.q[0].y); v[2] = __uint_as_float(r.q[0].z); v[3] = __uint_as_float(r.q[0].w);
@@ -169,52 +149,6 @@ __device__ __forceinline__ void load_slot_points(const T *loc, const T *aw, int6
     quad_transpose4(xs, cor); quad_transpose4(ys, cor); quad_transpose4(as, cor);
 }
 
-// The same in two steps, so that the loads of the NEXT (row, slot) can be in flight while the current one is computed:
-// issue_slot_points only loads (raw registers), finish_slot_points converts and transposes.
-template <typename T> struct RawPoints { u32x4 q[sizeof(T) == 4 ? 3 : 2]; };
-
-template <typename T>
-__device__ __forceinline__ RawPoints<T> issue_slot_points(const T *loc, const T *aw, int64_t idx0, int cor, bool live)
-{
-    RawPoints<T> r;
-#pragma unroll
-    for (int i = 0; i < (sizeof(T) == 4 ? 3 : 2); ++i) r.q[i] = u32x4{0u, 0u, 0u, 0u};
-    if (live) {
-        const T *l = loc + 2 * (idx0 + 4 * cor), *a = aw + idx0 + 4 * cor;
-        r.q[0] = *reinterpret_cast<const u32x4 *>(l);
-        if constexpr (sizeof(T) == 4) {
-            r.q[1] = *reinterpret_cast<const u32x4 *>(l + 4);
-            r.q[2] = *reinterpret_cast<const u32x4 *>(a);
-        } else {
-            const u32x2 t = *reinterpret_cast<const u32x2 *>(a);
-            r.q[1].x = t.x; r.q[1].y = t.y;
-        }
-    }
-    return r;
-}
-
-template <typename T>
-__device__ __forceinline__ void finish_slot_points(const RawPoints<T> &r, int cor, bool live, float (&xs)[4], float (&ys)[4], float (&as)[4])
-{
-    float xy[8];
-    if constexpr (sizeof(T) == 4) {
-        float lo[4], hi[4];
-        unpack_raw(static_cast<const float *>(nullptr), r.q[0], lo); unpack_raw(static_cast<const float *>(nullptr), r.q[1], hi);
-        unpack_raw(static_cast<const float *>(nullptr), r.q[2], as);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { xy[i] = lo[i]; xy[4 + i] = hi[i]; }
-    } else {
-        unpack_raw(static_cast<const T *>(nullptr), r.q[0], xy);
-        unpack_raw(static_cast<const T *>(nullptr), u32x2{r.q[1].x, r.q[1].y}, as);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        xs[i] = live ? xy[2 * i] : -10.f; ys[i] = live ? xy[2 * i + 1] : -10.f;       // far outside every map
-        as[i] = live ? as[i] : 0.f;
-    }
-    quad_transpose4(xs, cor); quad_transpose4(ys, cor); quad_transpose4(as, cor);
-}
-
 // lane R's value of `v`, for every lane of the quad (R a compile-time constant)
 template <int R> __device__ __forceinline__ int quad_bcast(int v)
 {
@@ -240,4 +174,3 @@ __device__ __forceinline__ void quad_sum4(float (&d)[4])
                  "v_add_f32_dpp %3, %3, %3 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
                  : "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3]));
 }
-

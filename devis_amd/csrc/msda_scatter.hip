@@ -2,13 +2,6 @@
 #include "msda_common.h"
 #include <algorithm>
 
-#ifndef MSDA_GRP_F32
-#define MSDA_GRP_F32 512
-#endif
-#ifndef MSDA_GRP_16
-#define MSDA_GRP_16 512
-#endif
-
 namespace msda {
 namespace {
 
@@ -443,17 +436,6 @@ msda_cull_summary_kernel(const Params p)
 // cuh:125-152); terms are the products (w_corner * attn) * grad_out[c].
 constexpr unsigned kOwnNil = 0xffffffffu;
 
-// Timeline probe (-DMSDA_SCATTER_TRACE, experimental builds only): lane 0 of wave 1 of the first 8 workgroups stamps the shader
-// clock at phase boundaries; scripts/scatter_trace.py reads the stamps back through msda_debug_trace and sums the phases.
-#ifdef MSDA_SCATTER_TRACE
-constexpr int kTraceLen = 8192;
-__device__ unsigned long long g_trace[8][kTraceLen];
-__device__ int g_trace_n[8];
-#define MSDA_TR(id) do { if (tr_on && tr_n < kTraceLen) g_trace[blockIdx.x][tr_n++] = ((unsigned long long)__builtin_readcyclecounter() << 8) | (unsigned)(id); } while (0)
-#else
-#define MSDA_TR(id) do { } while (0)
-#endif
-
 // ---- group-granular variant -------------------------------------------------------------------------------------
 // A chunk is kGrpChunk (row, level) GROUPS -- the <= 4 sampling points one query puts on one level of one source frame --
 // instead of 768 single points: the points of a group share their grad_out row, so the row is staged ONCE per group
@@ -463,11 +445,11 @@ __device__ int g_trace_n[8];
 // cull thread, 6 KiB instead of 19).  Thread t of pass j handles point (t & 3) of group 256 j + t / 4; a group's 16
 // entries are one 128-byte block, so the row of an entry at LDS address A is (A - entries) >> 7.
 constexpr int kGrpList = 3 * kOwnThreads;       // survivor list entries (groups)
-template <typename T> constexpr int grp_chunk() { return sizeof(T) == 4 ? MSDA_GRP_F32 : MSDA_GRP_16; }       // groups per chunk
+constexpr int kGrpChunk = 512;                  // groups per chunk
 // (rows are staged as fp32 for every storage type: 128 bytes per group)
 template <typename T> constexpr int grp_lds_bytes()
 {
-    return grp_chunk<T>() * 128 + 128 + 16 * grp_chunk<T>() * 8 + kOwnPix * 4 + kGrpList * 4;
+    return kGrpChunk * 128 + 128 + 16 * kGrpChunk * 8 + kOwnPix * 4 + kGrpList * 4;
 }
 
 // T = storage type of loc / attn / grad_out; GV = type of grad_value as written (float, or T: include/msda.h grad_value_dtype).
@@ -486,7 +468,7 @@ __global__ void __launch_bounds__(kOwnThreads, 4)
 msda_bwd_value_grp_kernel(const Params p, int dbg)
 {
     constexpr int D = 32, kRowB = D * 4;                        // bytes of one staged grad_out row (fp32)
-    constexpr int kOwnChunk = grp_chunk<T>();                   // groups per chunk
+    constexpr int kOwnChunk = kGrpChunk;
     constexpr int kPasses = (4 * kOwnChunk + kOwnThreads - 1) / kOwnThreads;
     constexpr bool kHalf = sizeof(T) == 2;
     extern __shared__ __attribute__((aligned(128))) unsigned char lds_raw[];
@@ -514,10 +496,6 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
     const int tid = threadIdx.x, lane = tid % kWave;
     const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
     const int MD = p.M * D, L = p.L, VL = p.LA + p.LB;
-#ifdef MSDA_SCATTER_TRACE
-    const bool tr_on = blockIdx.x < 8 && tid == 64;
-    int tr_n = 0;
-#endif
     if (tid == 0) {
         int first = 0;
         for (int l = 0; l < L; ++l) {
@@ -695,7 +673,6 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
     for (unsigned it = 0;; ++it) {
         const int cur = (int)(it & 1u);
         if (!s_desc2[cur][0]) break;
-        MSDA_TR(1);                 // item start
         const int l = s_desc2[cur][1], part = s_desc2[cur][2], m = s_desc2[cur][3], f = s_desc2[cur][4], clip = s_desc2[cur][5];
         const long long *s_src_tab = s_src_tab2[cur], *s_src_loc = s_src_loc2[cur];
         const int *s_src_q0 = s_src_q02[cur], *s_src_gmv = s_src_gmv2[cur];
@@ -719,7 +696,6 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
         const int SF = 1 << sfs, nvpix = npix << sfs;
         GV *gmap = static_cast<GV *>(p.grad_value) +
                    (((int64_t)clip * p.frames + f) * p.S + s_lsi[l]) * MD + m * D;        // pixel (0, 0) of the level, head m
-        MSDA_TR(2);                 // item decoded
         const int ng = s_nsrc * p.Lq;              // candidate groups: (source, query) pairs, <= 4 points each
 
         float acc[kOwnSlots][8];
@@ -878,24 +854,17 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
             }
         };
         auto process_chunk = [&](int base, int n, bool primed, int nbase, int nn) {
-            MSDA_TR(10);            // chunk start
             stage_rows(base, n);
             if (!primed) fetch_chunk(base, n);
-            MSDA_TR(11);            // rows / points issued
 #pragma unroll
             for (int j = 0; j < kPasses; ++j)
                 if (j == 0 || n > j * (kOwnThreads / 4)) taps_link(j, hact[j], hx[j], hy[j], ha[j], hq[j]);
-            MSDA_TR(12);            // taps + links done
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's rows have landed
             stage_rows_finish(n);
-            MSDA_TR(13);            // rows landed
             __syncthreads();
-            MSDA_TR(14);            // barrier 1
             if (nn > 0) fetch_chunk(nbase, nn);
             walk();
-            MSDA_TR(15);            // walk done
             __syncthreads();
-            MSDA_TR(16);            // barrier 2
         };
 
         // ---- cull the candidate groups in batches of one per thread against the band; chunks are cut from the END
@@ -982,9 +951,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
             if (lane == 0 && total) wbase = atomicAdd(&s_cnt[ci], total);
             wbase = __shfl(wbase, 0, kWave);
             if (cnt) list[listed + wbase + v - cnt] = ent_now | (pm << 22);
-            MSDA_TR(3);             // cull batch: records consumed, survivors listed
             __syncthreads();
-            MSDA_TR(4);             // cull batch barrier
             listed += s_cnt[ci];
             ci = (ci + 1) % 3;
             if (dbg & 8) listed = 0;                    // measurement: cull only
@@ -1002,7 +969,6 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
             }
             bcur = bnext;
         }
-        MSDA_TR(5);                 // all chunks done
         if (wave == 0 && dynamic) prepare(it + 1u, cur ^ 1);
         // ---- owners store their pixels: grad_value is overwritten, every pixel of the band exactly once
         auto put4 = [&](GV *dst, float a, float b, float c, float d) {      // 4 consecutive channels, non-temporal
@@ -1077,13 +1043,8 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
                 put4(gband + (int64_t)pix * MD + c4, sum.x, sum.y, sum.z, sum.w);
             }
         }
-        MSDA_TR(6);                 // stores issued
         __syncthreads();
-        MSDA_TR(7);                 // item end
     }
-#ifdef MSDA_SCATTER_TRACE
-    if (tr_on) g_trace_n[blockIdx.x] = tr_n;
-#endif
 }
 
 // The LDS scatter kernels OVERWRITE every pixel of a level whose row fits the band budget.  Pixels they
@@ -1203,12 +1164,3 @@ int launch_scatter_grp(int dtype, bool storage_typed, const Params &p, unsigned 
 }
 
 }  // namespace msda
-
-#ifdef MSDA_SCATTER_TRACE
-extern "C" int msda_debug_trace(unsigned long long *dst, int *counts)
-{
-    if (hipMemcpyFromSymbol(dst, HIP_SYMBOL(msda::g_trace), sizeof(unsigned long long) * 8 * msda::kTraceLen) != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(counts, HIP_SYMBOL(msda::g_trace_n), sizeof(int) * 8) != hipSuccess) return -2;
-    return msda::kTraceLen;
-}
-#endif

@@ -216,9 +216,7 @@ msda_fwd_win_kernel(const Params p, const WinPlan wp, int slab_bytes)
         for (int ph = 0; ph < nph; ++ph) {
             const int la = ph == 0 ? 0 : wp.split, lb = (ph == 0 && nph == 2) ? wp.split : L;     // levels of this phase
             __syncthreads();                                   // every wave is done with the previous windows
-#if !defined(MSDA_WIN_EXP) || MSDA_WIN_EXP != 1       // (timing experiments, wrong results: 1 = no staging, 2 = no corner work)
             win_stage<T>(p, sh, slab, clip, m, f, la, lb, wave, lane);
-#endif
             __syncthreads();
 #pragma unroll 1
             for (int k = 0; k < my_tiles; ++k) {
@@ -239,9 +237,6 @@ msda_fwd_win_kernel(const Params p, const WinPlan wp, int slab_bytes)
                 const int64_t row = (((int64_t)clip * p.frames + t) * p.Lq + max(q, 0)) * p.M + m;
                 auto corner = [&](auto Sc, int A, float Wt) {
                     constexpr bool SLAB = decltype(Sc)::value;
-#if defined(MSDA_WIN_EXP) && MSDA_WIN_EXP == 2
-                    wacc[0] += Wt * (float)A; return;
-#endif
 #if defined(__HIP_DEVICE_COMPILE__)
                     const RsRaw<T> raw = rs_issue_row<T, SLAB>(rsrc, A, delta2);
                     rs_fma_row<T>(raw, Wt, wacc);
@@ -261,14 +256,7 @@ msda_fwd_win_kernel(const Params p, const WinPlan wp, int slab_bytes)
                     const unsigned invP = (65536u + (unsigned)P - 1u) / (unsigned)P;      // kk / P for kk * P < 2^16
                     const bool wide = p.wide_loads && P == 4 && npts == 16;           // (uniform) see load_slot_points
                     float xs[4], ys[4], as[4];
-#if defined(MSDA_WIN_EXP) && MSDA_WIN_EXP == 3           // (timing: no point loads)
-                    if (wide) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) { xs[i] = 0.3f + 0.001f * (float)(lane + i); ys[i] = 0.4f + 0.001f * (float)(j + i); as[i] = 0.1f; }
-                    }
-#else
                     if (wide) load_slot_points<TL>(loc, aw, idx0, cor, live, xs, ys, as);
-#endif
                     // one group: this lane's point (x, y, a) on level lv; step R serves point R of the 16 rows
                     auto group = [&](int g0, float x, float y, float a, const WinLevel &lv, bool in_phase) __attribute__((always_inline)) {
                         const WinGeom g = win_geometry<ROWSH>(x, y, a, lv, in_phase, fS, sh.zero_off);
@@ -316,11 +304,7 @@ msda_fwd_win_kernel(const Params p, const WinPlan wp, int slab_bytes)
                         const int lvl = min((int)(((unsigned)kk * invP) >> 16), L - 1);
                         const WinLevel lv = win_level(sh, lvl);
                         const bool in_phase = lvl >= la && lvl < lb;
-#if defined(MSDA_WIN_EXP) && MSDA_WIN_EXP == 4           // (timing: points loaded, nothing done with them)
-                        wacc[0] += x + y + a + (float)lv.H;
-#else
                         group(g0, x, y, a, lv, in_phase);
-#endif
                     }
                 }
                 static_for<NT>([&](auto Kc) {

@@ -83,10 +83,7 @@ enum msda_status {
 /* ABI version of the loaded library (== MSDA_ABI_VERSION it was built with). */
 int msda_version(void);
 
-/* "abi=13 arch=gfx950 timing_only=0" (ABI v13).  timing_only=1: the library was compiled with timing-only experiment macros
- * (kernels that skip part of their work to measure floors; wrong results by construction -- such a build needs
- * -DMSDA_TIMING_ONLY_BUILD to compile at all).  It prefixes every msda_last_route() with "TIMING-ONLY BUILD", its operator entry
- * points fail with MSDA_ERR_ARG unless MSDA_ENABLE_HOOKS=1, and the bindings refuse to load it without that variable. */
+/* "abi=13 arch=gfx950" (ABI v13): the ABI version and the architecture the kernels were compiled for. */
 const char *msda_build_info(void);
 
 /* Thread-local description of the last failure on this thread ("" if none). */

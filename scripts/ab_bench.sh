@@ -1,7 +1,8 @@
 #!/bin/bash
 # Same-box A/B of several builds of the library (boxes differ by +-5 %, so numbers from different gpurun calls do not
-# compare).  Builds are selected with MSDA_LIB (devis_amd/build.py: the in-tree library is never overwritten):
-#   python -m devis_amd.build -DMSDA_SOMETHING=1 --out=devis_amd/libmsda_exp_x.so        (in the build container)
+# compare).  Builds are selected with MSDA_LIB (devis_amd/build.py: the in-tree library is never overwritten); the other
+# build comes from another checkout:
+#   (cd ../other && python -m devis_amd.build --out=$PWD/devis_amd/libmsda_exp_x.so)        (in the build container)
 #   gpurun -- bash scripts/ab_bench.sh devis_amd/libmsda_hip.so devis_amd/libmsda_exp_x.so [-- bench.py args]
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Device assembly + resource usage of one translation unit: scripts/isa.sh msda_rs [-DFLAG ...]  ->  /tmp/isa/<unit>.s, /tmp/isa/<unit>.usage
+# Device assembly + resource usage of one translation unit: scripts/isa.sh msda_rs [hipcc flag ...]  ->  /tmp/isa/<unit>.s, /tmp/isa/<unit>.usage
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 u=$1; shift

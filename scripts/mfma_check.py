@@ -53,21 +53,14 @@ def main():
             t = bench._event_ms(bwd, reps, 5)
             res[("t", mode)] = t
             res[("r", mode)] = route.split("; ")[-1]
-        # the owner-computes kernel alone on the levels the matrix-pipe kernel leaves it (measurement knob; the difference to the
-        # mfma=1 time is the matrix-pipe kernel's own duration)
-        lv = 2 if "two" in os.environ.get("MFMA_OWN", "two") else 3
-        own = {}
-        for n in (3, 2):
-            ab.knobs(MSDA_SCATTER_MFMA=0, MSDA_BWD_PHASES=2, MSDA_SCATTER_OWN_LEVELS=n)
-            own[n] = bench._event_ms(bwd, reps, 5)
-        os.environ.pop("MSDA_SCATTER_MFMA", None); os.environ.pop("MSDA_SCATTER_OWN_LEVELS", None)
+        os.environ.pop("MSDA_SCATTER_MFMA", None)
         ab.knobs()
         ref, got = res[0], res[1]
         err = float((got - ref).abs().max())
         scale = float(ref.abs().max())
         nan = int(torch.isnan(got).sum())
-        print("%-11s scatter %.4f -> %.4f ms   max|diff| %.3e of scale %.3e = %.2e   nan %d   owner kernel on levels [0,3) %.4f [0,2) %.4f"
-              % (name, res[("t", 0)], res[("t", 1)], err, scale, err / max(scale, 1e-30), nan, own[3], own[2]), flush=True)
+        print("%-11s scatter %.4f -> %.4f ms   max|diff| %.3e of scale %.3e = %.2e   nan %d"
+              % (name, res[("t", 0)], res[("t", 1)], err, scale, err / max(scale, 1e-30), nan), flush=True)
 
 
 if __name__ == "__main__":
