@@ -11,8 +11,11 @@ import torch
 
 from . import build as _build
 
-MSDA_ABI_VERSION = 13
+MSDA_ABI_VERSION = 14
 BWD_WORKSPACE_BYTES = 64
+# gradient groups of msda_backward_grads / msda_temporal_backward_grads (ABI v14)
+GRAD_VALUE, GRAD_SAMPLING = 1, 2
+GRAD_ALL = GRAD_VALUE | GRAD_SAMPLING
 _DTYPE_CODE = {torch.float32: 0, torch.float64: 1, torch.bfloat16: 2, torch.float16: 3}
 
 # every symbol include/msda.h declares (tests check the library exports each of them)
@@ -21,6 +24,7 @@ EXPORTED_SYMBOLS = (
     "msda_temporal_forward", "msda_temporal_backward", "msda_backward_workspace_bytes",
     "msda_prep_forward", "msda_prep_backward", "msda_reload_knobs", "msda_last_route", "msda_mask_rows", "msda_grad_value_dtype",
     "msda_route_key", "msda_pin_route", "msda_clear_routes", "msda_route_count",
+    "msda_backward_grads", "msda_temporal_backward_grads",
 )
 
 _lib = None
@@ -56,6 +60,8 @@ def load():
         lib.msda_forward.argtypes = [_ci] + [_vp] * 5 + [_ci] * 7 + [_vp, _vp, _vp, _vp]
         lib.msda_backward.restype = _ci
         lib.msda_backward.argtypes = [_ci] + [_vp] * 6 + [_ci] * 7 + [_vp, _ci] + [_vp] * 3 + [ctypes.c_longlong, _vp, _vp, _vp]
+        lib.msda_backward_grads.restype = _ci
+        lib.msda_backward_grads.argtypes = [_ci] + lib.msda_backward.argtypes
         lib.msda_grad_value_dtype.restype = _ci
         lib.msda_grad_value_dtype.argtypes = [_ci] * 11 + [_vp]
         lib.msda_backward_workspace_bytes.restype = ctypes.c_longlong
@@ -64,6 +70,8 @@ def load():
         lib.msda_temporal_forward.argtypes = [_ci] + [_vp] * 8 + [_ci] * 10 + [_vp, _vp, _vp, _vp]
         lib.msda_temporal_backward.restype = _ci
         lib.msda_temporal_backward.argtypes = [_ci] + [_vp] * 9 + [_ci] * 10 + [_vp, _ci] + [_vp] * 5 + [ctypes.c_longlong, _vp, _vp, _vp]
+        lib.msda_temporal_backward_grads.restype = _ci
+        lib.msda_temporal_backward_grads.argtypes = [_ci] + lib.msda_temporal_backward.argtypes
         lib.msda_prep_forward.restype = _ci
         lib.msda_prep_forward.argtypes = [_ci] + [_vp] * 7 + [ctypes.c_longlong] + [_ci] * 6 + [ctypes.c_longlong] + [_vp] * 5
         lib.msda_last_route.restype = ctypes.c_char_p
@@ -394,6 +402,31 @@ def backward(value, shapes, lsi, loc, aw, grad_out, grad_value, grad_loc, grad_a
     _check(rc, "msda_backward")
 
 
+def _grads_workspace(grads, workspace, device, batch, num_query, num_heads, virtual_levels):
+    """A call without GRAD_VALUE runs no scatter and needs no workspace (include/msda.h)."""
+    if workspace is not None or not grads & GRAD_VALUE:
+        return workspace
+    return bwd_workspace(device, batch, num_query, num_heads, virtual_levels)
+
+
+def _ws_bytes(ws):
+    return 0 if ws is None else ws.numel() * ws.element_size()
+
+
+def backward_grads(grads, value, shapes, lsi, loc, aw, grad_out, grad_value, grad_loc, grad_aw, workspace=None):
+    """msda_backward_grads: only the gradient groups in `grads` (GRAD_VALUE: grad_value; GRAD_SAMPLING: grad_loc and
+    grad_aw).  The outputs of a group that is not asked for may be None and are not written."""
+    N, S, M, D = value.shape
+    _, Lq, _, L, P, _ = loc.shape
+    with _on(value.device):
+        ws = _grads_workspace(grads, workspace, value.device, N, Lq, M, L)
+        rc = load().msda_backward_grads(
+            grads, type_code(value.dtype, loc.dtype), _p(value), _p(shapes), _p(lsi), _p(loc), _p(aw), _p(grad_out),
+            N, S, M, D, L, Lq, P, _p(grad_value), dtype_code(grad_value.dtype) if grad_value is not None else 0, _p(grad_loc),
+            _p(grad_aw), _p(ws), _ws_bytes(ws), value_strides(value), shapes_hint(shapes), _stream(value))
+    _check(rc, "msda_backward_grads")
+
+
 def temporal_forward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, clips, out):
     G, S, M, D = value.shape
     frames = G // clips
@@ -423,6 +456,25 @@ def temporal_backward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_o
             _p(grad_value), dtype_code(grad_value.dtype), _p(gloc_c), _p(gaw_c), _p(gloc_t), _p(gaw_t), _p(ws), ws.numel() * 4,
             value_strides(value, frames), shapes_hint(shapes), _stream(value))
     _check(rc, "msda_temporal_backward")
+
+
+def temporal_backward_grads(grads, value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_out, clips,
+                            grad_value, gloc_c, gaw_c, gloc_t, gaw_t, workspace=None):
+    """msda_temporal_backward_grads: as temporal_backward, for the gradient groups in `grads` only (GRAD_SAMPLING: the
+    four grad_loc / grad_aw outputs).  The outputs of a group that is not asked for may be None."""
+    G, S, M, D = value.shape
+    frames = G // clips
+    _, Lq, _, L, Pc, _ = loc_c.shape
+    window = ftab.shape[1] if ftab is not None else 0
+    Pt = loc_t.shape[4] if window else 1
+    with _on(value.device):
+        ws = _grads_workspace(grads, workspace, value.device, G, Lq, M, L * (1 + window))
+        rc = load().msda_temporal_backward_grads(
+            grads, type_code(value.dtype, loc_c.dtype), _p(value), _p(shapes), _p(lsi), _p(ftab), _p(loc_c), _p(aw_c),
+            _p(loc_t), _p(aw_t), _p(grad_out), clips, frames, window, S, M, D, L, Lq, Pc, Pt,
+            _p(grad_value), dtype_code(grad_value.dtype) if grad_value is not None else 0, _p(gloc_c), _p(gaw_c), _p(gloc_t),
+            _p(gaw_t), _p(ws), _ws_bytes(ws), value_strides(value, frames), shapes_hint(shapes), _stream(value))
+    _check(rc, "msda_temporal_backward_grads")
 
 
 def prep_forward(off_c, off_t, logit_c, logit_t, ref_c, ref_t, shapes, rows, M, L, W, Pc, Pt, loc_c, loc_t, aw_c, aw_t, ld=0):

@@ -480,8 +480,11 @@ bool storage_typed_grad_value_ok(int dtype, const Params &p)
     return true;
 }
 
-// Launches the forward, or the backward's gather pass + scatter, on the tile / resident-slab / scatter kernels.
-int launch_fast(int dtype, const Params &p, bool bwd, hipStream_t stream)
+// Launches the forward, or the backward's gather pass + scatter, on the tile / resident-slab / scatter kernels.  `grads`
+// (backward): the gradient groups asked for (msda_backward_grads) -- without kGradValue the gather pass runs as in the full
+// call but leaves no culling records and nothing follows it; without kGradSampling the culling-records kernel stands in for
+// the gather pass in front of the full call's scatter.
+int launch_fast(int dtype, const Params &p, bool bwd, hipStream_t stream, int grads)
 {
     const int esz = elem_bytes(dtype), VEC = 16 / esz, G = p.D / VEC, RPW = kWave / G;
     const int64_t tiles = (int64_t)p.groups * ((p.Lq + RPW - 1) / RPW);
@@ -553,11 +556,17 @@ int launch_fast(int dtype, const Params &p, bool bwd, hipStream_t stream)
         while (waves > 1 && lds_of(waves) > 48 * 1024) --waves;
         return launch_fwd_tile(dtype, G, p, (unsigned)blocks, waves > 1 ? lds_of(waves) : lds, stream, waves);
     }
+    const bool want_value = (grads & kGradValue) != 0, want_sampling = (grads & kGradSampling) != 0;
     if (!scatter_applicable(p)) {
+        if (!want_value) {      // the one-kernel backward without its atomics: no records, no tickets, nothing to zero-fill
+            Params pq = p;
+            pq.bbox = nullptr; pq.bsum = nullptr; pq.workspace = nullptr;
+            return launch_bwd_tile(dtype, G, false, pq, (unsigned)blocks, tile_lds_bytes(RPW, p.LA + p.LB, true), stream);
+        }
         if (p.gv_storage) return fail(MSDA_ERR_ARG, "msda backward: this call needs grad_value in the arithmetic type (see msda_grad_value_dtype)%s");
         if (hipMemsetAsync(p.grad_value, 0, (size_t)p.groups * p.S * p.M * p.D * sizeof(float), stream) != hipSuccess)
             return fail(MSDA_ERR_HIP, "msda backward: hipMemsetAsync(grad_value) failed%s");
-        return launch_bwd_tile(dtype, G, true, p, (unsigned)blocks, lds, stream);
+        return launch_bwd_tile(dtype, G, true, p, (unsigned)blocks, lds, stream, !want_sampling);
     }
     // Which levels the owner-computes scatter walks and which go to the matrix pipe is settled BEFORE the gather pass: the gather
     // pass leaves culling records only for the levels the owner kernel will walk band by band (16 clips: 0.400 -> 0.394 ms, 22 MB of stores less).
@@ -607,19 +616,38 @@ int launch_fast(int dtype, const Params &p, bool bwd, hipStream_t stream)
     }
     Params pq = p;                                 // the gather pass's view
     pq.rec_mask = rec_mask;
+    if (!want_value) {                             // no scatter follows: no records, no tickets
+        pq.bbox = nullptr; pq.bsum = nullptr;
+        pq.workspace = nullptr; pq.rec_mask = 0;
+    }
+    // Does the full call's gather pass leave (min, max) interval records?  Only the tile kernel writes those, so it must run
+    // then.  A call without kGradValue leaves no records and needs no workspace, but takes the full call's kernel: the one a
+    // full call with a workspace of msda_backward_workspace_bytes() takes (what the Python binding always passes).
+    const bool interval_records = want_value ? (p.bbox != nullptr && !p.cull_points)
+                                             : (knobs().bwd_cull != 0 && !(knobs().bwd_cull != 2 && owner_scatter_applicable(p, esz)));
     // MSDA_BWD_PHASES (measurement hook for bench.py): 1 = gather pass only, 2 = scatter pass only
     // (needs the workspace a previous gather pass filled), 3 = both (default)
     const int phases = knobs().bwd_phases;
     int rc = MSDA_OK;
-    if (phases & 1) {
+    if ((phases & 1) && !want_sampling) {
+        // grad_value alone: the records (and zeroed tickets) the gather pass would have left, from the sampling locations only
+        if (pq.workspace) {
+            rc = launch_cull_records(dtype, pq, stream);
+            if (rc) return rc;
+        }
+        if (pq.cull_points && pq.bsum) {
+            rc = launch_cull_summary(pq, stream);
+            if (rc) return rc;
+        }
+    } else if (phases & 1) {
         bool done = false;
         WinPlan w;
-        if ((p.cull_points || !p.bbox) && window_route(knobs().bwd_win, w)) {
+        if (!interval_records && window_route(knobs().bwd_win, w)) {
             rc = launch_bwd_win(dtype, pq, w, stream);
             if (rc) return rc;
             done = true;
         }
-        if (!done && rs_ok && (p.cull_points || !p.bbox)) {
+        if (!done && rs_ok && !interval_records) {
             // resident-slab gather pass: same applicability rule as the forward
             const int mode = knobs().bwd_rs;
             int tpw = rs_tiles_per_wave(p, rs_tiles_per_clip, host_pixels_below(p, l0_host) * rs_row, mode == 1, l2_budget,
@@ -681,12 +709,12 @@ int launch_fast(int dtype, const Params &p, bool bwd, hipStream_t stream)
             rc = launch_bwd_tile(dtype, G, false, pq, (unsigned)blocks, lds, stream);
             if (rc) return rc;
         }
-        if (p.cull_points && p.bsum) {       // block summaries of the per-point records just written
+        if (pq.cull_points && pq.bsum) {     // block summaries of the per-point records just written
             rc = launch_cull_summary(pq, stream);
             if (rc) return rc;
         }
     }
-    if (!(phases & 2)) return rc;
+    if (!(phases & 2) || !want_value) return rc;
     unsigned grid = (unsigned)device_cus();      // persistent: one 1024-thread workgroup per CU
     grid -= grid % 8;                            // multiple of the XCD count: item % M stays put
     if (owner_route) {
@@ -739,7 +767,7 @@ bool fast_path_takes(int dtype, const Params &p, bool bwd)
     return true;
 }
 
-int run(int dtype, const Params &p_in, bool bwd, hipStream_t stream)
+int run(int dtype, const Params &p_in, bool bwd, hipStream_t stream, int grads = kGradAll)
 {
     if (dtype < MSDA_F32 || dtype > MSDA_F16_LOC32) return fail(MSDA_ERR_DTYPE, "msda: unknown dtype code%s");
     Params p = p_in;
@@ -756,9 +784,9 @@ int run(int dtype, const Params &p_in, bool bwd, hipStream_t stream)
     p.wide_loads = aligned16(p.locA) && aligned16(p.awA) && (p.LB == 0 || (aligned16(p.locB) && aligned16(p.awB))) &&
                    (knobs().dbg & 128) == 0;                  // (measurement: MSDA_DBG=128 keeps the narrow loads)
     if (p.groups == 0 || p.Lq == 0) return MSDA_OK;
-    if (!knobs().force_generic && fast_path_takes(dtype, p, bwd)) return launch_fast(dtype, p, bwd, stream);
+    if (!knobs().force_generic && fast_path_takes(dtype, p, bwd)) return launch_fast(dtype, p, bwd, stream, grads);
     if (p.gv_storage) return fail(MSDA_ERR_ARG, "msda backward: this call needs grad_value in the arithmetic type (see msda_grad_value_dtype)%s");
-    return launch_generic(dtype, p, bwd, stream);
+    return launch_generic(dtype, p, bwd, stream, grads);
 }
 
 // `grad_value_dtype` of the backward entry points: the arithmetic type, or the 16-bit storage type where allowed.
@@ -850,7 +878,7 @@ int msda_version(void) { return MSDA_ABI_VERSION; }
 
 const char *msda_build_info(void)
 {
-    return "abi=13 arch=gfx950";
+    return "abi=14 arch=gfx950";
 }
 
 void msda_reload_knobs(void) { load_knobs(); }
@@ -958,14 +986,33 @@ int msda_backward(int dtype, const void *value, const int64_t *spatial_shapes,
                   void *workspace, long long workspace_bytes, const int64_t *value_strides,
                   const int64_t *spatial_shapes_host, void *stream)
 {
+    return msda_backward_grads(kGradAll, dtype, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out,
+                               batch, spatial_size, num_heads, channels, num_levels, num_query, num_point, grad_value,
+                               grad_value_dtype, grad_sampling_loc, grad_attn_weight, workspace, workspace_bytes, value_strides,
+                               spatial_shapes_host, stream);
+}
+
+int msda_backward_grads(int grads, int dtype, const void *value, const int64_t *spatial_shapes,
+                        const int64_t *level_start_index, const void *sampling_loc,
+                        const void *attn_weight, const void *grad_out,
+                        int batch, int spatial_size, int num_heads, int channels, int num_levels,
+                        int num_query, int num_point,
+                        void *grad_value, int grad_value_dtype, void *grad_sampling_loc, void *grad_attn_weight,
+                        void *workspace, long long workspace_bytes, const int64_t *value_strides,
+                        const int64_t *spatial_shapes_host, void *stream)
+{
     g_err[0] = 0; g_route[0] = 0;
+    if (grads & ~kGradAll) return fail(MSDA_ERR_ARG, "msda backward: grads must be a mask of MSDA_GRAD_VALUE and MSDA_GRAD_SAMPLING%s");
+    if (grads == 0) return MSDA_OK;
+    const bool want_value = (grads & kGradValue) != 0, want_sampling = (grads & kGradSampling) != 0;
     int rc = check_common(value, spatial_shapes, level_start_index, batch, spatial_size, num_heads,
                           channels, num_levels, num_query);
     if (rc) return rc;
     if (batch == 0) return MSDA_OK;
-    if (num_query == 0) return zero_grad_value(grad_value_dtype, grad_value, batch, spatial_size, num_heads, channels, stream);
-    if (!sampling_loc || !attn_weight || !grad_out || !grad_value || !grad_sampling_loc ||
-        !grad_attn_weight || num_point <= 0)
+    if (num_query == 0)
+        return want_value ? zero_grad_value(grad_value_dtype, grad_value, batch, spatial_size, num_heads, channels, stream) : MSDA_OK;
+    if (!sampling_loc || !attn_weight || !grad_out || (want_value && !grad_value) ||
+        (want_sampling && (!grad_sampling_loc || !grad_attn_weight)) || num_point <= 0)
         return fail(MSDA_ERR_ARG, "msda_backward: null pointer or non-positive num_point%s");
     Params p;
     memset(&p, 0, sizeof(p));
@@ -979,9 +1026,9 @@ int msda_backward(int dtype, const void *value, const int64_t *spatial_shapes,
     p.shapes_host = spatial_shapes_host;
     rc = set_value_strides(p, value_strides);
     if (rc) return rc;
-    rc = set_grad_value_dtype(dtype, grad_value_dtype, p);
+    rc = want_value ? set_grad_value_dtype(dtype, grad_value_dtype, p) : MSDA_OK;
     if (rc) return rc;
-    return run(dtype, p, true, static_cast<hipStream_t>(stream));
+    return run(dtype, p, true, static_cast<hipStream_t>(stream), grads);
 }
 
 int msda_temporal_forward(int dtype, const void *value, const int64_t *spatial_shapes,
@@ -1027,7 +1074,28 @@ int msda_temporal_backward(int dtype, const void *value, const int64_t *spatial_
                            void *grad_loc_temp, void *grad_aw_temp, void *workspace, long long workspace_bytes,
                            const int64_t *value_strides, const int64_t *spatial_shapes_host, void *stream)
 {
+    return msda_temporal_backward_grads(kGradAll, dtype, value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr,
+                                        loc_temp, aw_temp, grad_out, clips, frames, window, spatial_size, num_heads, channels,
+                                        num_levels, num_query, num_curr_point, num_temp_point, grad_value, grad_value_dtype,
+                                        grad_loc_curr, grad_aw_curr, grad_loc_temp, grad_aw_temp, workspace, workspace_bytes,
+                                        value_strides, spatial_shapes_host, stream);
+}
+
+int msda_temporal_backward_grads(int grads, int dtype, const void *value, const int64_t *spatial_shapes,
+                                 const int64_t *level_start_index, const int32_t *frame_table,
+                                 const void *loc_curr, const void *aw_curr,
+                                 const void *loc_temp, const void *aw_temp, const void *grad_out,
+                                 int clips, int frames, int window, int spatial_size, int num_heads,
+                                 int channels, int num_levels, int num_query,
+                                 int num_curr_point, int num_temp_point,
+                                 void *grad_value, int grad_value_dtype, void *grad_loc_curr, void *grad_aw_curr,
+                                 void *grad_loc_temp, void *grad_aw_temp, void *workspace, long long workspace_bytes,
+                                 const int64_t *value_strides, const int64_t *spatial_shapes_host, void *stream)
+{
     g_err[0] = 0; g_route[0] = 0;
+    if (grads & ~kGradAll) return fail(MSDA_ERR_ARG, "msda backward: grads must be a mask of MSDA_GRAD_VALUE and MSDA_GRAD_SAMPLING%s");
+    if (grads == 0) return MSDA_OK;
+    const bool want_value = (grads & kGradValue) != 0, want_sampling = (grads & kGradSampling) != 0;
     int rc = check_common(value, spatial_shapes, level_start_index, clips, spatial_size, num_heads,
                           channels, num_levels, num_query);
     if (rc) return rc;
@@ -1035,9 +1103,10 @@ int msda_temporal_backward(int dtype, const void *value, const int64_t *spatial_
         return fail(MSDA_ERR_ARG, "msda_temporal_backward: bad frames/window/points%s");
     if (clips == 0) return MSDA_OK;
     if (num_query == 0)
-        return zero_grad_value(grad_value_dtype, grad_value, clips * frames, spatial_size, num_heads, channels, stream);
-    if (!loc_curr || !aw_curr || !grad_out || !grad_value || !grad_loc_curr || !grad_aw_curr ||
-        (window > 0 && (!frame_table || !loc_temp || !aw_temp || !grad_loc_temp || !grad_aw_temp)))
+        return want_value ? zero_grad_value(grad_value_dtype, grad_value, clips * frames, spatial_size, num_heads, channels, stream)
+                          : MSDA_OK;
+    if (!loc_curr || !aw_curr || !grad_out || (want_value && !grad_value) || (want_sampling && (!grad_loc_curr || !grad_aw_curr)) ||
+        (window > 0 && (!frame_table || !loc_temp || !aw_temp || (want_sampling && (!grad_loc_temp || !grad_aw_temp)))))
         return fail(MSDA_ERR_ARG, "msda_temporal_backward: null pointer argument%s");
     Params p;
     memset(&p, 0, sizeof(p));
@@ -1053,9 +1122,9 @@ int msda_temporal_backward(int dtype, const void *value, const int64_t *spatial_
     p.shapes_host = spatial_shapes_host;
     rc = set_value_strides(p, value_strides);
     if (rc) return rc;
-    rc = set_grad_value_dtype(dtype, grad_value_dtype, p);
+    rc = want_value ? set_grad_value_dtype(dtype, grad_value_dtype, p) : MSDA_OK;
     if (rc) return rc;
-    return run(dtype, p, true, static_cast<hipStream_t>(stream));
+    return run(dtype, p, true, static_cast<hipStream_t>(stream), grads);
 }
 
 int msda_prep_forward(int dtype, const void *offsets_curr, const void *offsets_temp, const void *logits_curr,

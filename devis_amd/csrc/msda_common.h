@@ -332,6 +332,8 @@ constexpr int kOwnMaxSorted = 256;            // (level, band) pairs the owner-c
 constexpr int kScatterMaxSources = 64;      // 1 + frames * window must fit
 constexpr int kCullBlock = 64;              // queries per block summary of the culling records
 constexpr int kLiveWords = 64;              // up to 2048 cull batches per item take the block-summary pre-pass
+// gradient groups of a backward call (include/msda.h, msda_backward_grads)
+constexpr int kGradValue = MSDA_GRAD_VALUE, kGradSampling = MSDA_GRAD_SAMPLING, kGradAll = kGradValue | kGradSampling;
 
 // levels [result, L) form the slab: the last levels whose pixels are one contiguous tail of the map and
 // whose [pixels, D] slab fits `cap` elements
@@ -475,7 +477,9 @@ int dispatch_types(int dtype, F &&f)
 // ---- per-family launchers (each translation unit owns its kernels; MSDA_OK or a negative msda_status) ----
 // msda_tile.hip: G = D / (16 / sizeof(T)) lanes per row, one wave per workgroup
 int launch_fwd_tile(int dtype, int G, const Params &p, unsigned blocks, size_t lds, hipStream_t stream, int waves = 1);
-int launch_bwd_tile(int dtype, int G, bool atomics, const Params &p, unsigned blocks, size_t lds, hipStream_t stream);
+// value_only: grad_value alone (with atomics; no loads of `value`, no grad_loc / grad_attn)
+int launch_bwd_tile(int dtype, int G, bool atomics, const Params &p, unsigned blocks, size_t lds, hipStream_t stream,
+                    bool value_only = false);
 // msda_rs.hip: resident-slab kernels (D = 32); nt = tiles per wave of the forward (1, 2, 4); first_slab_level = the host's
 // guess of the first pyramid level inside the slab (1 or 2: picks the kernel whose software-pipelined slot body is compiled
 // for it -- speed only: a kernel whose device-side level differs falls back to its plain loop)
@@ -486,13 +490,17 @@ int launch_bwd_win(int dtype, const Params &p, const WinPlan &w, hipStream_t str
 // msda_scatter.hip: grad_value
 int launch_zero_unowned(const Params &p, int cap_slots, int grad_value_elem_bytes, hipStream_t stream);
 int launch_cull_summary(const Params &p, hipStream_t stream);
+// every culling record the scatter reads (and the zeroed ticket counters), as the gather pass leaves them, from the sampling
+// locations alone: for a backward that runs the scatter without the gather pass.  The levels in p.rec_mask only, as
+// per-point records (p.cull_points) or (min, max) intervals (their route has rec_mask = every level).
+int launch_cull_records(int dtype, const Params &p, hipStream_t stream);
 int launch_scatter_lds(int dtype, int G, const Params &p, unsigned grid, int cap_bytes, int dbg, hipStream_t stream);
 int launch_scatter_grp(int dtype, bool storage_typed_grad_value, const Params &p, unsigned grid, int dbg, hipStream_t stream);
 // msda_mfma.hip: grad_value of the trailing levels [l0, L) (at most 2, `tiles` = mfma_scatter_tiles(their pixels)) on the matrix pipe
 int mfma_scatter_tiles(long long pixels);
 int launch_scatter_mfma(int dtype, bool storage_typed_grad_value, const Params &p, int l0, int tiles, hipStream_t stream);
 // msda_generic.hip: any-shape kernels, the modules' fused pre-op pass, the padding-mask pass
-int launch_generic(int dtype, const Params &p, bool bwd, hipStream_t stream);
+int launch_generic(int dtype, const Params &p, bool bwd, hipStream_t stream, int grads = kGradAll);
 int launch_prep(int dtype, const PrepParams &p, bool bwd, hipStream_t stream);
 int launch_mask_rows(int bytes_per_thread, char *rows, const uint8_t *mask, long long pixels, int chunks,
                      long long stride_bytes, unsigned blocks, hipStream_t stream);

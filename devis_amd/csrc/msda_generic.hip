@@ -129,6 +129,68 @@ msda_bwd_generic_kernel(const Params p, int64_t rows)
     }
 }
 
+// One group of gradients alone (include/msda.h, msda_backward_grads), same rows and lanes as above.  A kernel of its own, not
+// flags on msda_bwd_generic_kernel: a template parameter more on that kernel -- even an unused one -- changes the code the
+// compiler emits for its shipped instantiations.  The grad_loc / grad_attn arithmetic below is that kernel's, statement for
+// statement (tests/test_grad_subset_gpu.py holds the two bitwise equal):
+//   VALUE (kGradValue)   grad_value with float atomics; `value` is never read and there are no wave sums;
+//   otherwise            grad_loc / grad_attn without the atomics (grad_value is neither zero-filled nor written).
+template <typename T, typename TL, typename A, bool VALUE>
+__global__ void __launch_bounds__(kWave)
+msda_bwd_generic_part_kernel(const Params p, int64_t rows)
+{
+    const int MD = p.M * p.D;
+    const int lane = threadIdx.x;
+    for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const int m = (int)(row % p.M);
+        const int group = (int)(row / ((int64_t)p.M * p.Lq));
+        const int clip = group / p.frames, t = group - clip * p.frames;
+        const T *value = static_cast<const T *>(p.value) + clip * p.v_clip + m * p.v_head;
+        A *gvalue = static_cast<A *>(p.grad_value) + (int64_t)clip * p.frames * p.S * MD + m * p.D;
+        const T *go = static_cast<const T *>(p.grad_out) + row * p.D;
+        for (int arr = 0; arr < 2; ++arr) {
+            const TL *loc = static_cast<const TL *>(arr ? p.locB : p.locA);
+            const TL *aw = static_cast<const TL *>(arr ? p.awB : p.awA);
+            TL *gloc = static_cast<TL *>(arr ? p.glocB : p.glocA);
+            TL *gaw = static_cast<TL *>(arr ? p.gawB : p.gawA);
+            const int P = arr ? p.PB : p.PA, nl = arr ? p.LB : p.LA, LP = nl * P;
+            for (int pt = 0; pt < LP; ++pt) {
+                const Level lv = make_level(p, t, (arr ? p.LA : 0) + pt / P);
+                const int64_t idx = row * LP + pt;
+                const A a = (A)Store<TL>::get(aw + idx);
+                const GTaps<A> tp = make_gtaps<A>((A)Store<TL>::get(loc + 2 * idx),
+                                                  (A)Store<TL>::get(loc + 2 * idx + 1), lv, 1);
+                if constexpr (VALUE) {
+                    if (!tp.valid) continue;
+                    for (int c = lane; c < p.D; c += kWave) {
+                        const A gc = (A)Store<T>::get(go + c);
+                        for (int k = 0; k < 4; ++k)
+                            if (tp.valid & (1 << k)) atomic_accumulate(gvalue + tp.off[k] * MD + c, tp.w[k] * a * gc);
+                    }
+                } else {
+                    A d[4] = {0, 0, 0, 0};
+                    if (tp.valid) {
+                        for (int c = lane; c < p.D; c += kWave) {
+                            const A gc = (A)Store<T>::get(go + c);
+                            for (int k = 0; k < 4; ++k)
+                                if (tp.valid & (1 << k)) d[k] += gc * (A)Store<T>::get(value + tp.off[k] * p.v_pix + c);
+                        }
+                    }
+                    for (int k = 0; k < 4; ++k) d[k] = wave_sum<A>(d[k]);
+                    if (lane == 0) {
+                        const A hh = 1 - tp.lh, hw = 1 - tp.lw;
+                        const A g_aw = tp.w[0] * d[0] + tp.w[1] * d[1] + tp.w[2] * d[2] + tp.w[3] * d[3];
+                        const A g_w = hh * (d[1] - d[0]) + tp.lh * (d[3] - d[2]);
+                        const A g_h = hw * (d[2] - d[0]) + tp.lw * (d[3] - d[1]);
+                        Store<TL>::put(gaw + idx, g_aw);
+                        Store<TL>::put(gloc + 2 * idx, (A)lv.W * g_w * a);
+                        Store<TL>::put(gloc + 2 * idx + 1, (A)lv.H * g_h * a);
+                    }
+                }
+            }
+        }
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 // pre-op fusion: the modules' chain between their Linears and the operator --
@@ -299,9 +361,21 @@ __global__ __launch_bounds__(256) void msda_mask_rows_kernel(char *__restrict__ 
 }
 
 template <typename T, typename TL, typename A>
-int generic(const Params &p, bool bwd, hipStream_t stream)
+int generic(const Params &p, bool bwd, int grads, hipStream_t stream)
 {
     const int64_t rows = (int64_t)p.groups * p.Lq * p.M;
+    if (bwd && grads == kGradSampling) {        // no grad_value: no zero-fill, no atomics
+        const unsigned blocks = (unsigned)(rows < 65536 * 16 ? rows : 65536 * 16);
+        hipLaunchKernelGGL((msda_bwd_generic_part_kernel<T, TL, A, false>), dim3(blocks), dim3(kWave), 0, stream, p, rows);
+        return check_launch("msda backward (generic kernel, grad_loc/grad_attn)");
+    }
+    if (bwd && grads == kGradValue) {
+        if (hipMemsetAsync(p.grad_value, 0, (size_t)p.groups * p.S * p.M * p.D * sizeof(A), stream) != hipSuccess)
+            return fail(MSDA_ERR_HIP, "msda backward: hipMemsetAsync(grad_value) failed%s");
+        const unsigned blocks = (unsigned)(rows < 65536 * 16 ? rows : 65536 * 16);
+        hipLaunchKernelGGL((msda_bwd_generic_part_kernel<T, TL, A, true>), dim3(blocks), dim3(kWave), 0, stream, p, rows);
+        return check_launch("msda backward (generic kernel, grad_value only, global atomics)");
+    }
     if (bwd) {
         if (hipMemsetAsync(p.grad_value, 0, (size_t)p.groups * p.S * p.M * p.D * sizeof(A), stream) != hipSuccess)
             return fail(MSDA_ERR_HIP, "msda backward: hipMemsetAsync(grad_value) failed%s");
@@ -329,11 +403,11 @@ int prep(const PrepParams &p, bool bwd, hipStream_t stream)
 
 }  // namespace
 
-int launch_generic(int dtype, const Params &p, bool bwd, hipStream_t stream)
+int launch_generic(int dtype, const Params &p, bool bwd, hipStream_t stream, int grads)
 {
-    if (dtype == MSDA_F64) return generic<double, double, double>(p, bwd, stream);
+    if (dtype == MSDA_F64) return generic<double, double, double>(p, bwd, grads, stream);
     return dispatch_types(dtype, [&](auto t, auto tl) {
-        return generic<typename decltype(t)::type, typename decltype(tl)::type, float>(p, bwd, stream);
+        return generic<typename decltype(t)::type, typename decltype(tl)::type, float>(p, bwd, grads, stream);
     });
 }
 

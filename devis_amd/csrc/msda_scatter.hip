@@ -391,6 +391,79 @@ msda_bwd_value_lds_kernel(const Params p, int cap_slots, int dbg)
     }
 }
 
+// Culling records WITHOUT the gather pass (the backward of a call that wants grad_value alone): the same bytes the gather
+// passes leave in p.bbox -- per point the top tap row floor(y * H - 0.5) as int16 (kNoRow16 for a point outside the range
+// test of make_taps, and for the slots past P), or per (row, level) the (min, max) of those rows (INT_MAX, INT_MIN when no
+// point is in range) -- computed from the sampling locations alone: which rows a point touches depends on neither `value`
+// nor the attention weight.  One thread per (row, virtual level); consecutive threads read consecutive point groups of a row.
+template <typename TL>
+__device__ __forceinline__ void load_points(const TL *loc, int P, bool wide, float (&x)[4], float (&y)[4])
+{
+    if (wide && P == 4) {       // the four points of a level: 32 / 16 contiguous, 16-byte aligned bytes
+        if constexpr (sizeof(TL) == 4) {
+            const float4 a = reinterpret_cast<const float4 *>(loc)[0], b = reinterpret_cast<const float4 *>(loc)[1];
+            x[0] = a.x; y[0] = a.y; x[1] = a.z; y[1] = a.w; x[2] = b.x; y[2] = b.y; x[3] = b.z; y[3] = b.w;
+        } else {
+            const uint4 q = *reinterpret_cast<const uint4 *>(loc);
+            unpack_pair(loc, q.x, x[0], y[0]); unpack_pair(loc, q.y, x[1], y[1]);
+            unpack_pair(loc, q.z, x[2], y[2]); unpack_pair(loc, q.w, x[3], y[3]);
+        }
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        x[k] = y[k] = -10.f;    // far outside every map
+        if (k < P) load_xy(loc + 2 * k, x[k], y[k]);
+    }
+}
+
+template <typename TL, bool POINTS>
+__global__ void __launch_bounds__(256)
+msda_cull_records_kernel(const Params p, int64_t total)
+{
+    const int VL = p.LA + p.LB;
+    if (blockIdx.x == 0 && threadIdx.x < MSDA_BWD_WORKSPACE_BYTES / 4 && p.workspace) p.workspace[threadIdx.x] = 0u;   // (as the gather passes)
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t row = i / VL;                       // (group, q, m), the row order of sampling_loc
+        const int vl = (int)(i - row * VL);
+        const int lvl = vl < p.LA ? vl : (vl - p.LA) % p.L;
+        if (lvl < 32 && !((p.rec_mask >> lvl) & 1u)) continue;     // (no records for this level: Params::rec_mask)
+        const int m = (int)(row % p.M);
+        const int64_t gq = row / p.M;
+        const int q = (int)(gq % p.Lq), group = (int)(gq / p.Lq);
+        const bool arrB = vl >= p.LA;
+        const int P = arrB ? p.PB : p.PA;
+        const int nl = arrB ? p.LB : p.LA;
+        const TL *loc = static_cast<const TL *>(arrB ? p.locB : p.locA) + 2 * ((row * nl + (arrB ? vl - p.LA : vl)) * P);
+        const float H = (float)(int)p.shapes[2 * lvl], W = (float)(int)p.shapes[2 * lvl + 1];     // (as make_level / make_taps)
+        int2 rec;
+        if constexpr (POINTS) {
+            float x[4], y[4];
+            load_points<TL>(loc, P, p.wide_loads != 0, x, y);
+            int r[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float h_im = __fsub_rn(__fmul_rn(y[k], H), 0.5f), w_im = __fsub_rn(__fmul_rn(x[k], W), 0.5f);
+                const bool rng = k < P && h_im > -1.f && w_im > -1.f && h_im < H && w_im < W;      // (make_taps)
+                r[k] = rng ? min((int)floorf(h_im), 32767) : kNoRow16;
+            }
+            rec = make_int2((r[0] & 0xffff) | (r[1] << 16), (r[2] & 0xffff) | (r[3] << 16));
+        } else {
+            rec = make_int2(0x7fffffff, -0x7fffffff - 1);
+            for (int k = 0; k < P; ++k) {
+                float x, y;
+                load_xy(loc + 2 * k, x, y);
+                const float h_im = __fsub_rn(__fmul_rn(y, H), 0.5f), w_im = __fsub_rn(__fmul_rn(x, W), 0.5f);
+                if (h_im > -1.f && w_im > -1.f && h_im < H && w_im < W) {
+                    const int hl = (int)floorf(h_im);
+                    rec.x = min(rec.x, hl); rec.y = max(rec.y, hl);
+                }
+            }
+        }
+        *reinterpret_cast<int2 *>(p.bbox + ((((int64_t)group * p.M + m) * VL + vl) * p.Lq + q) * 2) = rec;
+    }
+}
+
 // Coarse culling summary for long candidate ranges (encoder shapes, Lq = S): (min, max) top tap row over blocks
 // of kCullBlock consecutive queries of every (group, head, virtual level), reduced from the per-point records
 // the gather pass left.  One wave per block.
@@ -1125,6 +1198,19 @@ int launch_cull_summary(const Params &p, hipStream_t stream)
     const unsigned sb = (unsigned)((entries + 3) / 4 < 65536 ? (entries + 3) / 4 : 65536);
     hipLaunchKernelGGL(msda_cull_summary_kernel, dim3(sb), dim3(256), 0, stream, p);
     return check_launch("msda backward (culling block summaries)");
+}
+
+int launch_cull_records(int dtype, const Params &p, hipStream_t stream)
+{
+    const int64_t total = p.bbox ? (int64_t)p.groups * p.Lq * p.M * (p.LA + p.LB) : 0;
+    const int64_t want = (total + 255) / 256;
+    const unsigned blocks = (unsigned)(want < 1 ? 1 : (want < 65536 * 4 ? want : 65536 * 4));
+    return dispatch_types(dtype, [&](auto, auto tl) {
+        using TL = typename decltype(tl)::type;
+        if (p.cull_points) hipLaunchKernelGGL((msda_cull_records_kernel<TL, true>), dim3(blocks), dim3(256), 0, stream, p, total);
+        else hipLaunchKernelGGL((msda_cull_records_kernel<TL, false>), dim3(blocks), dim3(256), 0, stream, p, total);
+        return check_launch("msda backward (culling records)");
+    });
 }
 
 int launch_scatter_lds(int dtype, int G, const Params &p, unsigned grid, int cap_bytes, int dbg, hipStream_t stream)

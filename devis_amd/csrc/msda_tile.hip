@@ -459,6 +459,47 @@ msda_bwd_tile_kernel(const Params p)
     }
 }
 
+// grad_value alone (the backward of a call whose sampling locations and attention weights need no gradient, on the route of
+// the one-kernel backward above): the same (tile, head) workgroups and lanes, grad_value[corner k] += w_k * a * grad_out with
+// global float atomics -- no loads of `value`, no dots, no grad_loc / grad_attn, no LDS.  A row's G lanes read the same point
+// (one cache line); the corner offsets are those of the dense grad_value, whatever the layout of `value`.
+template <typename T, typename TL, int G>       // T: grad_out, TL: sampling_loc / attn_weight
+__global__ void __launch_bounds__(kWave)
+msda_bwd_tile_value_kernel(const Params p)
+{
+    constexpr int VEC = Store<T>::VEC;
+    constexpr int RPW = kWave / G;
+    const int lane = threadIdx.x;
+    int m, group, q0;
+    tile_coords<RPW>(p, m, group, q0);
+    const int clip = group / p.frames, t = group - clip * p.frames;
+    const int r = lane / G, sub = lane % G;
+    if (r >= min(RPW, p.Lq - q0)) return;
+    const int MD = p.M * p.D;
+    float *__restrict__ gvalue = static_cast<float *>(p.grad_value) + (int64_t)clip * p.frames * p.S * MD + m * p.D + sub * VEC;
+    const int64_t row = ((int64_t)group * p.Lq + q0 + r) * p.M + m;
+    float g[VEC];
+    Store<T>::load(static_cast<const T *>(p.grad_out) + row * p.D + sub * VEC, g);
+    for (int arr = 0; arr < (p.LB > 0 ? 2 : 1); ++arr) {
+        const TL *loc = static_cast<const TL *>(arr ? p.locB : p.locA);
+        const TL *aw = static_cast<const TL *>(arr ? p.awB : p.awA);
+        const int P = arr ? p.PB : p.PA, LP = (arr ? p.LB : p.LA) * P, vl0 = arr ? p.LA : 0;
+#pragma unroll 1
+        for (int pt = 0; pt < LP; ++pt) {
+            const int64_t idx = row * LP + pt;
+            const float x = Store<TL>::get(loc + 2 * idx), y = Store<TL>::get(loc + 2 * idx + 1), a = Store<TL>::get(aw + idx);
+            const Taps tp = make_taps(x, y, make_level(p, t, vl0 + pt / P), MD);
+            if (!tp.valid) continue;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (!(tp.valid & (1 << k))) continue;
+                const float wa = tp.w[k] * a;
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) atomic_accumulate(gvalue + tp.off[k] + c, wa * g[c]);
+            }
+        }
+    }
+}
 
 template <typename T, typename TL, int G>
 int fwd_tile(const Params &p, unsigned blocks, size_t lds, hipStream_t stream, int waves)
@@ -477,8 +518,12 @@ int fwd_tile(const Params &p, unsigned blocks, size_t lds, hipStream_t stream, i
 }
 
 template <typename T, typename TL, int G>
-int bwd_tile(bool atomics, const Params &p, unsigned blocks, size_t lds, hipStream_t stream)
+int bwd_tile(bool atomics, bool value_only, const Params &p, unsigned blocks, size_t lds, hipStream_t stream)
 {
+    if (value_only) {
+        hipLaunchKernelGGL((msda_bwd_tile_value_kernel<T, TL, G>), dim3(blocks), dim3(kWave), 0, stream, p);
+        return check_launch("msda backward (tile kernel, grad_value only, global atomics)");
+    }
     if (atomics) {
         hipLaunchKernelGGL((msda_bwd_tile_kernel<T, TL, G, true>), dim3(blocks), dim3(kWave), lds, stream, p);
         return check_launch("msda backward (tile kernel, global atomics)");
@@ -514,11 +559,12 @@ int launch_fwd_tile(int dtype, int G, const Params &p, unsigned blocks, size_t l
     });
 }
 
-int launch_bwd_tile(int dtype, int G, bool atomics, const Params &p, unsigned blocks, size_t lds, hipStream_t stream)
+int launch_bwd_tile(int dtype, int G, bool atomics, const Params &p, unsigned blocks, size_t lds, hipStream_t stream, bool value_only)
 {
     return dispatch_types(dtype, [&](auto t, auto tl) {
         return by_lanes(G, [&](auto g) {
-            return bwd_tile<typename decltype(t)::type, typename decltype(tl)::type, decltype(g)::value>(atomics, p, blocks, lds, stream);
+            return bwd_tile<typename decltype(t)::type, typename decltype(tl)::type, decltype(g)::value>(atomics, value_only, p, blocks, lds,
+                                                                                                       stream);
         });
     });
 }

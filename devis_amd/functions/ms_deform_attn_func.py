@@ -74,24 +74,42 @@ def _forward(value, shapes, lsi, loc, aw, im2col_step, padding_mask=None):
     return output
 
 
-def _backward(value, shapes, lsi, loc, aw, grad_output, im2col_step, padding_mask=None):
+def _grads_mask(value_grad, *sampling_grads):
+    """The gradient groups of a backward (``_native.GRAD_VALUE`` / ``GRAD_SAMPLING``) from ``ctx.needs_input_grad`` flags:
+    value's, and those of the sampling locations and attention weights (one pass computes all of the latter)."""
+    return (_native.GRAD_VALUE if value_grad else 0) | (_native.GRAD_SAMPLING if any(sampling_grads) else 0)
+
+
+def _backward(value, shapes, lsi, loc, aw, grad_output, im2col_step, padding_mask=None, grads=_native.GRAD_ALL):
     """Host side of the backward: (grad_value in value's dtype, grad_loc, grad_aw).  ``padding_mask``: the bool mask
-    `value` was produced under; grad_value's masked rows come back zero."""
+    `value` was produced under; grad_value's masked rows come back zero.  ``grads``: the gradient groups to compute
+    (``_native.GRAD_VALUE`` / ``GRAD_SAMPLING``); the others are neither allocated nor computed and come back None."""
     grad_output = grad_output.contiguous()
     N = value.shape[0]
+    want_value, want_sampling = bool(grads & _native.GRAD_VALUE), bool(grads & _native.GRAD_SAMPLING)
     # all three are fully written by the library (ABI v4: no zeros_like as in cu:121; skipped points -> 0).  16-bit
     # storage: grad_value comes back in the storage type where the library can write it so (ABI v10), else in fp32
     live = N > 0 and loc.shape[1] > 0
     step = _im2col_step(N, im2col_step) if live else 0
-    acc = _native.grad_value_dtype(value[:step], shapes, loc.shape[1], loc.shape[3], loc.shape[4], grad_out=grad_output) if live else value.dtype
-    grad_value = (torch.empty if live else torch.zeros)(value.shape, dtype=acc, device=value.device)
-    grad_loc = torch.empty_like(loc)
-    grad_aw = torch.empty_like(aw)
-    if live:
+    grad_value = grad_loc = grad_aw = None
+    if want_value:
+        acc = _native.grad_value_dtype(value[:step], shapes, loc.shape[1], loc.shape[3], loc.shape[4], grad_out=grad_output) if live else value.dtype
+        grad_value = (torch.empty if live else torch.zeros)(value.shape, dtype=acc, device=value.device)
+    if want_sampling:
+        grad_loc = torch.empty_like(loc)
+        grad_aw = torch.empty_like(aw)
+    if live and grads == _native.GRAD_ALL:
         for n in range(0, N, step):
             _native.backward(value[n:n + step], shapes, lsi, loc[n:n + step], aw[n:n + step],
                              grad_output[n:n + step], grad_value[n:n + step],
                              grad_loc[n:n + step], grad_aw[n:n + step])
+    elif live and grads:
+        chunk = lambda t, n: None if t is None else t[n:n + step]       # noqa: E731
+        for n in range(0, N, step):
+            _native.backward_grads(grads, value[n:n + step], shapes, lsi, loc[n:n + step], aw[n:n + step],
+                                   grad_output[n:n + step], chunk(grad_value, n), chunk(grad_loc, n), chunk(grad_aw, n))
+    if not want_value:
+        return grad_value, grad_loc, grad_aw
     if acc != value.dtype:
         grad_value = grad_value.to(value.dtype)
     if padding_mask is not None and grad_value.numel():
@@ -134,12 +152,22 @@ class MSDeformAttnFunction(Function):
     @once_differentiable
     def backward(ctx, grad_output):
         value, shapes, lsi, loc, aw = ctx.saved_tensors
+        needs = ctx.needs_input_grad
+        grads = _grads_mask(needs[0], needs[3], needs[4])
         if torch.compiler.is_compiling():
-            grad_value, grad_loc, grad_aw = _ops().ms_deform_attn_backward(value, shapes, lsi, loc, aw, grad_output,
-                                                                           ctx.im2col_step, ctx.padding_mask)
+            if grads == _native.GRAD_ALL:
+                grad_value, grad_loc, grad_aw = _ops().ms_deform_attn_backward(value, shapes, lsi, loc, aw, grad_output,
+                                                                               ctx.im2col_step, ctx.padding_mask)
+            else:
+                grad_value, grad_loc, grad_aw = _ops().none_slots(_ops().ms_deform_attn_backward_grads(
+                    value, shapes, lsi, loc, aw, grad_output, ctx.im2col_step, grads, ctx.padding_mask))
         else:
             grad_value, grad_loc, grad_aw = _backward(value, shapes, lsi, loc, aw, grad_output, ctx.im2col_step,
-                                                      ctx.padding_mask)
+                                                      ctx.padding_mask, grads)
+        if not needs[3]:
+            grad_loc = None
+        if not needs[4]:
+            grad_aw = None
         # one gradient slot per forward argument INCLUDING the optional padding_mask: autograd accepts trailing None
         # gradients beyond the inputs apply() was given, so the 6-argument (reference) call works with the same tuple
         return grad_value, None, None, grad_loc, grad_aw, None, None
@@ -179,17 +207,27 @@ def _temporal_forward(value, spatial_shapes, level_start_index, frame_table, loc
     return out
 
 
-def _temporal_backward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_output, clips):
-    """(grad_value in value's dtype, grad_loc_c, grad_aw_c, grad_loc_t, grad_aw_t)."""
+def _temporal_backward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_output, clips, grads=_native.GRAD_ALL):
+    """(grad_value in value's dtype, grad_loc_c, grad_aw_c, grad_loc_t, grad_aw_t); the groups not in ``grads``
+    (``_native.GRAD_VALUE``: grad_value, ``GRAD_SAMPLING``: the other four) come back None."""
     grad_output = grad_output.contiguous()
     W = ftab.shape[1]
-    acc = _native.grad_value_dtype(value, shapes, loc_c.shape[1], loc_c.shape[3], loc_c.shape[4], clips=clips,
-                                   window=W, Pt=loc_t.shape[4], grad_out=grad_output)
-    grad_value = torch.empty(value.shape, dtype=acc, device=value.device)      # overwritten (ABI v4)
-    gloc_c, gaw_c = torch.empty_like(loc_c), torch.empty_like(aw_c)
-    gloc_t, gaw_t = torch.empty_like(loc_t), torch.empty_like(aw_t)
-    _native.temporal_backward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_output,
-                              clips, grad_value, gloc_c, gaw_c, gloc_t, gaw_t)
+    grad_value = gloc_c = gaw_c = gloc_t = gaw_t = None
+    if grads & _native.GRAD_VALUE:
+        acc = _native.grad_value_dtype(value, shapes, loc_c.shape[1], loc_c.shape[3], loc_c.shape[4], clips=clips,
+                                       window=W, Pt=loc_t.shape[4], grad_out=grad_output)
+        grad_value = torch.empty(value.shape, dtype=acc, device=value.device)      # overwritten (ABI v4)
+    if grads & _native.GRAD_SAMPLING:
+        gloc_c, gaw_c = torch.empty_like(loc_c), torch.empty_like(aw_c)
+        gloc_t, gaw_t = torch.empty_like(loc_t), torch.empty_like(aw_t)
+    if grads == _native.GRAD_ALL:
+        _native.temporal_backward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_output,
+                                  clips, grad_value, gloc_c, gaw_c, gloc_t, gaw_t)
+    elif grads:
+        _native.temporal_backward_grads(grads, value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_output,
+                                        clips, grad_value, gloc_c, gaw_c, gloc_t, gaw_t)
+    if grad_value is None:
+        return grad_value, gloc_c, gaw_c, gloc_t, gaw_t
     if acc != value.dtype:
         grad_value = grad_value.to(value.dtype)
     return grad_value, gloc_c, gaw_c, gloc_t, gaw_t
@@ -221,9 +259,17 @@ class MSDeformAttnTemporalFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
-        fn = _ops().temporal_backward if torch.compiler.is_compiling() else _temporal_backward
-        grad_value, gloc_c, gaw_c, gloc_t, gaw_t = fn(*ctx.saved_tensors, grad_output, ctx.clips)
-        return grad_value, None, None, None, gloc_c, gaw_c, gloc_t, gaw_t, None
+        needs = ctx.needs_input_grad
+        grads = _grads_mask(needs[0], *needs[4:8])
+        if not torch.compiler.is_compiling():
+            grad_value, gloc_c, gaw_c, gloc_t, gaw_t = _temporal_backward(*ctx.saved_tensors, grad_output, ctx.clips, grads)
+        elif grads == _native.GRAD_ALL:
+            grad_value, gloc_c, gaw_c, gloc_t, gaw_t = _ops().temporal_backward(*ctx.saved_tensors, grad_output, ctx.clips)
+        else:
+            grad_value, gloc_c, gaw_c, gloc_t, gaw_t = _ops().none_slots(
+                _ops().temporal_backward_grads(*ctx.saved_tensors, grad_output, ctx.clips, grads))
+        sampling = [g if need else None for g, need in zip((gloc_c, gaw_c, gloc_t, gaw_t), needs[4:8])]
+        return (grad_value, None, None, None, *sampling, None)
 
 
 def ms_deform_attn_core_pytorch(value, value_spatial_shapes, sampling_locations, attention_weights):

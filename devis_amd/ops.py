@@ -8,6 +8,8 @@ through the C ABI, the same numbers -- and whose fake implementation gives shape
 =============================  ==========================================================================================
 ``ms_deform_attn_forward``     ``MSDeformAttnFunction`` forward (the im2col chunk loop), + the module's ``sum(H*W) == S``
 ``ms_deform_attn_backward``    ``MSDeformAttnFunction`` backward -> (grad_value, grad_loc, grad_aw)
+``*_backward_grads``           the two backwards for a partial ``grads`` mask (``_native.GRAD_VALUE`` / ``GRAD_SAMPLING``):
+                               a group not asked for comes back as a tensor with 0 elements
 ``temporal_forward/backward``  ``MSDeformAttnTemporalFunction``
 ``prep_forward/backward``      ``MSDeformPrepFunction`` (no temporal part: ``loc_t`` / ``aw_t`` come back with 0 slots)
 ``prep_fused_forward/backward``  ``MSDeformPrepFusedFunction``
@@ -101,6 +103,39 @@ def _(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_
     return _empty(value, value.shape), torch.empty_like(sampling_loc), torch.empty_like(attn_weight)
 
 
+@_op("ms_deform_attn_backward_grads")
+def ms_deform_attn_backward_grads(value: Tensor, spatial_shapes: Tensor, level_start_index: Tensor, sampling_loc: Tensor,
+                                  attn_weight: Tensor, grad_output: Tensor, im2col_step: int, grads: int,
+                                  padding_mask: Optional[Tensor] = None) -> tuple[Tensor, Tensor, Tensor]:
+    """``MSDeformAttnFunction.backward`` for the gradient groups in ``grads`` only; the others are 0-element tensors."""
+    _F._check_inputs([("value", value), ("spatial_shapes", spatial_shapes), ("level_start_index", level_start_index),
+                      ("sampling_loc", sampling_loc), ("attn_weight", attn_weight)])
+    out = _F._backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step,
+                       padding_mask, grads)
+    return _fill_slots(out, _fake_backward_grads(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
+                                                 grad_output, im2col_step, grads, padding_mask))
+
+
+@ms_deform_attn_backward_grads.register_fake
+def _fake_backward_grads(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step,
+                         grads, padding_mask=None):
+    _F._require(0 <= grads <= _native.GRAD_ALL, "grads must be a mask of GRAD_VALUE and GRAD_SAMPLING")
+    v = grads & _native.GRAD_VALUE
+    s = grads & _native.GRAD_SAMPLING
+    return (_empty(value, value.shape if v else (0,)), _empty(sampling_loc, sampling_loc.shape if s else (0,)),
+            _empty(attn_weight, attn_weight.shape if s else (0,)))
+
+
+def _fill_slots(outputs, fakes):
+    """A custom op returns tensors: the None of a group that was not computed becomes its 0-element stand-in."""
+    return tuple(fake if t is None else t for t, fake in zip(outputs, fakes))
+
+
+def none_slots(outputs):
+    """Inverse of _fill_slots for the autograd formulas: 0-element gradient tensors -> None."""
+    return tuple(_none_slot(t) for t in outputs)
+
+
 def _setup_forward(ctx, inputs, output):
     value, shapes, lsi, loc, aw, im2col_step, padding_mask = inputs[:7]
     ctx.im2col_step = im2col_step
@@ -109,8 +144,14 @@ def _setup_forward(ctx, inputs, output):
 
 def _backward_forward(ctx, grad_output):
     value, shapes, lsi, loc, aw, padding_mask = ctx.saved_tensors
-    gv, gl, ga = ms_deform_attn_backward(value, shapes, lsi, loc, aw, grad_output, ctx.im2col_step, padding_mask)
-    return gv, None, None, gl, ga, None, None, None
+    needs = ctx.needs_input_grad
+    grads = _F._grads_mask(needs[0], needs[3], needs[4])
+    if grads == _native.GRAD_ALL:
+        gv, gl, ga = ms_deform_attn_backward(value, shapes, lsi, loc, aw, grad_output, ctx.im2col_step, padding_mask)
+    else:
+        gv, gl, ga = none_slots(ms_deform_attn_backward_grads(value, shapes, lsi, loc, aw, grad_output, ctx.im2col_step,
+                                                              grads, padding_mask))
+    return gv, None, None, gl if needs[3] else None, ga if needs[4] else None, None, None, None
 
 
 ms_deform_attn_forward.register_autograd(_backward_forward, setup_context=_setup_forward)
@@ -152,6 +193,30 @@ def _(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, 
             torch.empty_like(loc_temp), torch.empty_like(aw_temp))
 
 
+@_op("temporal_backward_grads")
+def temporal_backward_grads(value: Tensor, spatial_shapes: Tensor, level_start_index: Tensor, frame_table: Tensor,
+                            loc_curr: Tensor, aw_curr: Tensor, loc_temp: Tensor, aw_temp: Tensor, grad_output: Tensor,
+                            clips: int, grads: int) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """``MSDeformAttnTemporalFunction.backward`` for the gradient groups in ``grads`` only; the others are 0-element tensors."""
+    _F._check_inputs([("value", value), ("spatial_shapes", spatial_shapes), ("level_start_index", level_start_index),
+                      ("frame_table", frame_table), ("loc_curr", loc_curr), ("aw_curr", aw_curr), ("loc_temp", loc_temp),
+                      ("aw_temp", aw_temp)])
+    out = _F._temporal_backward(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, loc_temp,
+                                aw_temp, grad_output, clips, grads)
+    return _fill_slots(out, _fake_temporal_backward_grads(value, spatial_shapes, level_start_index, frame_table, loc_curr,
+                                                          aw_curr, loc_temp, aw_temp, grad_output, clips, grads))
+
+
+@temporal_backward_grads.register_fake
+def _fake_temporal_backward_grads(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, loc_temp,
+                                  aw_temp, grad_output, clips, grads):
+    _F._require(0 <= grads <= _native.GRAD_ALL, "grads must be a mask of GRAD_VALUE and GRAD_SAMPLING")
+    v = grads & _native.GRAD_VALUE
+    s = grads & _native.GRAD_SAMPLING
+    return (_empty(value, value.shape if v else (0,)),) + tuple(_empty(t, t.shape if s else (0,))
+                                                               for t in (loc_curr, aw_curr, loc_temp, aw_temp))
+
+
 def _setup_temporal(ctx, inputs, output):
     ctx.clips = inputs[8]
     ctx.save_for_backward(*inputs[:8])
@@ -159,8 +224,15 @@ def _setup_temporal(ctx, inputs, output):
 
 def _backward_temporal(ctx, grad_output):
     value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t = ctx.saved_tensors
-    gv, glc, gac, glt, gat = temporal_backward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_output, ctx.clips)
-    return gv, None, None, None, glc, gac, glt, gat, None
+    needs = ctx.needs_input_grad
+    grads = _F._grads_mask(needs[0], *needs[4:8])
+    if grads == _native.GRAD_ALL:
+        gv, glc, gac, glt, gat = temporal_backward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_output, ctx.clips)
+    else:
+        gv, glc, gac, glt, gat = none_slots(temporal_backward_grads(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t,
+                                                                    grad_output, ctx.clips, grads))
+    sampling = [g if need else None for g, need in zip((glc, gac, glt, gat), needs[4:8])]
+    return (gv, None, None, None, *sampling, None)
 
 
 temporal_forward.register_autograd(_backward_temporal, setup_context=_setup_temporal)

@@ -61,7 +61,7 @@
 extern "C" {
 #endif
 
-#define MSDA_ABI_VERSION 13
+#define MSDA_ABI_VERSION 14
 #define MSDA_BWD_WORKSPACE_BYTES 64   /* minimum device scratch of the backward entry points (ticket counters) */
 
 enum msda_dtype {
@@ -83,7 +83,7 @@ enum msda_status {
 /* ABI version of the loaded library (== MSDA_ABI_VERSION it was built with). */
 int msda_version(void);
 
-/* "abi=13 arch=gfx950" (ABI v13): the ABI version and the architecture the kernels were compiled for. */
+/* "abi=14 arch=gfx950" (since ABI v13): the ABI version and the architecture the kernels were compiled for. */
 const char *msda_build_info(void);
 
 /* Thread-local description of the last failure on this thread ("" if none). */
@@ -188,6 +188,48 @@ int msda_grad_value_dtype(int dtype, int clips, int frames, int window, int spat
  * num_heads and virtual_levels = num_levels (msda_backward) or num_levels * (1 + window)
  * (msda_temporal_backward; batch = clips * frames). */
 long long msda_backward_workspace_bytes(int batch, int num_query, int num_heads, int virtual_levels);
+
+/*
+ * Backward of only the gradients a caller needs (ABI v14).  `grads` is a mask of two groups:
+ *   MSDA_GRAD_VALUE     grad_value;
+ *   MSDA_GRAD_SAMPLING  grad_sampling_loc and grad_attn_weight (one pass computes both; the temporal entry point: all four
+ *                       of grad_loc_curr, grad_aw_curr, grad_loc_temp, grad_aw_temp).
+ * The remaining arguments are those of msda_backward / msda_temporal_backward, which are these calls with grads =
+ * MSDA_GRAD_VALUE | MSDA_GRAD_SAMPLING and launch what they launched before.  grads = 0 returns MSDA_OK and launches
+ * nothing; any other bit is MSDA_ERR_ARG.  The output pointers of a group that is not asked for may be NULL and are never
+ * written (nor is grad_value_dtype checked without MSDA_GRAD_VALUE).
+ *   MSDA_GRAD_SAMPLING alone: the gather pass of the full call made with a workspace of msda_backward_workspace_bytes()
+ *       -- the same kernel with the same settings, whatever workspace this call passes -- without the culling records, and
+ *       no zero-fill or scatter of grad_value.  `workspace` may be NULL and is not written.
+ *   MSDA_GRAD_VALUE alone: `value` is never read.  Where the full call runs a gather pass and a scatter, a culling-records
+ *       kernel (msda_last_route: "culling records") reads only the sampling locations and writes every record the scatter
+ *       reads, byte for byte as the gather pass would, and the zeroed ticket counters; the scatter that follows is the
+ *       full call's.  (The gather pass may also leave records of levels the scatter does not read; this kernel does not.)  The
+ *       one-kernel tile and generic backward routes take variants that only accumulate grad_value ("grad_value only").
+ *       `workspace`, msda_backward_workspace_bytes and msda_grad_value_dtype mean what they mean for the full call.
+ */
+#define MSDA_GRAD_VALUE 1
+#define MSDA_GRAD_SAMPLING 2
+
+int msda_backward_grads(int grads, int dtype, const void *value, const int64_t *spatial_shapes,
+                        const int64_t *level_start_index, const void *sampling_loc,
+                        const void *attn_weight, const void *grad_out,
+                        int batch, int spatial_size, int num_heads, int channels, int num_levels,
+                        int num_query, int num_point,
+                        void *grad_value, int grad_value_dtype, void *grad_sampling_loc, void *grad_attn_weight,
+                        void *workspace, long long workspace_bytes, const int64_t *value_strides,
+                        const int64_t *spatial_shapes_host, void *stream);
+
+int msda_temporal_backward_grads(int grads, int dtype, const void *value, const int64_t *spatial_shapes,
+                                 const int64_t *level_start_index, const int32_t *frame_table,
+                                 const void *loc_curr, const void *aw_curr,
+                                 const void *loc_temp, const void *aw_temp, const void *grad_out,
+                                 int clips, int frames, int window, int spatial_size, int num_heads,
+                                 int channels, int num_levels, int num_query,
+                                 int num_curr_point, int num_temp_point,
+                                 void *grad_value, int grad_value_dtype, void *grad_loc_curr, void *grad_aw_curr,
+                                 void *grad_loc_temp, void *grad_aw_temp, void *workspace, long long workspace_bytes,
+                                 const int64_t *value_strides, const int64_t *spatial_shapes_host, void *stream);
 
 /*
  * Fused temporal forward: for every frame t of every clip, current-frame attention on value[t] PLUS
