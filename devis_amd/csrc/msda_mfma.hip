@@ -83,7 +83,9 @@ msda_bwd_value_mfma_kernel(const Params p, int l0)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     unsigned char *Ahi = lds + wave * (2 * kTile), *Alo = Ahi + kTile;
 
-    // the levels of this launch, from the DEVICE shapes (the host's copy only chose the kernel)
+    // the levels of this launch, from the DEVICE shapes (the host's copy only chose the kernel).  poff is a level's first row in
+    // the LDS tiles; in grad_value each level starts at its own level_start_index (include/msda.h: levels need not be adjacent),
+    // so pixel pix of level li (poff[li] <= pix) is row lsi0 + pix + (lsi[l0 + li] - lsi0 - poff[li]) of the map
     int H[NL], Wd[NL], poff[NL], npix = 0;
 #pragma unroll
     for (int li = 0; li < NL; ++li) {
@@ -91,6 +93,7 @@ msda_bwd_value_mfma_kernel(const Params p, int l0)
         poff[li] = npix; npix += H[li] * Wd[li];
     }
     const int lsi0 = (int)p.lsi[l0];
+    const int skip1 = NL == 2 ? (int)p.lsi[l0 + NL - 1] - lsi0 - poff[NL - 1] : 0;     // rows between the two levels' maps
     const int MD = p.M * D;
     const int clips = p.groups / p.frames;
     const int n_items = clips * p.frames * p.M;
@@ -101,7 +104,10 @@ msda_bwd_value_mfma_kernel(const Params p, int l0)
         for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
             const int m = item % p.M, gf = item / p.M;
             GV *gmap = static_cast<GV *>(p.grad_value) + ((long long)gf * p.S + lsi0) * MD + m * D;
-            for (int i = tid; i < npix * D; i += NW * 64) Store<GV>::put(gmap + (long long)(i / D) * MD + (i % D), __builtin_nanf(""));
+            for (int i = tid; i < npix * D; i += NW * 64) {
+                const int pix = i / D, row = NL == 2 && pix >= poff[NL - 1] ? pix + skip1 : pix;
+                Store<GV>::put(gmap + (long long)row * MD + (i % D), __builtin_nanf(""));
+            }
         }
         return;
     }
@@ -358,7 +364,8 @@ msda_bwd_value_mfma_kernel(const Params p, int l0)
 #pragma unroll
                     for (int w = 0; w < NW; ++w) v += part[w][k];
                     const int r = r0 + i + k, pixs = 32 * t + (r & 3) + 8 * (r >> 2);       // (uniform; the lane's pixel: + 4 kh)
-                    if (pixs + kh4 < npix) Store<GV>::put(gmap + (long long)pixs * MD + lane_off, v);
+                    const int row = NL == 2 && pixs + kh4 >= poff[NL - 1] ? pixs + skip1 : pixs;
+                    if (pixs + kh4 < npix) Store<GV>::put(gmap + (long long)row * MD + lane_off, v);
                 }
                 __builtin_amdgcn_sched_barrier(0);          // (without it every batch's loads are hoisted to the top: 64 registers more)
             }
@@ -376,8 +383,11 @@ int scatter_mfma_launch(const Params &p, int l0, unsigned grid, hipStream_t stre
     constexpr size_t lds = mfma_lds_bytes(MT, NW);
     if (const int rc = grant_lds(reinterpret_cast<const void *>(kern), lds, granted, "the matrix-pipe scatter kernel")) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, stream, p, l0);
-    return check_launch(std::is_same<GV, float>::value ? "msda backward (matrix-pipe scatter kernel, coarse levels)"
-                                                       : "msda backward (matrix-pipe scatter kernel, coarse levels, grad_value in the storage type)");
+    constexpr bool f32 = std::is_same<GV, float>::value;     // (the level count in the route: tests tell NL = 1 from NL = 2 by it)
+    return check_launch(NL == 1 ? (f32 ? "msda backward (matrix-pipe scatter kernel, coarse levels, 1 level)"
+                                       : "msda backward (matrix-pipe scatter kernel, coarse levels, 1 level, grad_value in the storage type)")
+                                : (f32 ? "msda backward (matrix-pipe scatter kernel, coarse levels, 2 levels)"
+                                       : "msda backward (matrix-pipe scatter kernel, coarse levels, 2 levels, grad_value in the storage type)"));
 }
 
 template <typename T, typename TL, typename GV>

@@ -49,8 +49,17 @@
  *     never in DeVIS) is decided from it.  A stale hint that hides such a level does not return silently wrong
  *     sums: the kernel sees the device shapes and fills that level's pixels of grad_value with NaN.
  *
- * Symbols:  N batch, S = sum_l H_l*W_l, M heads, D channels per head, Lq queries, L levels,
- *           P points;  spatial_shapes[l] = (H_l, W_l);  sampling_loc[..., 0] = x (width), 1 = y.
+ * Symbols:  N batch, S pixel rows of `value` per batch entry (frame), M heads, D channels per head, Lq queries,
+ *           L levels, P points;  spatial_shapes[l] = (H_l, W_l);  sampling_loc[..., 0] = x (width), 1 = y.
+ *
+ * Level layout: pixel (y, x) of level l is row level_start_index[l] + y*W_l + x of `value` (the reference's
+ * addressing, ms_deform_im2col_cuda.cuh:268-278).  Level l occupies rows [lsi[l], lsi[l] + H_l*W_l) of [0, S);
+ * S = sum_l H_l*W_l with lsi the cumsum is the usual case, not a requirement:
+ *   - levels may come in any order, with gaps before, between and after them;
+ *   - gap rows (rows of no level) of `value` are never read;
+ *   - gap rows of grad_value are written as 0 by every backward entry point (it need not be zeroed by the caller);
+ *   - overlapping level ranges are NOT supported: the backward overwrites a level's rows rather than adding to them;
+ *   - the temporal entry points: the same layout in every frame (a frame is S rows).
  */
 #ifndef MSDA_H_
 #define MSDA_H_
@@ -108,8 +117,8 @@ const char *msda_last_route(void);
  *                     shapes -- calls made without spatial_shapes_host are never looked up.  Plain calls: clips = N, frames = 1,
  *                     window = 0.
  *   msda_pin_route    settings = "name=value name=value ..." with names fwd_rs, fwd_rs_nt, fwd_win, fwd_tile_waves, bwd_rs,
- *                     bwd_rs_tpw, bwd_rs_fsplit, bwd_win (the MSDA_* knobs of the same names, see Conventions) and
- *                     scatter_order (1 = level order, 2 = image order).  An empty string removes the pin.  A knob SET in
+ *                     bwd_rs_tpw, bwd_rs_fsplit, bwd_win, scatter_mfma (the MSDA_* knobs of the same names, see
+ *                     Conventions) and scatter_order (1 = level order, 2 = image order).  An empty string removes the pin.  A knob SET in
  *                     the environment (MSDA_ENABLE_HOOKS=1) wins over a pin, whatever its value (also its default).
  *   msda_clear_routes removes every pin;  msda_route_count: pins held.
  * devis_amd.tune() measures and pins; devis_amd/routes.json is the table audited on MI355X, loaded with the library.

@@ -46,14 +46,22 @@ def oracle_fwd_bwd(d, dtype=np.float64):
     return out, gv, gl, ga
 
 
+def window_level_starts(lsi, S, W):
+    """Level starts of W frames of S rows each stacked along the pixel axis: frame w's levels sit where they sit in one frame,
+    w * S rows further on (for a compact pyramid: the cumsum of the tiled shapes, as the reference computes them)."""
+    lsi = np.asarray(lsi, dtype=np.int64)
+    return np.concatenate([lsi + w * S for w in range(W)]).astype(np.int64)
+
+
 def temporal_reference(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_out=None):
     """Oracle for the fused temporal op = the reference's call pattern (ms_deform_attn.py:325-364):
     per frame t one call on value[t] and one on the `window` frames ftab[t] stacked along the level
-    axis with spatial_shapes.repeat(window).  numpy float64 in/out.  value [T,S,M,D] (one clip)."""
+    axis with spatial_shapes.repeat(window).  numpy float64 in/out.  value [T,S,M,D] (one clip); the level
+    layout `lsi` need not tile [0, S) (see relayout)."""
     T, S, M, D = value.shape
     W = ftab.shape[1]
     t_shapes = np.tile(shapes, (W, 1))
-    t_lsi = O.level_start_index(t_shapes)
+    t_lsi = window_level_starts(lsi, S, W)
     outs, gv = [], np.zeros_like(value)
     gl_c, ga_c, gl_t, ga_t = (np.zeros_like(x) for x in (loc_c, aw_c, loc_t, aw_t))
     for t in range(T):
@@ -66,7 +74,8 @@ def temporal_reference(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_
             a, b, c = O.backward(value[t][None], shapes, lsi, loc_c[t][None], aw_c[t][None], g)
             gv[t] += a[0]; gl_c[t] = b[0]; ga_c[t] = c[0]
             a, b, c = O.backward(stacked, t_shapes, t_lsi, loc_t[t][None], aw_t[t][None], g)
-            np.add.at(gv, ftab[t], a[0].reshape(W, S, M, D))      # index_put-add, repeats accumulate
+            for w, f in enumerate(ftab[t]):                         # index_put-add, repeats accumulate (np.add.at, unbuffered)
+                gv[f] += a[0, w * S:(w + 1) * S]
             gl_t[t] = b[0]; ga_t[t] = c[0]
     out = np.concatenate(outs, 0)
     if grad_out is None:
@@ -117,3 +126,69 @@ def localise(loc, shapes, sigma_px, seed, levels_per_slot=None):
     wh = np.tile(wh, (LL // L, 1))                                      # [LL, 2]
     noise = rng.standard_normal(loc.shape) * sigma_px / wh[:, None, :]
     return (c[:, None, None, None, :] + noise).astype(loc.dtype)
+
+
+LAYOUTS = ("gaps", "aligned", "tail_gap", "reversed", "shuffled")
+
+
+def relayout(d, kind, seed):
+    """The call of input dict `d` (make_inputs / make_temporal_inputs: a compact pyramid) with `value` moved into a larger pixel
+    axis of S' rows and level_start_index to match (include/msda.h: levels in any order, with gaps).  Rows of no level are
+    NaN -- no kernel may read them -- and `gap` [S'] marks them.  kind:
+      gaps      a gap of 1..70 rows before every level and after the last one (lsi[0] > 0)
+      aligned   every level starts on a multiple of 64 rows
+      tail_gap  one gap, between levels L-2 and L-1, at least as long as level L-1 (one level: before it)
+      reversed  coarse levels first in memory, gaps as for `gaps`
+      shuffled  a random level order, gaps of 0..70 rows"""
+    assert kind in LAYOUTS, kind
+    rng = np.random.default_rng(seed)
+    shapes = np.asarray(d["shapes"], dtype=np.int64)
+    lsi = np.asarray(d["lsi"], dtype=np.int64)
+    hw = shapes[:, 0] * shapes[:, 1]
+    L = len(hw)
+    assert np.array_equal(lsi, O.level_start_index(shapes)), "relayout starts from a compact layout"
+    order = list(range(L))
+    if kind == "reversed":
+        order = order[::-1]
+    elif kind == "shuffled":
+        order = [int(i) for i in rng.permutation(L)]
+        if L > 1 and order == list(range(L)):
+            order = order[1:] + order[:1]
+    gap = np.zeros(L + 1, dtype=np.int64)            # gap[i]: rows before the i-th level in memory; gap[L]: after the last
+    if kind in ("gaps", "reversed"):
+        gap[:] = rng.integers(1, 71, size=L + 1)
+    elif kind == "shuffled":
+        gap[:] = rng.integers(0, 71, size=L + 1)
+    elif kind == "tail_gap":
+        gap[L - 1 if L > 1 else 0] = hw[-1] + rng.integers(1, 71)
+    new_lsi = np.zeros(L, dtype=np.int64)
+    pos = 0
+    for i, l in enumerate(order):
+        pos += int(gap[i])
+        if kind == "aligned":
+            pos = -(-pos // 64) * 64
+        new_lsi[l] = pos
+        pos += int(hw[l])
+    S2 = pos + int(gap[L]) if kind != "aligned" else -(-pos // 64) * 64
+    value = d["value"]
+    out = np.full(value.shape[:1] + (S2,) + value.shape[2:], np.nan, dtype=value.dtype)
+    is_gap = np.ones(S2, dtype=bool)
+    for l in range(L):
+        out[:, new_lsi[l]:new_lsi[l] + hw[l]] = value[:, lsi[l]:lsi[l] + hw[l]]
+        is_gap[new_lsi[l]:new_lsi[l] + hw[l]] = False
+    r = dict(d)
+    r.update(value=out, lsi=new_lsi, gap=is_gap)
+    return r
+
+
+def gaps_zeroed(d):
+    """`d` with the gap rows of `value` set to 0 (the oracle's input: it reads no gap row either, and NaN would hide that)."""
+    r = dict(d)
+    r["value"] = np.where(d["gap"][None, :, None, None], np.zeros((), d["value"].dtype), d["value"])
+    return r
+
+
+def level_rows(x, d):
+    """Rows of a [N, S', ...] array that belong to a level, in level order -- the compact layout's rows."""
+    shapes, lsi = np.asarray(d["shapes"]), np.asarray(d["lsi"])
+    return np.concatenate([x[:, s:s + h * w] for (h, w), s in zip(shapes.tolist(), lsi.tolist())], 1)

@@ -101,3 +101,33 @@ def test_random_route_pins_never_change_results(seed):
         if i in (2, 4):
             continue            # grad_loc in fp32 against the fp64 oracle: cell flips at pixel borders (checked in fp32 elsewhere)
         assert _maxabs(a, b) <= 1e-4 * max(1.0, np.abs(b).max()), (picks, i)
+
+
+@pytest.mark.parametrize("seed", range(100))
+def test_random_layouts_and_route_pins(seed):
+    """include/msda.h: levels in any order, with gaps.  A random level layout (tests/helpers.py relayout: gap rows of `value` NaN)
+    under a random subset of route pins, through the C ABI into a NaN-poisoned grad_value: against the oracle, gap rows of
+    grad_value exactly 0."""
+    from devis_amd import _native
+    from helpers import LAYOUTS, relayout
+    from test_layout_gpu import _rounded, check, run_temporal, temporal_reference_clips
+    rng = np.random.default_rng(4000 + seed)
+    T = int(rng.integers(2, 5))
+    W, M, Lq = T - 1, int(rng.choice([3, 8])), int(rng.integers(16, 70))
+    pyr = [[(12, 20), (6, 10)], [(23, 40), (12, 20), (6, 10)], [(9, 7), (5, 4), (3, 2)], [(16, 16), (8, 8), (4, 4), (2, 2)]][seed % 4]
+    kind = LAYOUTS[int(rng.integers(len(LAYOUTS)))]
+    Pt = int(rng.integers(1, 5))
+    d = make_temporal_inputs(seed, T, W, M, 32, Lq, pyr, 4, Pt, dtype=np.float64)
+    r = _rounded(relayout(d, kind, seed), torch.float32)
+    S = r["value"].shape[1]
+    picks = {k: int(rng.choice(v)) for k, v in PIN_CHOICES.items() if rng.random() < 0.5}
+    _native.load()
+    keys = [_native.route_key(b, 0, 1, T, W, S, M, 32, len(pyr), Lq, 4, Pt, pyr) for b in (False, True)]
+    for k in keys:
+        _native.pin_route(k, picks)
+    try:
+        got, routes = run_temporal(r, torch.float32)
+    finally:
+        for k in keys:
+            _native.pin_route(k, "")
+    check(got, temporal_reference_clips(r, torch.float32)[0], r, torch.float32)
