@@ -10,6 +10,7 @@ A query row = one (frame, query) producing C=256 outputs; M-queries/s = clips*T*
     python bench.py                       # 1 GPU, default K/W, prints ONE JSON line
     python bench.py --dump-outputs DIR    # ... and writes what the last timed step computed to DIR/*.npy (seeded
                                           # inputs: two builds compare output for output)
+    python bench.py --full                # ... and then everything else it measures (below), in the same line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...          # no launcher: bench.py starts that very torchrun as a child (launch_ranks),
@@ -18,13 +19,17 @@ A query row = one (frame, query) producing C=256 outputs; M-queries/s = clips*T*
 Multi-GPU (`--gpus N`): clip-parallel -- every rank runs the same per-GPU batch of clips (weak
 scaling), no collective on the data path; timing = barrier + synchronize on both sides, max over ranks.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line: `roofline` and
+`cpu_baseline` are null there.  `--full` measures the rest after the timed steps and adds it to the same line:
   roofline     -- for the dominant kernel (the longer of the fused forward / backward kernels):
                   algorithmic bytes per launch / its average launch duration measured
-                  here with HIP events on the launch stream, against the 8 TB/s HBM peak;
+                  here with HIP events on the launch stream, against the 8 TB/s HBM peak; beside it
+                  `kernels`, `scatter_pass` and `routes`;
   cpu_baseline -- the reference's pure-PyTorch CPU path (oracle/ restatement of
                   ms_deform_attn_core_pytorch, fwd+bwd through autograd, reference call pattern)
-                  timed on this box's host cores on a bounded sample (rank 0, N=1 only).
+                  timed on this box's host cores on a bounded sample (rank 0, N=1 only);
+  padded_value_layout, other_configs -- the padded `value` rows the modules hand the op, and the
+                  other BASELINE configurations, precisions and call sizes (N=1 for the latter).
 """
 import argparse
 import json
@@ -82,9 +87,12 @@ def parse_args():
     ap.add_argument("--value-layout", choices=["dense", "padded"], default="dense",
                     help="dense = the reference's [N,S,M,D]; padded = one spare head slot per pixel row, what "
                          "devis_amd's modules feed the op (functions.project_value; DESIGN.md section 5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the extra keys for the other BASELINE configs")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the per-kernel times and roofline, the padded value layout, the CPU "
+                         "baseline and the other configurations (a plain run prints the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without the extra keys for the other BASELINE configs")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: host time of the CPU baseline's sample")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="torch.distributed backend of an N > 1 run (nccl = RCCL; gloo only for --share-device test runs)")
     ap.add_argument("--share-device", action="store_true",
@@ -772,7 +780,7 @@ def main():
     # ---- the same K steps on the layout devis_amd's own modules hand the op (value_proj writes one spare
     # head slot per pixel row, functions.project_value): reported beside the headline, never as `value`
     padded_line = None
-    if args.value_layout == "dense" and args.pattern == "fused" and args.mode == "clip-parallel":
+    if args.full and args.value_layout == "dense" and args.pattern == "fused" and args.mode == "clip-parallel":
         # INTERLEAVED blocks (A-B-A-B, medians) so that clock / thermal drift inside the run cannot favour either layout:
         # dense = what `value` above reports (the reference's tensor), padded = what devis_amd's value_proj writes
         dense_value = b["value"]
@@ -814,7 +822,7 @@ def main():
 
     # ---- per-kernel durations with HIP events on the launch stream (fused pattern only) ----------
     roofline, extra = None, {}
-    if rank == 0 and args.pattern == "fused" and args.mode == "clip-parallel":
+    if args.full and rank == 0 and args.pattern == "fused" and args.mode == "clip-parallel":
         from devis_amd import _native
         stream = torch.cuda.current_stream()
         out = torch.empty((args.clips * T, q, M * D), dtype=dtype, device=device)
@@ -956,7 +964,7 @@ def main():
 
     # ---- CPU baseline: the reference's pure-PyTorch path on the host cores (bounded sample) -----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import msda_oracle as O
         # grid_sample's backward degrades badly when oversubscribed (256 threads: >300 s per clip);
         # 16 threads is near its best on this host -- `cores` reports what was actually used
@@ -1014,7 +1022,7 @@ def main():
         dist.all_reduce(ones, op=dist.ReduceOp.SUM)
         ranks_seen = int(ones.item())
     others = None
-    if rank == 0 and world == 1 and not args.no_other_configs and args.mode == "clip-parallel":
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs and args.mode == "clip-parallel":
         del b, leaves
         torch.cuda.empty_cache()
         others = other_configs(args, device)
@@ -1038,7 +1046,7 @@ def main():
             "roofline": roofline, "cpu_baseline": cpu, "ranks_seen": ranks_seen,
             **({"test_run": "--share-device: all %d ranks on ONE GPU over gloo -- the N-rank protocol only, not a scaling figure" % world}
                if args.share_device else {}),
-            "prewarm_seconds": args.prewarm_seconds,
+            "prewarm_seconds": args.prewarm_seconds, "full": args.full,
         }
         line.update(extra)
         if others is not None:

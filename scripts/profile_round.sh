@@ -9,9 +9,9 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$1
 mkdir -p "$O"
 cd "$R"
-timeout -k 10 900 python3 bench.py > "$O/bench.json" 2> "$O/bench.err" || { rc=$?; echo "bench.py failed with exit status $rc"; tail -5 "$O/bench.err"; exit $rc; }
+timeout -k 10 900 python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { rc=$?; echo "bench.py failed with exit status $rc"; tail -5 "$O/bench.err"; exit $rc; }
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -- python3 "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-other-configs > "$O/kt.log" 2>&1 \
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -- python3 "$R/bench.py" --steps 10 --warmup 3 --full --no-cpu-baseline --no-other-configs > "$O/kt.log" 2>&1 \
   || { rc=$?; echo "kernel trace failed with exit status $rc"; tail -5 "$O/kt.log"; exit $rc; }
 f=$(find "$O/kt" -name '*kernel_stats.csv' | head -1)
 [ -n "$f" ] && cp "$f" "$O/kernel_stats.csv"
