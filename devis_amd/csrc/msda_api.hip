@@ -46,7 +46,7 @@ size_t tile_lds_bytes(int rpw, int nvl, bool bwd, bool intervals = false)
 // All of them are environment variables that are read ONCE (first call into the library, or msda_reload_knobs())
 // and only when MSDA_ENABLE_HOOKS=1: a production process cannot have its results or speed changed by a stray
 // variable, and the launch path does not call getenv.  tests/ and bench.py set MSDA_ENABLE_HOOKS=1 and call
-// msda_reload_knobs() after changing a knob.
+// msda_reload_knobs() after changing a knob.  Each knob is one row of kKnobs below.
 struct Knobs {
     int fwd_rs = -1, fwd_rs_nt = 0;     // resident-slab forward: -1 auto, 0 off, 1 force; tiles per wave (0 = auto)
     int bwd_rs = -1, bwd_rs_tpw = 0;    // resident-slab gather pass: -1 auto, 0 off, 1 force; tiles per wave (0 = auto)
@@ -59,88 +59,102 @@ struct Knobs {
     int bwd_phases = 3;                 // 1 = gather pass only, 2 = scatter pass only, 3 = both
     int bwd_cull = 1;                   // 0: no culling structure, 2: (min, max) intervals instead of per-point records
     int bwd_all_records = 0;            // measurement: the gather pass leaves records for every level (a later scatter-only call may walk them)
-    int scatter_lds_kb = 144, scatter_dbg = 0;
+    int scatter_lds_kb = 144;
+    int scatter_dbg = 0;                // MSDA_SCATTER_DBG without bits 256 / 2048: measurement bits the scatter kernels read
+    int scatter_order = 0;              // owner-computes scatter's item order: 0 = rule, 1 = level order (MSDA_SCATTER_DBG bit 256),
+                                        // 2 = image order wherever the bands can be sorted (bit 2048)
     int scatter_own = -1;               // owner-computes scatter: -1 auto, 0 off (the LDS-atomic scatter instead)
     int scatter_mfma = -1;              // matrix-pipe scatter of the coarse levels (msda_mfma.hip): -1 auto, 0 off, 1 wherever it applies
     int scatter_part = 0;               // measurement: 1 = only the owner-computes kernel of a scatter that runs both, 2 = only the matrix-pipe kernel
     int force_generic = 0;
     int det_route = 0;                  // MSDA_GRAD_DETERMINISTIC grad_value: 0 auto, 1 = route (a) (any shape), 2 = route (b) (LDS bands)
     int dbg = 0;
-    unsigned forced = 0;                // route knobs that were SET in the environment (kForce* bits), whatever their value: a knob
+    unsigned forced = 0;                // bit i: the variable of kKnobs[i] was SET in the environment, whatever its value: a knob
                                         // forced to its default (MSDA_FWD_RS=-1 for a rules-only A/B run) still wins over a pin
 };
-enum : unsigned { kForceFwdRs = 1, kForceFwdRsNt = 2, kForceFwdWin = 4, kForceFwdTileWaves = 8, kForceBwdRs = 16, kForceBwdRsTpw = 32,
-                  kForceBwdRsFsplit = 64, kForceBwdWin = 128, kForceScatterDbg = 256, kForceScatterMfma = 512 };
+
+// How a variable's text becomes the knob's value.
+enum class Parse { Int, IsOne, IsAtomic, DbgBits, OrderBits };
+struct KnobDef {
+    const char *env;                    // environment variable
+    const char *pin;                    // name in msda_pin_route settings, or null: not pinnable
+    int Knobs::*field;
+    Parse parse;
+};
+const KnobDef kKnobs[] = {
+    {"MSDA_FWD_RS", "fwd_rs", &Knobs::fwd_rs, Parse::Int},
+    {"MSDA_FWD_RS_NT", "fwd_rs_nt", &Knobs::fwd_rs_nt, Parse::Int},
+    {"MSDA_FWD_WIN", "fwd_win", &Knobs::fwd_win, Parse::Int},
+    {"MSDA_FWD_TILE_WAVES", "fwd_tile_waves", &Knobs::fwd_tile_waves, Parse::Int},
+    {"MSDA_BWD_RS", "bwd_rs", &Knobs::bwd_rs, Parse::Int},
+    {"MSDA_BWD_RS_TPW", "bwd_rs_tpw", &Knobs::bwd_rs_tpw, Parse::Int},
+    {"MSDA_BWD_RS_FSPLIT", "bwd_rs_fsplit", &Knobs::bwd_rs_fsplit, Parse::Int},
+    {"MSDA_BWD_WIN", "bwd_win", &Knobs::bwd_win, Parse::Int},
+    {"MSDA_SCATTER_DBG", "scatter_order", &Knobs::scatter_order, Parse::OrderBits},
+    {"MSDA_SCATTER_MFMA", "scatter_mfma", &Knobs::scatter_mfma, Parse::Int},
+    {"MSDA_WIN_MIN_HALO", nullptr, &Knobs::win_min_halo, Parse::Int},
+    {"MSDA_BWD_MODE", nullptr, &Knobs::bwd_atomic, Parse::IsAtomic},
+    {"MSDA_BWD_PHASES", nullptr, &Knobs::bwd_phases, Parse::Int},
+    {"MSDA_BWD_CULL", nullptr, &Knobs::bwd_cull, Parse::Int},
+    {"MSDA_BWD_ALL_RECORDS", nullptr, &Knobs::bwd_all_records, Parse::Int},
+    {"MSDA_SCATTER_LDS_KB", nullptr, &Knobs::scatter_lds_kb, Parse::Int},
+    {"MSDA_SCATTER_DBG", nullptr, &Knobs::scatter_dbg, Parse::DbgBits},
+    {"MSDA_SCATTER_OWN", nullptr, &Knobs::scatter_own, Parse::Int},
+    {"MSDA_SCATTER_PART", nullptr, &Knobs::scatter_part, Parse::Int},
+    {"MSDA_FORCE_GENERIC", nullptr, &Knobs::force_generic, Parse::IsOne},
+    {"MSDA_DET_ROUTE", nullptr, &Knobs::det_route, Parse::Int},
+    {"MSDA_DBG", nullptr, &Knobs::dbg, Parse::Int},
+};
+constexpr int kNumKnobs = sizeof(kKnobs) / sizeof(kKnobs[0]);
+static_assert(kNumKnobs <= 32, "Knobs::forced has one bit per knob");
 Knobs g_knobs;
 int g_knobs_loaded = 0;
 
-int env_int(const char *name, int dflt)
+int knob_value(Parse parse, const char *text)
 {
-    const char *e = getenv(name);
-    return (e && e[0]) ? atoi(e) : dflt;
-}
-
-bool env_set(const char *name)
-{
-    const char *e = getenv(name);
-    return e && e[0];
+    const int v = atoi(text);
+    switch (parse) {
+        case Parse::IsOne: return v == 1;
+        case Parse::IsAtomic: return strcmp(text, "atomic") == 0;
+        case Parse::DbgBits: return v & ~(256 | 2048);
+        case Parse::OrderBits: return (v & 256) ? 1 : (v & 2048) ? 2 : 0;
+        default: return v;
+    }
 }
 
 void load_knobs()
 {
     Knobs k;
-    if (env_int("MSDA_ENABLE_HOOKS", 0) == 1) {
-        k.forced = (env_set("MSDA_FWD_RS") ? kForceFwdRs : 0u) | (env_set("MSDA_FWD_RS_NT") ? kForceFwdRsNt : 0u) |
-                   (env_set("MSDA_FWD_WIN") ? kForceFwdWin : 0u) | (env_set("MSDA_FWD_TILE_WAVES") ? kForceFwdTileWaves : 0u) |
-                   (env_set("MSDA_BWD_RS") ? kForceBwdRs : 0u) | (env_set("MSDA_BWD_RS_TPW") ? kForceBwdRsTpw : 0u) |
-                   (env_set("MSDA_BWD_RS_FSPLIT") ? kForceBwdRsFsplit : 0u) | (env_set("MSDA_BWD_WIN") ? kForceBwdWin : 0u) |
-                   (env_set("MSDA_SCATTER_DBG") ? kForceScatterDbg : 0u) | (env_set("MSDA_SCATTER_MFMA") ? kForceScatterMfma : 0u);
-        k.fwd_rs = env_int("MSDA_FWD_RS", k.fwd_rs); k.fwd_rs_nt = env_int("MSDA_FWD_RS_NT", k.fwd_rs_nt);
-        k.bwd_rs = env_int("MSDA_BWD_RS", k.bwd_rs); k.bwd_rs_tpw = env_int("MSDA_BWD_RS_TPW", k.bwd_rs_tpw);
-        k.bwd_rs_fsplit = env_int("MSDA_BWD_RS_FSPLIT", k.bwd_rs_fsplit);
-        k.fwd_tile_waves = env_int("MSDA_FWD_TILE_WAVES", k.fwd_tile_waves);
-        k.fwd_win = env_int("MSDA_FWD_WIN", k.fwd_win); k.bwd_win = env_int("MSDA_BWD_WIN", k.bwd_win);
-        k.win_min_halo = env_int("MSDA_WIN_MIN_HALO", k.win_min_halo);
-        const char *mode = getenv("MSDA_BWD_MODE");
-        k.bwd_atomic = (mode && !strcmp(mode, "atomic")) ? 1 : 0;
-        k.bwd_phases = env_int("MSDA_BWD_PHASES", k.bwd_phases);
-        k.bwd_cull = env_int("MSDA_BWD_CULL", k.bwd_cull);
-        k.bwd_all_records = env_int("MSDA_BWD_ALL_RECORDS", k.bwd_all_records);
-        k.scatter_lds_kb = env_int("MSDA_SCATTER_LDS_KB", k.scatter_lds_kb);
-        k.scatter_dbg = env_int("MSDA_SCATTER_DBG", k.scatter_dbg);
-        k.scatter_own = env_int("MSDA_SCATTER_OWN", k.scatter_own);
-        k.scatter_mfma = env_int("MSDA_SCATTER_MFMA", k.scatter_mfma);
-        k.scatter_part = env_int("MSDA_SCATTER_PART", k.scatter_part);
-        k.force_generic = env_int("MSDA_FORCE_GENERIC", 0) == 1;
-        k.det_route = env_int("MSDA_DET_ROUTE", 0);
-        k.dbg = env_int("MSDA_DBG", 0);
-    }
+    const char *hooks = getenv("MSDA_ENABLE_HOOKS");
+    if (hooks && atoi(hooks) == 1)
+        for (int i = 0; i < kNumKnobs; ++i) {
+            const char *e = getenv(kKnobs[i].env);
+            if (!e || !e[0]) continue;
+            k.*kKnobs[i].field = knob_value(kKnobs[i].parse, e);
+            k.forced |= 1u << i;
+        }
     g_knobs = k;
     __atomic_store_n(&g_knobs_loaded, 1, __ATOMIC_RELEASE);
 }
 
-// While a call runs with a pinned route (msda_pin_route), this thread's knobs() answers the pinned settings laid over the
-// environment's: see RouteScope below.
-thread_local const Knobs *tl_route_knobs = nullptr;
-
-inline const Knobs &knobs()
+// The knobs of the environment, without any pin.
+const Knobs &env_knobs()
 {
-    if (tl_route_knobs) return *tl_route_knobs;
     if (!__atomic_load_n(&g_knobs_loaded, __ATOMIC_ACQUIRE)) load_knobs();      // benign race: every thread reads the same environment
     return g_knobs;
 }
 
 // ---- measured route table (ABI v12) ---------------------------------------------------------------------------------
-// The rules in launch_fast choose a kernel family, tiles per wave, the gather pass's grid and the scatter's item order from
-// sizes alone; they were calibrated on three pyramids and a few batch sizes and are the FALLBACK.  A
+// The rules of the plan_* functions choose a kernel family, tiles per wave, the gather pass's grid and the scatter's item order
+// from sizes alone; they were calibrated on three pyramids and a few batch sizes and are the FALLBACK.  A
 // caller that has TIMED the alternatives for a call shape (devis_amd.tune, or the audited table shipped as
 // devis_amd/routes.json) pins the winner here: key = everything the rules look at (direction, dtype code, clips, frames,
 // window, S, M, D, L, Lq, points, the host copy of the shapes), settings = the route knobs.  A knob forced through the
 // environment (tests, A/B runs) wins over a pin.  Results never depend on a pin: every route computes the same function.
+constexpr int kNotPinned = -2;
 struct RoutePin {
     std::string key;
-    int fwd_rs = -2, fwd_rs_nt = -2, fwd_win = -2, fwd_tile_waves = -2;        // -2 = not pinned
-    int bwd_rs = -2, bwd_rs_tpw = -2, bwd_rs_fsplit = -2, bwd_win = -2, scatter_order = -2, scatter_mfma = -2;
+    int value[kNumKnobs];               // per row of kKnobs: the pinned value, or kNotPinned
 };
 std::mutex g_routes_mutex;
 std::vector<RoutePin> g_routes;
@@ -158,6 +172,7 @@ int route_key(char *buf, int len, bool bwd, int dtype, const Params &p)
 
 bool parse_route_settings(const char *text, RoutePin &pin)
 {
+    std::fill(pin.value, pin.value + kNumKnobs, kNotPinned);
     std::string t(text ? text : "");
     size_t i = 0;
     while (i < t.size()) {
@@ -168,52 +183,31 @@ bool parse_route_settings(const char *text, RoutePin &pin)
         size_t end = t.find_first_of(" ,", eq);
         if (end == std::string::npos) end = t.size();
         const std::string name = t.substr(i, eq - i);
-        const int v = atoi(t.substr(eq + 1, end - eq - 1).c_str());
-        if (name == "fwd_rs") pin.fwd_rs = v; else if (name == "fwd_rs_nt") pin.fwd_rs_nt = v;
-        else if (name == "fwd_win") pin.fwd_win = v; else if (name == "fwd_tile_waves") pin.fwd_tile_waves = v;
-        else if (name == "bwd_rs") pin.bwd_rs = v; else if (name == "bwd_rs_tpw") pin.bwd_rs_tpw = v;
-        else if (name == "bwd_rs_fsplit") pin.bwd_rs_fsplit = v; else if (name == "bwd_win") pin.bwd_win = v;
-        else if (name == "scatter_order") pin.scatter_order = v; else if (name == "scatter_mfma") pin.scatter_mfma = v;
-        else return false;
+        int row = 0;
+        while (row < kNumKnobs && !(kKnobs[row].pin && name == kKnobs[row].pin)) ++row;
+        if (row == kNumKnobs) return false;
+        pin.value[row] = atoi(t.substr(eq + 1, end - eq - 1).c_str());
         i = end;
     }
     return true;
 }
 
-// For the duration of one entry-point call: the pinned settings of this call's shape (if any) laid over the knobs.
-struct RouteScope {
-    Knobs merged;
-    bool active = false;
-    RouteScope(bool bwd, int dtype, const Params &p)
-    {
-        if (__atomic_load_n(&g_routes_n, __ATOMIC_ACQUIRE) == 0 || tl_route_knobs) return;
-        char key[512];
-        if (route_key(key, (int)sizeof key, bwd, dtype, p) < 0) return;
-        RoutePin pin;
-        {
-            std::lock_guard<std::mutex> lock(g_routes_mutex);
-            bool found = false;
-            for (const RoutePin &r : g_routes)
-                if (r.key == key) { pin = r; found = true; break; }
-            if (!found) return;
-        }
-        merged = knobs();
-        const unsigned forced = merged.forced;
-        auto lay = [forced](int &dst, unsigned bit, int pinned) { if (pinned != -2 && !(forced & bit)) dst = pinned; };
-        lay(merged.fwd_rs, kForceFwdRs, pin.fwd_rs); lay(merged.fwd_rs_nt, kForceFwdRsNt, pin.fwd_rs_nt);
-        lay(merged.fwd_win, kForceFwdWin, pin.fwd_win); lay(merged.fwd_tile_waves, kForceFwdTileWaves, pin.fwd_tile_waves);
-        lay(merged.bwd_rs, kForceBwdRs, pin.bwd_rs); lay(merged.bwd_rs_tpw, kForceBwdRsTpw, pin.bwd_rs_tpw);
-        lay(merged.bwd_rs_fsplit, kForceBwdRsFsplit, pin.bwd_rs_fsplit); lay(merged.bwd_win, kForceBwdWin, pin.bwd_win);
-        lay(merged.scatter_mfma, kForceScatterMfma, pin.scatter_mfma);
-        if (pin.scatter_order == 1 && !(forced & kForceScatterDbg)) merged.scatter_dbg |= 256;
-        if (pin.scatter_order == 2 && !(forced & kForceScatterDbg)) merged.scatter_dbg |= 2048;
-        tl_route_knobs = &merged;
-        active = true;
+// The knobs of one entry-point call: the pinned settings of its shape (if any) laid over the environment's.
+Knobs call_knobs(bool bwd, int dtype, const Params &p)
+{
+    Knobs k = env_knobs();
+    if (__atomic_load_n(&g_routes_n, __ATOMIC_ACQUIRE) == 0) return k;
+    char key[512];
+    if (route_key(key, (int)sizeof key, bwd, dtype, p) < 0) return k;
+    std::lock_guard<std::mutex> lock(g_routes_mutex);
+    for (const RoutePin &r : g_routes) {
+        if (r.key != key) continue;
+        for (int i = 0; i < kNumKnobs; ++i)
+            if (r.value[i] != kNotPinned && !(k.forced & (1u << i))) k.*kKnobs[i].field = r.value[i];
+        break;
     }
-    ~RouteScope() { if (active) tl_route_knobs = nullptr; }
-    RouteScope(const RouteScope &) = delete;
-    RouteScope &operator=(const RouteScope &) = delete;
-};
+    return k;
+}
 
 int current_device()
 {
@@ -329,9 +323,9 @@ bool standard_value_layout(const Params &p)
 
 // Can grad_value go through a scatter kernel (owner-computes or LDS atomics)?  MSDA_BWD_MODE=atomic forces the
 // one-kernel backward with global atomics (kept for A/B measurements and as the any-shape path).
-bool scatter_applicable(const Params &p)
+bool scatter_applicable(const Params &p, const Knobs &k)
 {
-    if (knobs().bwd_atomic) return false;
+    if (k.bwd_atomic) return false;
     if (p.L > kScatterMaxLevels || (p.D % 4) != 0 || p.D / 4 > kWave || ((p.D / 4) & (p.D / 4 - 1)) != 0) return false;   // D / 4 lanes per hit
     if (1 + p.frames * p.window > kScatterMaxSources || p.Lq >= (1 << 24)) return false;   // survivor-list entry fields
     if (p.window == 0 && p.LA != p.L) return false;
@@ -341,11 +335,11 @@ bool scatter_applicable(const Params &p)
 
 // The owner-computes scatter (msda_bwd_value_grp_kernel) takes D = 32 with <= 4 points per level and the per-point
 // culling records (or no records at all).
-bool owner_scatter_applicable(const Params &p, int esz)
+bool owner_scatter_applicable(const Params &p, int esz, const Knobs &k)
 {
     // (work items -- (clip, frame, head, band) with at most one band per pixel row -- are counted in 32 bits)
-    return p.D == 32 && (esz == 4 || esz == 2) && p.PA <= 4 && p.PB <= 4 && p.Lq < (1 << 22) && knobs().scatter_own != 0 &&
-           knobs().scatter_lds_kb == 144 && (int64_t)p.groups * p.M * ((int64_t)p.S + p.L) < 0x7fffffffLL && scatter_applicable(p);
+    return p.D == 32 && (esz == 4 || esz == 2) && p.PA <= 4 && p.PB <= 4 && p.Lq < (1 << 22) && k.scatter_own != 0 &&
+           k.scatter_lds_kb == 144 && (int64_t)p.groups * p.M * ((int64_t)p.S + p.L) < 0x7fffffffLL && scatter_applicable(p, k);
 }
 
 // The resident-slab kernels take D = 32 in 2- / 4-byte types when the index arithmetic fits and at least the last
@@ -364,8 +358,8 @@ bool rs_fits(const Params &p, int esz)
 // Plan of the resident-window kernels (msda_win.hip; WinPlan in msda_common.h) for an encoder-shaped call: the largest tile
 // whose rows fit a workgroup (frames * ceil(queries / 16) wave tiles <= 3 per wave), then the widest halo whose windows fit
 // the LDS -- all levels at once when that halo reaches 6 pixels, else level 0 and the other levels in two staging phases.
-// `force`: the test knob; without it the call must LOOK like an encoder (one query per pixel).
-bool win_plan(const Params &p, int esz, bool force, WinPlan &w)
+// `force`: the test knob; without it the call must LOOK like an encoder (one query per pixel).  `min_halo`: MSDA_WIN_MIN_HALO.
+bool win_plan(const Params &p, int esz, bool force, int min_halo, WinPlan &w)
 {
     if (!rs_fits(p, esz) || !p.shapes_host || p.L > kWinMaxLevels || p.L < 1) return false;
     long long pixels = 0;
@@ -412,7 +406,6 @@ bool win_plan(const Params &p, int esz, bool force, WinPlan &w)
             return h;
         };
         int split = 0, h0 = widest(0, p.L), h1 = h0;
-        const int min_halo = knobs().win_min_halo;
         if (h0 < min_halo && p.L > 1) {
             int best = h0;
             for (int sp = 1; sp < p.L; ++sp) {
@@ -445,7 +438,7 @@ bool win_plan(const Params &p, int esz, bool force, WinPlan &w)
 }
 
 // win_plan searches tile sizes and halos (~10^5 integer operations): the last plan is kept, keyed by everything it depends on.
-bool win_plan_cached(const Params &p, int esz, bool force, WinPlan &w)
+bool win_plan_cached(const Params &p, int esz, bool force, int min_halo, WinPlan &w)
 {
     struct Key { int L, frames, esz, Lq, min_halo; int64_t shapes[2 * kWinMaxLevels]; };
     static thread_local Key last_key;
@@ -454,11 +447,11 @@ bool win_plan_cached(const Params &p, int esz, bool force, WinPlan &w)
     if (!p.shapes_host || p.L < 1 || p.L > kWinMaxLevels || !rs_fits(p, esz)) return false;
     Key k;
     memset(&k, 0, sizeof k);
-    k.L = p.L; k.frames = p.frames; k.esz = esz; k.Lq = p.Lq; k.min_halo = knobs().win_min_halo;
+    k.L = p.L; k.frames = p.frames; k.esz = esz; k.Lq = p.Lq; k.min_halo = min_halo;
     for (int i = 0; i < 2 * p.L; ++i) k.shapes[i] = p.shapes_host[i];
     if (last_state < 0 || memcmp(&k, &last_key, sizeof k) != 0) {
         // (the remaining inputs of win_plan -- D, M, strides, window -- only gate it through rs_fits, checked above)
-        last_state = win_plan(p, esz, force, last_plan) ? 1 : 0;
+        last_state = win_plan(p, esz, force, min_halo, last_plan) ? 1 : 0;
         last_key = k;
     }
     if (last_state != 1) return false;
@@ -470,11 +463,12 @@ bool win_plan_cached(const Params &p, int esz, bool force, WinPlan &w)
 // scatter will produce it: that kernel overwrites every pixel exactly once from fp32 registers.  Every other route
 // accumulates into grad_value (LDS-atomic flush aside, float atomics) and needs the arithmetic type.  Levels wider than a
 // band take that kernel's float-atomic branch, so the host copy of the shapes must be there and say they do not occur.
-bool storage_typed_grad_value_ok(int dtype, const Params &p)
+// Its callers pass the unpinned knobs: no pinnable knob changes the answer.
+bool storage_typed_grad_value_ok(int dtype, const Params &p, const Knobs &k)
 {
     if (storage_dtype(dtype) != MSDA_BF16 && storage_dtype(dtype) != MSDA_F16) return false;
-    if (knobs().force_generic || knobs().bwd_cull == 2) return false;
-    if (!owner_scatter_applicable(p, 2) || !p.shapes_host) return false;
+    if (k.force_generic || k.bwd_cull == 2) return false;
+    if (!owner_scatter_applicable(p, 2, k) || !p.shapes_host) return false;
     for (int l = 0; l < p.L; ++l)
         if (p.shapes_host[2 * l + 1] > kOwnPix || p.shapes_host[2 * l + 1] <= 0) return false;
     // the shape conditions of fast_path_takes (pointer alignment is checked at the call: a mismatch is an error there)
@@ -483,273 +477,384 @@ bool storage_typed_grad_value_ok(int dtype, const Params &p)
     return true;
 }
 
-// Launches the forward, or the backward's gather pass + scatter, on the tile / resident-slab / scatter kernels.  `grads`
-// (backward): the gradient groups asked for (msda_backward_grads) -- without kGradValue the gather pass runs as in the full
-// call but leaves no culling records and nothing follows it; without kGradSampling the culling-records kernel stands in for
-// the gather pass in front of the full call's scatter.
-int launch_fast(int dtype, const Params &p, bool bwd, hipStream_t stream, int grads)
+int zero_grad_value(int grad_value_dtype, void *grad_value, int groups, int S, int M, int D, void *stream)
 {
-    const int esz = elem_bytes(dtype), VEC = 16 / esz, G = p.D / VEC, RPW = kWave / G;
-    const int64_t tiles = (int64_t)p.groups * ((p.Lq + RPW - 1) / RPW);
-    const int64_t blocks = tiles * p.M;
-    if (blocks > 0x7fffffffLL) return fail(MSDA_ERR_ARG, "msda: problem too large for one launch%s");
-    const size_t lds = tile_lds_bytes(RPW, p.LA + p.LB, bwd, bwd && p.bbox != nullptr);
-    const int rs_tiles_per_clip = p.frames * ((p.Lq + kRsRows - 1) / kRsRows);
-    const int64_t clips = p.groups / p.frames;
-    const int rs_row = 32 * esz;                                  // bytes of one pixel of one head
-    const bool rs_ok = rs_fits(p, esz);
-    const int l0_host = rs_ok ? host_first_slab_level(p, (kRsSlabBytes - kRsSlack) / rs_row) : p.L;
-    const long long l2_budget = esz == 4 ? (2ll << 20) : (4ll << 20);        // see rs_tiles_per_wave
+    if (grad_value_dtype < MSDA_F32 || grad_value_dtype > MSDA_F16) return fail(MSDA_ERR_DTYPE, "msda: unknown dtype code%s");
+    if (!grad_value) return fail(MSDA_ERR_ARG, "msda backward: null grad_value%s");
+    const size_t bytes = (size_t)groups * S * M * D * (size_t)elem_bytes(grad_value_dtype);
+    if (hipMemsetAsync(grad_value, 0, bytes, static_cast<hipStream_t>(stream)) != hipSuccess)
+        return fail(MSDA_ERR_HIP, "msda backward: hipMemsetAsync(grad_value) failed%s");
+    return MSDA_OK;
+}
 
-    // Encoder-shaped calls (one query per pixel) take the resident-window kernels when the slab of the resident-slab kernels
-    // would hold the last level at most (fp32 at 800x1333: 273 of 22223 pixels) -- measured forward 2.38 -> 1.07 ms, gather pass 2.85 -> 1.60 ms there; where
-    // more levels fit the slab (16-bit types, the 360x640 pyramid) the two families are on a par and the slab kernels stay.
-    auto window_route = [&](int mode, WinPlan &w) {
-        // (round 4 audit: also when a 4-byte slab holds only the last TWO levels -- SwinL 480x768 in fp32: forward 0.49 -> 0.37 ms,
-        // gather pass 0.66 -> 0.55; 2-byte slabs of that kind -- 800x1333 bf16 -- are on a par and stay)
-        // (temporal calls only: single-frame encoder calls on that pyramid are 6-26 % faster on the slab kernels)
-        const bool few_levels = l0_host >= p.L - 1 || (esz == 4 && p.frames > 1 && p.L > 2 && l0_host >= p.L - 2);
-        if (mode == 0 || (mode != 1 && !(p.Lq == p.S && p.L > 1 && few_levels))) return false;     // (cheap tests first)
-        return win_plan_cached(p, esz, mode == 1, w);
-    };
-    if (!bwd) {
-        WinPlan w;
-        if (window_route(knobs().fwd_win, w)) return launch_fwd_win(dtype, p, w, stream);
-        if (rs_ok) {
-            // resident-slab forward: up to NT * 16 tiles of 16 rows per workgroup, so that the per-frame slab staging is
-            // amortised; tiles per wave (NT) and workgroups per (clip, head) (parts): see rs_tiles_per_wave
-            const int mode = knobs().fwd_rs;                               // -1 auto, 0 off, 1 force
-            // at most 2 tiles per wave for slabs that start at level 2 (large pyramids) and for fp32: the 4-tile instantiations of
-            // those slot bodies spill 10-40 VGPRs (profiles/r04_resource_usage.txt); BASELINE configs[1] forward 0.306 -> 0.290 ms,
-            // SwinL 0.088 -> 0.082, 2-clip fp32 encoder call 0.52 -> 0.46
-            const int max_nt = (l0_host >= 2 || esz == 4) ? 2 : 4;
-            int nt = rs_tiles_per_wave(p, rs_tiles_per_clip, host_pixels_below(p, l0_host) * rs_row, mode == 1, l2_budget, max_nt);
-            // the slab must hold at least the last level.  (Since the whole-row loads / stores of the points and gradients
-            // the kernel wins for every dtype as soon as ANY level fits -- 800x1333, levels 2-3 resident.)
-            if (mode != 1 && l0_host > p.L - 1) nt = 0;
-            const int force_nt = knobs().fwd_rs_nt;
-            if (force_nt == 1 || force_nt == 2 || force_nt == 4) nt = force_nt;
-            const int parts = nt ? (rs_tiles_per_clip + kRsWaves * nt - 1) / (kRsWaves * nt) : 0;
-            // few tiles per (clip, head) leave waves of the workgroups without one: 19 tiles (300 queries of a single-frame call)
-            // on 2 x 16 waves -- 36-image decoder-like call in fp32 on the SwinL pyramid 0.078 ms here, 0.055 on the tile kernels
-            // (only where the slab starts at level 2 in a 4-byte type, i.e. saves the least: elsewhere, and in the gather pass, the slab
-            // kernels stay ahead by 4-19 %)
-            if (mode != 1 && nt && esz == 4 && l0_host >= 2 && 10LL * rs_tiles_per_clip < 7LL * parts * kRsWaves * nt) nt = 0;
-            if (mode != 0 && nt && clips * p.M * parts <= 0x7fffffffLL) {
-                // fp32, one tile per wave, slab from level 2 on: the software-pipelined slot body of that instantiation spills 31 VGPRs
-                // and its plain loop (the kernel compiled for a level-1 slab falls back to it) is 16-27 % faster on the SwinL pyramid
-                // (decoder call, 4 / 16 / 32 clips: 0.175 -> 0.137, 0.644 -> 0.540, 1.178 -> 0.973 ms; 800x1333: the same)
-                const int body_l0 = (esz == 4 && nt == 1 && l0_host >= 2) ? 1 : l0_host;
-                return launch_fwd_rs(dtype, nt, body_l0, p, parts, (unsigned)(clips * p.M * parts), stream);
-            }
-        }
-        // SMALL forwards -- one clip at the 60 / 180 queries per frame of DeVIS's shipped configs is 192-1104 single-wave workgroups on
-        // 1024 SIMDs, each walking its rows' 96 points as a chain of dependent gather batches -- put THREE waves on a tile, each with
-        // a share of the tile's 16-point chunks, partial rows added through LDS in wave order (msda_fwd_tile_kernel, MW): 60 queries
-        // fp32 0.020 -> 0.013 ms, fp16 0.034 -> 0.015; 180 queries fp16 0.041 -> 0.027; 300 queries bf16 0.043 -> 0.031.  With more
-        // workgroups than SIMDs (fp32 from 180 queries on) the chip is busy anyway and the split only adds the exchange
-        // (profiles/r04_logs/small_batch_tile_waves.log: no gain at 1824 workgroups).
-        const int chunks = (p.LA * p.PA + kPch - 1) / kPch + (p.LB * p.PB + kPch - 1) / kPch;
-        int waves = knobs().fwd_tile_waves;
-        // (fewer single-wave workgroups than SIMDs -- 4 per CU; 4-byte types: than three quarters of them)
-        if (waves < 0) waves = blocks <= (long long)device_cus() * (esz == 4 ? 3 : 4) ? 3 : 1;
-        waves = std::max(1, std::min(std::min(waves, chunks), kTileMaxWaves));
-        if (!(G == 4 || G == 8)) waves = 1;
-        auto lds_of = [&](int w) { return (size_t)w * RPW * kRowSlots * 32 + (size_t)(p.LA + p.LB) * sizeof(Level) + (size_t)w * kWave * VEC * 4; };
-        while (waves > 1 && lds_of(waves) > 48 * 1024) --waves;
-        return launch_fwd_tile(dtype, G, p, (unsigned)blocks, waves > 1 ? lds_of(waves) : lds, stream, waves);
-    }
-    const bool want_value = (grads & kGradValue) != 0, want_sampling = (grads & kGradSampling) != 0;
-    if (!scatter_applicable(p)) {
-        if (!want_value) {      // the one-kernel backward without its atomics: no records, no tickets, nothing to zero-fill
-            Params pq = p;
-            pq.bbox = nullptr; pq.bsum = nullptr; pq.workspace = nullptr;
-            return launch_bwd_tile(dtype, G, false, pq, (unsigned)blocks, tile_lds_bytes(RPW, p.LA + p.LB, true), stream);
-        }
-        if (p.gv_storage) return fail(MSDA_ERR_ARG, "msda backward: this call needs grad_value in the arithmetic type (see msda_grad_value_dtype)%s");
-        if (hipMemsetAsync(p.grad_value, 0, (size_t)p.groups * p.S * p.M * p.D * sizeof(float), stream) != hipSuccess)
-            return fail(MSDA_ERR_HIP, "msda backward: hipMemsetAsync(grad_value) failed%s");
-        return launch_bwd_tile(dtype, G, true, p, (unsigned)blocks, lds, stream, !want_sampling);
-    }
-    // Which levels the owner-computes scatter walks and which go to the matrix pipe is settled BEFORE the gather pass: the gather
-    // pass leaves culling records only for the levels the owner kernel will walk band by band (16 clips: 0.400 -> 0.394 ms, 22 MB of stores less).
-    int l0 = p.L, mfma_tiles = 0;
-    const bool owner_route = owner_scatter_applicable(p, esz) && (p.cull_points || !p.bbox);
-    if (owner_route) {
-        // The coarse levels -- the last one or two of the pyramid, together at most ~300 pixels -- on the matrix pipe (msda_mfma.hip):
-        // the owner-computes kernel then runs on levels [0, l0).  Needs the host copy of the shapes (a true copy: include/msda.h)
-        // and at least 16 queries (a step is 16 groups).  Automatic for decoder-shaped batches: an item walks (1 + sources) x Lq
-        // groups in 8 waves, so a handful of items of encoder length would be the kernel's whole duration.
-        // (its loads are buffer loads with 32-bit byte offsets inside one clip: grad_out and the point arrays of a clip below 2 GiB)
-        const long long lesz = (dtype == MSDA_BF16_LOC32 || dtype == MSDA_F16_LOC32) ? 4 : esz;
-        const long long clip_rows = (long long)p.frames * p.Lq;
-        const bool mfma_fits = clip_rows * p.M * p.D * esz < 0x7fffffffLL &&
-                               clip_rows * p.M * std::max((long long)p.LA * p.PA, (long long)p.LB * p.PB) * 2 * lesz < 0x7fffffffLL;
-        if (knobs().scatter_mfma != 0 && mfma_fits && p.shapes_host && p.Lq >= 16 && p.L >= 2) {
-            long long px = 0;
-            for (int l = p.L - 1; l >= 1 && l >= p.L - 2; --l) {
-                const long long hw = p.shapes_host[2 * l] * p.shapes_host[2 * l + 1];
-                if (p.shapes_host[2 * l] <= 0 || p.shapes_host[2 * l + 1] <= 0 || !mfma_scatter_tiles(px + hw)) break;
-                px += hw; l0 = l; mfma_tiles = mfma_scatter_tiles(px);
-            }
-            const long long items = (long long)p.groups * p.M, per_item = (long long)p.Lq * (1 + p.window);
-            // Automatic rule (profiles/r06_logs/mfma_check.log; scatter pass, owner kernel alone -> with this kernel, ms): the two coarse
-            // levels of the 360x640 pyramid cost the owner kernel 0.19 ms at 16 clips of 300 queries and this one 0.12 (0.563 -> 0.502;
-            // bf16 0.564 -> 0.473; 4 / 8 / 32 clips 0.159 -> 0.148 / 0.289 -> 0.265 / 1.096 -> 1.064); the single 273-pixel level of the
-            // 800x1333 pyramid 0.553 -> 0.512 (with the owner kernel's bands rotated unconditionally; see below).
-            // It needs items to fill the chip -- 2 clips (96 items) 0.089 -> 0.110, one clip 0.053 -> 0.088 -- and items long enough to
-            // pay for their zero-fill and reduction: the plain op on 48 images x 300 queries (19 steps per item) 0.100 -> 0.109.  Encoder-
-            // shaped calls (one query per pixel: tens of thousands of groups per item) win once there are enough items -- 4 clips at
-            // 360x640: 1.924 -> 1.733 -- and lose with one clip's 48 (0.556 -> 0.987; BASELINE configs[1], 64 items: 0.644 -> 0.688).
-            const bool enough = items >= 128 && per_item >= 512 && (per_item <= 8192 || items >= 192);
-            // (after the owner kernel's band rotation became conditional -- msda_scatter.hip -- the 96-pixel last level of the SwinL
-            // pyramid pays as well: 16 clips 0.679 -> 0.636; the 273-pixel one of 800x1333 is level: 0.514 -> 0.510)
-            if (mfma_tiles && knobs().scatter_mfma < 0 && !(enough && (p.L - l0 == 2 || px >= 64))) { l0 = p.L; mfma_tiles = 0; }
+// Grid of the persistent scatter kernels: one 1024-thread workgroup per CU, a multiple of the XCD count (item % M stays put).
+unsigned persistent_grid()
+{
+    const unsigned cus = (unsigned)device_cus();
+    return cus - cus % 8;
+}
+
+// What the fast path's rules read of a call, worked out once.
+struct Shape {
+    int esz;                            // bytes of a value element
+    int G, RPW;                         // tile kernels: G = D / (16 / esz) lanes per row, 64 / G rows per wave,
+    unsigned blocks;                    // one workgroup per (wave of rows, head)
+    size_t tile_lds;                    // ... and its LDS (backward: with the interval records when p.bbox is set)
+    int64_t clips;
+    bool rs_ok;                         // rs_fits
+    int rs_tiles_per_clip, l0_host;     // resident-slab kernels: 16-row tiles per clip, first slab level
+    long long outside, l2_budget;       // bytes of one (clip, head)'s levels below l0_host; see rs_tiles_per_wave
+};
+
+int shape_of(int dtype, const Params &p, bool bwd, Shape &s)
+{
+    s.esz = elem_bytes(dtype);
+    s.G = p.D / (16 / s.esz);
+    s.RPW = kWave / s.G;
+    const int64_t blocks = (int64_t)p.groups * ((p.Lq + s.RPW - 1) / s.RPW) * p.M;
+    if (blocks > 0x7fffffffLL) return fail(MSDA_ERR_ARG, "msda: problem too large for one launch%s");
+    s.blocks = (unsigned)blocks;
+    s.tile_lds = tile_lds_bytes(s.RPW, p.LA + p.LB, bwd, bwd && p.bbox != nullptr);
+    s.clips = p.groups / p.frames;
+    s.rs_ok = rs_fits(p, s.esz);
+    s.rs_tiles_per_clip = p.frames * ((p.Lq + kRsRows - 1) / kRsRows);
+    const int rs_row = 32 * s.esz;                                // bytes of one pixel of one head
+    s.l0_host = s.rs_ok ? host_first_slab_level(p, (kRsSlabBytes - kRsSlack) / rs_row) : p.L;
+    s.outside = host_pixels_below(p, s.l0_host) * rs_row;
+    s.l2_budget = s.esz == 4 ? (2ll << 20) : (4ll << 20);         // see rs_tiles_per_wave
+    return MSDA_OK;
+}
+
+// Encoder-shaped calls (one query per pixel) take the resident-window kernels when the slab of the resident-slab kernels
+// would hold the last level at most (fp32 at 800x1333: 273 of 22223 pixels) -- measured forward 2.38 -> 1.07 ms, gather pass 2.85 -> 1.60 ms there; where
+// more levels fit the slab (16-bit types, the 360x640 pyramid) the two families are on a par and the slab kernels stay.
+// `mode`: MSDA_FWD_WIN / MSDA_BWD_WIN.
+bool window_route(const Shape &s, const Params &p, const Knobs &k, int mode, WinPlan &w)
+{
+    // (round 4 audit: also when a 4-byte slab holds only the last TWO levels -- SwinL 480x768 in fp32: forward 0.49 -> 0.37 ms,
+    // gather pass 0.66 -> 0.55; 2-byte slabs of that kind -- 800x1333 bf16 -- are on a par and stay)
+    // (temporal calls only: single-frame encoder calls on that pyramid are 6-26 % faster on the slab kernels)
+    const bool few_levels = s.l0_host >= p.L - 1 || (s.esz == 4 && p.frames > 1 && p.L > 2 && s.l0_host >= p.L - 2);
+    if (mode == 0 || (mode != 1 && !(p.Lq == p.S && p.L > 1 && few_levels))) return false;     // (cheap tests first)
+    return win_plan_cached(p, s.esz, mode == 1, k.win_min_halo, w);
+}
+
+// ---- forward ------------------------------------------------------------------------------------------------
+struct FwdPlan {
+    enum { kWindow, kSlab, kTile } family = kTile;
+    WinPlan win;                        // kWindow
+    int nt = 0, body_l0 = 0, parts = 0; // kSlab: tiles per wave, level the slot body is compiled for, workgroups per (clip, head)
+    int waves = 1;                      // kTile: waves per tile
+    size_t lds = 0;                     // kTile
+};
+
+FwdPlan plan_forward(const Shape &s, const Params &p, const Knobs &k)
+{
+    FwdPlan f;
+    if (window_route(s, p, k, k.fwd_win, f.win)) { f.family = FwdPlan::kWindow; return f; }
+    if (s.rs_ok) {
+        // resident-slab forward: up to NT * 16 tiles of 16 rows per workgroup, so that the per-frame slab staging is
+        // amortised; tiles per wave (NT) and workgroups per (clip, head) (parts): see rs_tiles_per_wave
+        const int mode = k.fwd_rs;                                     // -1 auto, 0 off, 1 force
+        // at most 2 tiles per wave for slabs that start at level 2 (large pyramids) and for fp32: the 4-tile instantiations of
+        // those slot bodies spill 10-40 VGPRs (profiles/r04_resource_usage.txt); BASELINE configs[1] forward 0.306 -> 0.290 ms,
+        // SwinL 0.088 -> 0.082, 2-clip fp32 encoder call 0.52 -> 0.46
+        const int max_nt = (s.l0_host >= 2 || s.esz == 4) ? 2 : 4;
+        int nt = rs_tiles_per_wave(p, s.rs_tiles_per_clip, s.outside, mode == 1, s.l2_budget, max_nt);
+        // the slab must hold at least the last level.  (Since the whole-row loads / stores of the points and gradients
+        // the kernel wins for every dtype as soon as ANY level fits -- 800x1333, levels 2-3 resident.)
+        if (mode != 1 && s.l0_host > p.L - 1) nt = 0;
+        if (k.fwd_rs_nt == 1 || k.fwd_rs_nt == 2 || k.fwd_rs_nt == 4) nt = k.fwd_rs_nt;
+        const int parts = nt ? (s.rs_tiles_per_clip + kRsWaves * nt - 1) / (kRsWaves * nt) : 0;
+        // few tiles per (clip, head) leave waves of the workgroups without one: 19 tiles (300 queries of a single-frame call)
+        // on 2 x 16 waves -- 36-image decoder-like call in fp32 on the SwinL pyramid 0.078 ms here, 0.055 on the tile kernels
+        // (only where the slab starts at level 2 in a 4-byte type, i.e. saves the least: elsewhere, and in the gather pass, the slab
+        // kernels stay ahead by 4-19 %)
+        if (mode != 1 && nt && s.esz == 4 && s.l0_host >= 2 && 10LL * s.rs_tiles_per_clip < 7LL * parts * kRsWaves * nt) nt = 0;
+        if (mode != 0 && nt && s.clips * p.M * parts <= 0x7fffffffLL) {
+            f.family = FwdPlan::kSlab;
+            f.nt = nt;
+            f.parts = parts;
+            // fp32, one tile per wave, slab from level 2 on: the software-pipelined slot body of that instantiation spills 31 VGPRs
+            // and its plain loop (the kernel compiled for a level-1 slab falls back to it) is 16-27 % faster on the SwinL pyramid
+            // (decoder call, 4 / 16 / 32 clips: 0.175 -> 0.137, 0.644 -> 0.540, 1.178 -> 0.973 ms; 800x1333: the same)
+            f.body_l0 = (s.esz == 4 && nt == 1 && s.l0_host >= 2) ? 1 : s.l0_host;
+            return f;
         }
     }
+    // SMALL forwards -- one clip at the 60 / 180 queries per frame of DeVIS's shipped configs is 192-1104 single-wave workgroups on
+    // 1024 SIMDs, each walking its rows' 96 points as a chain of dependent gather batches -- put THREE waves on a tile, each with
+    // a share of the tile's 16-point chunks, partial rows added through LDS in wave order (msda_fwd_tile_kernel, MW): 60 queries
+    // fp32 0.020 -> 0.013 ms, fp16 0.034 -> 0.015; 180 queries fp16 0.041 -> 0.027; 300 queries bf16 0.043 -> 0.031.  With more
+    // workgroups than SIMDs (fp32 from 180 queries on) the chip is busy anyway and the split only adds the exchange
+    // (profiles/r04_logs/small_batch_tile_waves.log: no gain at 1824 workgroups).
+    const int G = s.G, RPW = s.RPW, VEC = 16 / s.esz;
+    const int chunks = (p.LA * p.PA + kPch - 1) / kPch + (p.LB * p.PB + kPch - 1) / kPch;
+    int waves = k.fwd_tile_waves;
+    // (fewer single-wave workgroups than SIMDs -- 4 per CU; 4-byte types: than three quarters of them)
+    if (waves < 0) waves = s.blocks <= (long long)device_cus() * (s.esz == 4 ? 3 : 4) ? 3 : 1;
+    waves = std::max(1, std::min(std::min(waves, chunks), kTileMaxWaves));
+    if (!(G == 4 || G == 8)) waves = 1;
+    auto lds_of = [&](int w) { return (size_t)w * RPW * kRowSlots * 32 + (size_t)(p.LA + p.LB) * sizeof(Level) + (size_t)w * kWave * VEC * 4; };
+    while (waves > 1 && lds_of(waves) > 48 * 1024) --waves;
+    f.waves = waves;
+    f.lds = waves > 1 ? lds_of(waves) : s.tile_lds;
+    return f;
+}
+
+int launch_forward(int dtype, const Params &p, const Knobs &k, const Shape &s, hipStream_t stream)
+{
+    const FwdPlan f = plan_forward(s, p, k);
+    switch (f.family) {
+        case FwdPlan::kWindow: return launch_fwd_win(dtype, p, f.win, stream);
+        case FwdPlan::kSlab: return launch_fwd_rs(dtype, f.nt, f.body_l0, p, f.parts, (unsigned)(s.clips * p.M * f.parts), stream);
+        default: return launch_fwd_tile(dtype, s.G, p, s.blocks, f.lds, stream, f.waves);
+    }
+}
+
+// ---- backward: scatter plan -----------------------------------------------------------------------------------
+struct ScatterPlan {
+    enum { kAtomic, kOwner, kLds } route = kAtomic;   // one-kernel backward with global atomics / owner-computes / LDS-atomic scatter
+    int l0 = 0;                         // kOwner: the owner-computes kernel walks levels [0, l0), the matrix-pipe kernel [l0, L)
+    int mfma_tiles = 0;                 // kOwner: tiles of the matrix-pipe kernel, 0 = it does not run
+    bool run_owner = false, run_mfma = false;   // kOwner: which of the two kernels run (MSDA_SCATTER_PART)
+    bool fused_zero = false;            // kOwner: the zero-fill rides in the owner kernel's prologue (bit 512 of its dbg)
+    bool image_order = false;           // kOwner: the owner kernel's items in image order
+    unsigned rec_mask = ~0u;            // levels the gather pass leaves culling records for (Params::rec_mask)
+    bool interval_records = false;      // the gather pass leaves (min, max) interval records: only the tile kernel writes those
+};
+
+// The coarse levels -- the last one or two of the pyramid, together at most ~300 pixels -- on the matrix pipe (msda_mfma.hip):
+// the owner-computes kernel then runs on levels [0, l0).  Needs the host copy of the shapes (a true copy: include/msda.h)
+// and at least 16 queries (a step is 16 groups).  Automatic for decoder-shaped batches: an item walks (1 + sources) x Lq
+// groups in 8 waves, so a handful of items of encoder length would be the kernel's whole duration.
+void plan_matrix_pipe(int dtype, const Shape &s, const Params &p, const Knobs &k, ScatterPlan &sc)
+{
+    // (its loads are buffer loads with 32-bit byte offsets inside one clip: grad_out and the point arrays of a clip below 2 GiB)
+    const long long lesz = (dtype == MSDA_BF16_LOC32 || dtype == MSDA_F16_LOC32) ? 4 : s.esz;
+    const long long clip_rows = (long long)p.frames * p.Lq;
+    const bool mfma_fits = clip_rows * p.M * p.D * s.esz < 0x7fffffffLL &&
+                           clip_rows * p.M * std::max((long long)p.LA * p.PA, (long long)p.LB * p.PB) * 2 * lesz < 0x7fffffffLL;
+    if (k.scatter_mfma == 0 || !mfma_fits || !p.shapes_host || p.Lq < 16 || p.L < 2) return;
+    long long px = 0;
+    for (int l = p.L - 1; l >= 1 && l >= p.L - 2; --l) {
+        const long long hw = p.shapes_host[2 * l] * p.shapes_host[2 * l + 1];
+        if (p.shapes_host[2 * l] <= 0 || p.shapes_host[2 * l + 1] <= 0 || !mfma_scatter_tiles(px + hw)) break;
+        px += hw; sc.l0 = l; sc.mfma_tiles = mfma_scatter_tiles(px);
+    }
+    const long long items = (long long)p.groups * p.M, per_item = (long long)p.Lq * (1 + p.window);
+    // Automatic rule (profiles/r06_logs/mfma_check.log; scatter pass, owner kernel alone -> with this kernel, ms): the two coarse
+    // levels of the 360x640 pyramid cost the owner kernel 0.19 ms at 16 clips of 300 queries and this one 0.12 (0.563 -> 0.502;
+    // bf16 0.564 -> 0.473; 4 / 8 / 32 clips 0.159 -> 0.148 / 0.289 -> 0.265 / 1.096 -> 1.064); the single 273-pixel level of the
+    // 800x1333 pyramid 0.553 -> 0.512 (with the owner kernel's bands rotated unconditionally; see below).
+    // It needs items to fill the chip -- 2 clips (96 items) 0.089 -> 0.110, one clip 0.053 -> 0.088 -- and items long enough to
+    // pay for their zero-fill and reduction: the plain op on 48 images x 300 queries (19 steps per item) 0.100 -> 0.109.  Encoder-
+    // shaped calls (one query per pixel: tens of thousands of groups per item) win once there are enough items -- 4 clips at
+    // 360x640: 1.924 -> 1.733 -- and lose with one clip's 48 (0.556 -> 0.987; BASELINE configs[1], 64 items: 0.644 -> 0.688).
+    const bool enough = items >= 128 && per_item >= 512 && (per_item <= 8192 || items >= 192);
+    // (after the owner kernel's band rotation became conditional -- msda_scatter.hip -- the 96-pixel last level of the SwinL
+    // pyramid pays as well: 16 clips 0.679 -> 0.636; the 273-pixel one of 800x1333 is level: 0.514 -> 0.510)
+    if (sc.mfma_tiles && k.scatter_mfma < 0 && !(enough && (p.L - sc.l0 == 2 || px >= 64))) { sc.l0 = p.L; sc.mfma_tiles = 0; }
+}
+
+// Items of the owner-computes scatter in image order for long candidate ranges of a TEMPORAL call (the encoder's fused call: the
+// frames of one band run side by side and share the rows and points of the queries near it), when the host knows the band count
+// (scatter_order 1, MSDA_SCATTER_DBG bit 256: the level-by-level order).  Plain calls keep the heaviest-first order: measured on one box,
+// image order / level order: 800x1333 T = 6 one clip 2.76 / 2.86 ms, 360x640 T = 6 0.54 / 0.55, but the single-frame
+// encoder call of BASELINE configs[1] (N = 8, bf16) 0.92 / 0.63 and the SwinL one (N = 6, fp16) 0.23 / 0.17 -- with
+// `clip` outermost the batch is 8 serial tails.
+// (round 4, after the per-item fixed costs shrank: at 360x640, Lq = 4820, image order is now the slower one, 0.555 / 0.529)
+// (a pinned route, msda_pin_route scatter_order: 1 = level order, 2 = image order wherever the bands can be sorted)
+bool owner_image_order(const Params &p, const Knobs &k, int own_levels)
+{
+    if (!((p.Lq >= 8192 && p.frames > 1) || k.scatter_order == 2) || !p.shapes_host || k.scatter_order == 1) return false;
+    int bands = 0;
+    for (int l = 0; l < own_levels; ++l) {
+        const long long H = p.shapes_host[2 * l], W = p.shapes_host[2 * l + 1];
+        if (H <= 0 || W <= 0) return false;         // (degenerate level: the device counts its bands differently)
+        const long long R = std::min<long long>(H, kOwnPix / W);
+        bands += R > 0 ? (int)((H + R - 1) / R) : 1;
+    }
+    return bands <= kOwnMaxSorted;
+}
+
+// Which scatter produces grad_value, and (since the gather pass leaves culling records only for the levels the owner kernel
+// will walk band by band -- 16 clips: 0.400 -> 0.394 ms, 22 MB of stores less) which records the gather pass leaves: settled
+// BEFORE the gather pass.  `grads` without kGradValue: no scatter follows, rec_mask = 0.
+ScatterPlan plan_scatter(int dtype, const Shape &s, const Params &p, const Knobs &k, int grads)
+{
+    ScatterPlan sc;
+    if (!scatter_applicable(p, k)) return sc;
+    const bool want_value = (grads & kGradValue) != 0;
+    const bool owner = owner_scatter_applicable(p, s.esz, k) && (p.cull_points || !p.bbox);
+    sc.route = owner ? ScatterPlan::kOwner : ScatterPlan::kLds;
+    sc.l0 = p.L;
+    if (owner) plan_matrix_pipe(dtype, s, p, k, sc);
     // Culling records: not for the matrix-pipe levels, and not for levels of ONE band (the host copy of the shapes says so: every
     // group is a candidate of the only band, the owner kernel takes all its points) -- the 23x40 level of the 360x640 pyramid.
-    unsigned rec_mask = ~0u;
-    if (owner_route && !knobs().bwd_all_records) {
-        for (int l = l0; l < p.L && l < 32; ++l) rec_mask &= ~(1u << l);
-        for (int l = 0; p.shapes_host && l < l0 && l < 32; ++l) {
+    if (owner && !k.bwd_all_records) {
+        for (int l = sc.l0; l < p.L && l < 32; ++l) sc.rec_mask &= ~(1u << l);
+        for (int l = 0; p.shapes_host && l < sc.l0 && l < 32; ++l) {
             const long long H = p.shapes_host[2 * l], W = p.shapes_host[2 * l + 1];
-            if (H > 0 && W > 0 && W <= kOwnPix && H <= kOwnPix / W) rec_mask &= ~(1u << l);
+            if (H > 0 && W > 0 && W <= kOwnPix && H <= kOwnPix / W) sc.rec_mask &= ~(1u << l);
         }
     }
-    Params pq = p;                                 // the gather pass's view
-    pq.rec_mask = rec_mask;
-    if (!want_value) {                             // no scatter follows: no records, no tickets
-        pq.bbox = nullptr; pq.bsum = nullptr;
-        pq.workspace = nullptr; pq.rec_mask = 0;
+    if (!want_value) sc.rec_mask = 0;
+    // Does the full call's gather pass leave (min, max) interval records?  A call without kGradValue leaves no records and needs
+    // no workspace, but takes the full call's kernel: the one a full call with a workspace of msda_backward_workspace_bytes()
+    // takes (what the Python binding always passes).
+    sc.interval_records = want_value ? (p.bbox != nullptr && !p.cull_points)
+                                     : (k.bwd_cull != 0 && !(k.bwd_cull != 2 && owner_scatter_applicable(p, s.esz, k)));
+    if (!owner) return sc;
+    // When every level's row fits a band (the host copy of the shapes says so) no pixel takes the float-atomic branch, and the
+    // zero-fill of the pixels outside the levels -- normally none -- rides in the scatter kernel's prologue (bit 512) instead of
+    // a launch of its own in front of it: one dependent dispatch less per backward (one clip from a HIP graph 0.127 -> see r04 logs)
+    sc.fused_zero = p.shapes_host != nullptr && (k.scatter_dbg & 1024) == 0;
+    for (int l = 0; sc.fused_zero && l < p.L; ++l) sc.fused_zero = p.shapes_host[2 * l + 1] > 0 && p.shapes_host[2 * l + 1] <= kOwnPix;
+    sc.image_order = owner_image_order(p, k, sc.l0);
+    sc.run_owner = !(sc.mfma_tiles && k.scatter_part == 2);
+    sc.run_mfma = sc.mfma_tiles && k.scatter_part != 1;
+    return sc;
+}
+
+// ---- backward: gather pass --------------------------------------------------------------------------------------
+struct GatherPlan {
+    enum { kRecordsOnly, kWindow, kSlab, kTile } kind = kTile;
+    WinPlan win;                        // kWindow
+    int parts = 0, frame_split = 0;     // kSlab: workgroups per (clip, head) -- or per (clip, head, frame) with frame_split
+    unsigned grid = 0;                  // kSlab
+};
+
+// Workgroups per (clip, head, frame) of the resident-slab gather pass with one source frame per workgroup, 0 = not that grid.
+// One source frame per workgroup (round 4): the gather pass carries nothing from frame to frame, so (clip, head, frame,
+// half of the clip's tiles) workgroups stage ONE slab each and meet at no barrier afterwards -- a quarter of the staging
+// traffic of (clip, head, part) workgroups walking the frames.  Pays from ~8 clips on (same box, fp32:
+// 8 / 16 / 32 clips 0.245 -> 0.229 / 0.48 -> 0.44 / 0.881 -> 0.874 ms; 4 clips with TWO workgroups per frame
+// 0.100 -> 0.122 -- with four it pays there too, see below).
+// SMALL batches -- the one clip per GPU DeVIS itself issues (main.py:85) -- cannot fill the chip with (clip, head, part)
+// workgroups at all (tpw = 0) and used to fall to the tile kernels: with the frames as a workgroup index 1 / 2 clips make
+// 192 / 384 workgroups of <= 2 tiles per wave (same box, gather pass of 1 clip fp32 0.058 -> 0.040 ms, bf16 0.074 -> 0.037;
+// 2 clips 0.088 -> 0.063, 0.094 -> 0.065; profiles/r04_logs/small_batch_sweep.log).  `small`: set when that rule chose it.
+int gather_frame_parts(const Shape &s, const Params &p, const Knobs &k, int tpw, int parts, bool &small)
+{
+    small = false;
+    if (k.bwd_rs_fsplit >= 0) return k.bwd_rs_fsplit;
+    const int mode = k.bwd_rs, esz = s.esz, cus = device_cus();
+    // (round 4, second sweep, profiles/r04_logs/gather_fsplit_sweep.log: 2-byte types gain 5-10 % at 8 / 16 / 32 / 64 clips;
+    // fp32 gains 4-11 % up to 32 clips and loses 3 % at 64)
+    // Only while the levels outside the slab are small: the frame-split grid keeps 16 frame maps per XCD in flight instead
+    // of 4 -- fine for the 360x640 pyramid's level 0 (460 KB in fp32), 12-16 % SLOWER on the 800x1333 one (levels 0-1
+    // outside: 2.7 MB per map; 16 clips bf16 0.531 -> 0.618 ms, fp32 0.906 -> 1.012).
+    const long long wgs = s.clips * p.M * p.frames * 2;
+    // (route audit, profiles/r04_logs/route_audit_*.log: SwinL pyramid in fp32, 737 KB outside, 8-32 clips 14-20 % slower)
+    const bool small_outside = s.outside <= (512ll << 10);
+    // (encoder-shaped batches: 8 clips at 360x640 in fp32 2.50 -> 2.80 ms on this grid, in bf16 2.49 -> 2.13)
+    if (p.frames > 1 && small_outside && wgs >= 3LL * cus && (esz == 2 || (wgs < 24LL * cus && p.Lq != p.S))) return 2;
+    // (2-byte encoder-shaped batches one size below that: four workgroups per frame at 4 clips, 1.23 -> 1.13 ms at 360x640,
+    // 1.94 -> 1.80 on the SwinL pyramid)
+    if (esz == 2 && p.frames > 1 && p.Lq == p.S && small_outside && 2 * wgs >= 3LL * cus) return 4;
+    // fp32 batches whose (clip, head, part) workgroups are a single round over the CUs (4 clips): four workgroups per (clip,
+    // head, frame) balance better -- 0.103 -> 0.099 / 0.177 -> 0.149 / 0.259 -> 0.242 ms on the three audited pyramids;
+    // 2-byte types lose 2-14 % there and stay, and so do encoder-shaped calls (one clip is 232 workgroups of 4 tiles: 0.36 vs
+    // 0.47 ms on the frame-split grid)
+    if (tpw && esz == 4 && mode == -1 && p.frames > 1 && p.Lq != p.S && s.l0_host <= p.L - 1 && s.clips * p.M * parts <= cus) return 4;
+    if (!tpw && mode == -1 && p.frames > 1 && s.l0_host <= p.L - 1 && s.clips * p.M * p.frames * 4 >= cus / 2) {
+        // (2-byte types with two clips: 2 workgroups per (clip, head, frame) -- 0.067 -> 0.056 ms; fp32 the other way round)
+        // Whatever the query count -- DeVIS's shipped configs run 60 queries per frame (YouTube-VIS) and 180 (OVIS), 24 / 72
+        // tiles per clip: one clip of 60 queries 0.050 -> 0.020 ms in fp32, 0.065 -> 0.020 in fp16, 10 queries 0.042 -> 0.018
+        // (the tile kernels walk a chain of 24 dependent gather batches per wave however few rows there are)
+        small = true;
+        return (esz == 2 && s.clips * p.M * p.frames * 2 >= 3LL * cus / 4) ? 2 : 4;
     }
-    // Does the full call's gather pass leave (min, max) interval records?  Only the tile kernel writes those, so it must run
-    // then.  A call without kGradValue leaves no records and needs no workspace, but takes the full call's kernel: the one a
-    // full call with a workspace of msda_backward_workspace_bytes() takes (what the Python binding always passes).
-    const bool interval_records = want_value ? (p.bbox != nullptr && !p.cull_points)
-                                             : (knobs().bwd_cull != 0 && !(knobs().bwd_cull != 2 && owner_scatter_applicable(p, esz)));
+    return 0;
+}
+
+GatherPlan plan_gather(const Shape &s, const Params &p, const Knobs &k, int grads, bool interval_records)
+{
+    GatherPlan g;
+    // grad_value alone: the records (and zeroed tickets) the gather pass would have left, from the sampling locations only
+    if (!(grads & kGradSampling)) { g.kind = GatherPlan::kRecordsOnly; return g; }
+    if (interval_records) return g;                 // (only the tile kernel writes interval records)
+    if (window_route(s, p, k, k.bwd_win, g.win)) { g.kind = GatherPlan::kWindow; return g; }
+    if (!s.rs_ok) return g;
+    // resident-slab gather pass: same applicability rule as the forward
+    const int mode = k.bwd_rs;
+    int tpw = rs_tiles_per_wave(p, s.rs_tiles_per_clip, s.outside, mode == 1, s.l2_budget,
+                                s.l0_host >= 2 ? 2 : 4);      // (as in the forward: configs[1] gather pass 0.407 -> 0.395 ms)
+    if (k.bwd_rs_tpw > 0) tpw = k.bwd_rs_tpw;
+    const int parts = tpw ? (s.rs_tiles_per_clip + tpw * kRsWaves - 1) / (tpw * kRsWaves) : 1;       // (L2: see the forward)
+    const bool want = mode == 1 || (mode == -1 && tpw && s.l0_host <= p.L - 1);
+    bool want_small = false;
+    const int fparts = gather_frame_parts(s, p, k, tpw, parts, want_small);
+    const long long frame_grid = s.clips * p.M * p.frames * fparts, grid = s.clips * p.M * parts;
+    if ((want || want_small) && fparts > 0 && p.frames > 1 && frame_grid <= 0x7fffffffLL) {
+        g.kind = GatherPlan::kSlab; g.parts = fparts; g.frame_split = 1; g.grid = (unsigned)frame_grid;
+    } else if (want && grid <= 0x7fffffffLL) {
+        g.kind = GatherPlan::kSlab; g.parts = parts; g.grid = (unsigned)grid;
+    }
+    return g;
+}
+
+// The backward's gather pass + scatter on the tile / resident-slab / resident-window / scatter kernels.  `grads`: the gradient
+// groups asked for (msda_backward_grads) -- without kGradValue the gather pass runs as in the full call but leaves no culling
+// records and nothing follows it; without kGradSampling the culling-records kernel stands in for the gather pass in front of
+// the full call's scatter.
+int launch_backward(int dtype, const Params &p, const Knobs &k, const Shape &s, hipStream_t stream, int grads)
+{
+    const bool want_value = (grads & kGradValue) != 0, want_sampling = (grads & kGradSampling) != 0;
+    const ScatterPlan sc = plan_scatter(dtype, s, p, k, grads);
+    Params pq = p;                                 // the gather pass's view
+    pq.rec_mask = sc.rec_mask;
+    if (!want_value) { pq.bbox = nullptr; pq.bsum = nullptr; pq.workspace = nullptr; }      // no scatter follows: no records, no tickets
+    if (p.gv_storage && sc.route != ScatterPlan::kOwner)      // (only the owner-computes scatter writes the storage type)
+        return fail(MSDA_ERR_ARG, "msda backward: this call needs grad_value in the arithmetic type (see msda_grad_value_dtype)%s");
+    if (sc.route == ScatterPlan::kAtomic) {
+        // the one-kernel backward; without grad_value without its atomics: no records, no tickets, nothing to zero-fill
+        if (!want_value) return launch_bwd_tile(dtype, s.G, false, pq, s.blocks, tile_lds_bytes(s.RPW, p.LA + p.LB, true), stream);
+        if (const int rc = zero_grad_value(MSDA_F32, p.grad_value, p.groups, p.S, p.M, p.D, stream)) return rc;
+        return launch_bwd_tile(dtype, s.G, true, p, s.blocks, s.tile_lds, stream, !want_sampling);
+    }
     // MSDA_BWD_PHASES (measurement hook for bench.py): 1 = gather pass only, 2 = scatter pass only
     // (needs the workspace a previous gather pass filled), 3 = both (default)
-    const int phases = knobs().bwd_phases;
     int rc = MSDA_OK;
-    if ((phases & 1) && !want_sampling) {
-        // grad_value alone: the records (and zeroed tickets) the gather pass would have left, from the sampling locations only
-        if (pq.workspace) {
-            rc = launch_cull_records(dtype, pq, stream);
-            if (rc) return rc;
+    if (k.bwd_phases & 1) {
+        const GatherPlan g = plan_gather(s, p, k, grads, sc.interval_records);
+        switch (g.kind) {
+            case GatherPlan::kRecordsOnly: rc = pq.workspace ? launch_cull_records(dtype, pq, stream) : MSDA_OK; break;
+            case GatherPlan::kWindow: rc = launch_bwd_win(dtype, pq, g.win, stream); break;
+            case GatherPlan::kSlab: rc = launch_bwd_rs(dtype, s.l0_host, pq, g.parts, g.grid, stream, g.frame_split); break;
+            default: rc = launch_bwd_tile(dtype, s.G, false, pq, s.blocks, s.tile_lds, stream);
         }
-        if (pq.cull_points && pq.bsum) {
-            rc = launch_cull_summary(pq, stream);
-            if (rc) return rc;
-        }
-    } else if (phases & 1) {
-        bool done = false;
-        WinPlan w;
-        if (!interval_records && window_route(knobs().bwd_win, w)) {
-            rc = launch_bwd_win(dtype, pq, w, stream);
-            if (rc) return rc;
-            done = true;
-        }
-        if (!done && rs_ok && !interval_records) {
-            // resident-slab gather pass: same applicability rule as the forward
-            const int mode = knobs().bwd_rs;
-            int tpw = rs_tiles_per_wave(p, rs_tiles_per_clip, host_pixels_below(p, l0_host) * rs_row, mode == 1, l2_budget,
-                                        l0_host >= 2 ? 2 : 4);      // (as in the forward: configs[1] gather pass 0.407 -> 0.395 ms)
-            if (knobs().bwd_rs_tpw > 0) tpw = knobs().bwd_rs_tpw;
-            const int parts = tpw ? (rs_tiles_per_clip + tpw * kRsWaves - 1) / (tpw * kRsWaves) : 1;       // (L2: see the forward)
-            const bool want = mode == 1 || (mode == -1 && tpw && l0_host <= p.L - 1);
-            // One source frame per workgroup (round 4): the gather pass carries nothing from frame to frame, so (clip, head, frame,
-            // half of the clip's tiles) workgroups stage ONE slab each and meet at no barrier afterwards -- a quarter of the staging
-            // traffic of (clip, head, part) workgroups walking the frames.  Pays from ~8 clips on (same box, fp32:
-            // 8 / 16 / 32 clips 0.245 -> 0.229 / 0.48 -> 0.44 / 0.881 -> 0.874 ms; 4 clips with TWO workgroups per frame
-            // 0.100 -> 0.122 -- with four it pays there too, see below).
-            // SMALL batches -- the one clip per GPU DeVIS itself issues (main.py:85) -- cannot fill the chip with (clip, head, part)
-            // workgroups at all (tpw = 0) and used to fall to the tile kernels: with the frames as a workgroup index 1 / 2 clips make
-            // 192 / 384 workgroups of <= 2 tiles per wave (same box, gather pass of 1 clip fp32 0.058 -> 0.040 ms, bf16 0.074 -> 0.037;
-            // 2 clips 0.088 -> 0.063, 0.094 -> 0.065; profiles/r04_logs/small_batch_sweep.log).
-            int fparts = knobs().bwd_rs_fsplit;
-            bool want_small = false;
-            if (fparts < 0) {
-                // (round 4, second sweep, profiles/r04_logs/gather_fsplit_sweep.log: 2-byte types gain 5-10 % at 8 / 16 / 32 / 64 clips;
-                // fp32 gains 4-11 % up to 32 clips and loses 3 % at 64)
-                // Only while the levels outside the slab are small: the frame-split grid keeps 16 frame maps per XCD in flight instead
-                // of 4 -- fine for the 360x640 pyramid's level 0 (460 KB in fp32), 12-16 % SLOWER on the 800x1333 one (levels 0-1
-                // outside: 2.7 MB per map; 16 clips bf16 0.531 -> 0.618 ms, fp32 0.906 -> 1.012).
-                const long long wgs = clips * p.M * p.frames * 2;
-                // (route audit, profiles/r04_logs/route_audit_*.log: SwinL pyramid in fp32, 737 KB outside, 8-32 clips 14-20 % slower)
-                const bool small_outside = host_pixels_below(p, l0_host) * rs_row <= (512ll << 10);
-                // (encoder-shaped batches: 8 clips at 360x640 in fp32 2.50 -> 2.80 ms on this grid, in bf16 2.49 -> 2.13)
-                fparts = (p.frames > 1 && small_outside && wgs >= 3LL * device_cus() &&
-                          (esz == 2 || (wgs < 24LL * device_cus() && p.Lq != p.S))) ? 2 : 0;
-                // (2-byte encoder-shaped batches one size below that: four workgroups per frame at 4 clips, 1.23 -> 1.13 ms at 360x640,
-                // 1.94 -> 1.80 on the SwinL pyramid)
-                if (!fparts && esz == 2 && p.frames > 1 && p.Lq == p.S && small_outside && 2 * wgs >= 3LL * device_cus()) fparts = 4;
-                // fp32 batches whose (clip, head, part) workgroups are a single round over the CUs (4 clips): four workgroups per (clip,
-                // head, frame) balance better -- 0.103 -> 0.099 / 0.177 -> 0.149 / 0.259 -> 0.242 ms on the three audited pyramids;
-                // 2-byte types lose 2-14 % there and stay, and so do encoder-shaped calls (one clip is 232 workgroups of 4 tiles: 0.36 vs
-                // 0.47 ms on the frame-split grid)
-                if (!fparts && tpw && esz == 4 && mode == -1 && p.frames > 1 && p.Lq != p.S && l0_host <= p.L - 1 && clips * p.M * parts <= device_cus()) fparts = 4;
-                if (!fparts && !tpw && mode == -1 && p.frames > 1 && l0_host <= p.L - 1 && clips * p.M * p.frames * 4 >= device_cus() / 2) {
-                    // (2-byte types with two clips: 2 workgroups per (clip, head, frame) -- 0.067 -> 0.056 ms; fp32 the other way round)
-                    // Whatever the query count -- DeVIS's shipped configs run 60 queries per frame (YouTube-VIS) and 180 (OVIS), 24 / 72
-                    // tiles per clip: one clip of 60 queries 0.050 -> 0.020 ms in fp32, 0.065 -> 0.020 in fp16, 10 queries 0.042 -> 0.018
-                    // (the tile kernels walk a chain of 24 dependent gather batches per wave however few rows there are)
-                    fparts = (esz == 2 && clips * p.M * p.frames * 2 >= 3LL * device_cus() / 4) ? 2 : 4;
-                    want_small = true;
-                }
-            }
-            if ((want || want_small) && fparts > 0 && p.frames > 1 && clips * p.M * p.frames * fparts <= 0x7fffffffLL) {
-                rc = launch_bwd_rs(dtype, l0_host, pq, fparts, (unsigned)(clips * p.M * p.frames * fparts), stream, 1);
-                if (rc) return rc;
-                done = true;
-            } else if (want && clips * p.M * parts <= 0x7fffffffLL) {
-                rc = launch_bwd_rs(dtype, l0_host, pq, parts, (unsigned)(clips * p.M * parts), stream);
-                if (rc) return rc;
-                done = true;
-            }
-        }
-        if (!done) {
-            rc = launch_bwd_tile(dtype, G, false, pq, (unsigned)blocks, lds, stream);
-            if (rc) return rc;
-        }
-        if (pq.cull_points && pq.bsum) {     // block summaries of the per-point records just written
-            rc = launch_cull_summary(pq, stream);
-            if (rc) return rc;
-        }
+        if (!rc && pq.cull_points && pq.bsum) rc = launch_cull_summary(pq, stream);      // block summaries of the records just written
+        if (rc) return rc;
     }
-    if (!(phases & 2) || !want_value) return rc;
-    unsigned grid = (unsigned)device_cus();      // persistent: one 1024-thread workgroup per CU
-    grid -= grid % 8;                            // multiple of the XCD count: item % M stays put
-    if (owner_route) {
+    if (!(k.bwd_phases & 2) || !want_value) return rc;
+    const unsigned grid = persistent_grid();
+    if (sc.route == ScatterPlan::kOwner) {
         // owner-computes scatter: no float atomics; pixels outside its bands are zero-filled first
-        // When every level's row fits a band (the host copy of the shapes says so) no pixel takes the float-atomic branch, and the
-        // zero-fill of the pixels outside the levels -- normally none -- rides in the scatter kernel's prologue (bit 512) instead of
-        // a launch of its own in front of it: one dependent dispatch less per backward (one clip from a HIP graph 0.127 -> see r04 logs)
-        bool fused_zero = p.shapes_host != nullptr && (knobs().scatter_dbg & 1024) == 0;
-        for (int l = 0; fused_zero && l < p.L; ++l) fused_zero = p.shapes_host[2 * l + 1] > 0 && p.shapes_host[2 * l + 1] <= kOwnPix;
-        if (!fused_zero) {
+        if (!sc.fused_zero) {
             rc = launch_zero_unowned(p, kOwnPix * p.D, p.gv_storage ? 2 : 4, stream);
             if (rc) return rc;
         }
         Params pg = p;
-        if (l0 < p.L) pg.own_levels = l0;
-        pg.rec_mask = rec_mask;
-        if (!(mfma_tiles && knobs().scatter_part == 2))
-            rc = launch_scatter_grp(dtype, p.gv_storage != 0, pg, grid * (1024 / kOwnThreads), (knobs().scatter_dbg & (511 | 2048 | 4096)) | (fused_zero ? 512 : 0), stream);
-        if (rc || !mfma_tiles || knobs().scatter_part == 1) return rc;
-        return launch_scatter_mfma(dtype, p.gv_storage != 0, p, l0, mfma_tiles, stream);
+        pg.own_levels = sc.l0;
+        pg.rec_mask = sc.rec_mask;
+        if (sc.run_owner)
+            rc = launch_scatter_grp(dtype, p.gv_storage != 0, pg, grid * (1024 / kOwnThreads), (k.scatter_dbg & (511 | 4096)) | (sc.fused_zero ? 512 : 0),
+                                    sc.image_order, stream);
+        if (rc || !sc.run_mfma) return rc;
+        return launch_scatter_mfma(dtype, p.gv_storage != 0, p, sc.l0, sc.mfma_tiles, stream);
     }
-    if (p.gv_storage) return fail(MSDA_ERR_ARG, "msda backward: this call needs grad_value in the arithmetic type (see msda_grad_value_dtype)%s");
     // LDS-atomic scatter: 144 KiB of 8-byte accumulators per workgroup
-    const int cap_bytes = knobs().scatter_lds_kb * 1024;
+    const int cap_bytes = k.scatter_lds_kb * 1024;
     rc = launch_zero_unowned(p, cap_bytes / 8, 4, stream);
     if (rc) return rc;
-    return launch_scatter_lds(dtype, p.D / 4, p, grid, cap_bytes, knobs().scatter_dbg, stream);      // 4 channels per lane
+    return launch_scatter_lds(dtype, p.D / 4, p, grid, cap_bytes, k.scatter_dbg, stream);      // 4 channels per lane
 }
 
 // Shapes the 16-byte-lane kernels take: D a multiple of the lane vector with 64 / G rows per wave, aligned bases,
 // 32-bit element offsets inside a clip.
-bool fast_path_takes(int dtype, const Params &p, bool bwd)
+bool fast_path_takes(int dtype, const Params &p, const Knobs &k, bool bwd)
 {
     if (dtype == MSDA_F64) return false;
     const int esz = elem_bytes(dtype), VEC = 16 / esz;
@@ -765,29 +870,32 @@ bool fast_path_takes(int dtype, const Params &p, bool bwd)
         return false;
     if (p.v_clip % VEC || p.v_head % VEC || p.v_pix % VEC) return false;
     // the one-kernel backward scatters grad_value (always dense) at value's offsets
-    if (bwd && !scatter_applicable(p) && !standard_value_layout(p)) return false;
+    if (bwd && !scatter_applicable(p, k) && !standard_value_layout(p)) return false;
     if (tile_lds_bytes(kWave / G, p.LA + p.LB, bwd) > 60 * 1024) return false;
     return true;
 }
 
-int run(int dtype, const Params &p_in, bool bwd, hipStream_t stream, int grads = kGradAll)
+int run(int dtype, const Params &p_in, const Knobs &k, bool bwd, hipStream_t stream, int grads = kGradAll)
 {
     if (dtype < MSDA_F32 || dtype > MSDA_F16_LOC32) return fail(MSDA_ERR_DTYPE, "msda: unknown dtype code%s");
     Params p = p_in;
     p.own_levels = p.L;
     p.rec_mask = ~0u;
-    const RouteScope pinned(bwd, dtype, p);     // (the pinned settings of this call shape, if any, are what knobs() answers below)
-    p.dbg = knobs().dbg;
+    p.dbg = k.dbg;
     // culling records per point (4 x int16) when the owner-computes scatter will read them; (min, max) intervals for the
     // LDS-atomic scatter (MSDA_BWD_CULL=2 forces them)
-    p.cull_points = bwd && p.bbox && knobs().bwd_cull != 2 && owner_scatter_applicable(p, elem_bytes(dtype));
+    p.cull_points = bwd && p.bbox && k.bwd_cull != 2 && owner_scatter_applicable(p, elem_bytes(dtype), k);
     if (!p.cull_points) p.bsum = nullptr;
     p.wide_stores = bwd && aligned16(p.glocA) && aligned16(p.gawA) && (p.LB == 0 || (aligned16(p.glocB) && aligned16(p.gawB))) &&
-                    (knobs().dbg & 64) == 0;                  // (measurement: MSDA_DBG=64 keeps the narrow stores)
+                    (k.dbg & 64) == 0;                        // (measurement: MSDA_DBG=64 keeps the narrow stores)
     p.wide_loads = aligned16(p.locA) && aligned16(p.awA) && (p.LB == 0 || (aligned16(p.locB) && aligned16(p.awB))) &&
-                   (knobs().dbg & 128) == 0;                  // (measurement: MSDA_DBG=128 keeps the narrow loads)
+                   (k.dbg & 128) == 0;                        // (measurement: MSDA_DBG=128 keeps the narrow loads)
     if (p.groups == 0 || p.Lq == 0) return MSDA_OK;
-    if (!knobs().force_generic && fast_path_takes(dtype, p, bwd)) return launch_fast(dtype, p, bwd, stream, grads);
+    if (!k.force_generic && fast_path_takes(dtype, p, k, bwd)) {
+        Shape s;
+        if (const int rc = shape_of(dtype, p, bwd, s)) return rc;
+        return bwd ? launch_backward(dtype, p, k, s, stream, grads) : launch_forward(dtype, p, k, s, stream);
+    }
     if (p.gv_storage) return fail(MSDA_ERR_ARG, "msda backward: this call needs grad_value in the arithmetic type (see msda_grad_value_dtype)%s");
     return launch_generic(dtype, p, bwd, stream, grads);
 }
@@ -798,18 +906,38 @@ int set_grad_value_dtype(int dtype, int grad_value_dtype, Params &p)
     const int arith = dtype == MSDA_F64 ? MSDA_F64 : MSDA_F32;
     p.gv_storage = 0;
     if (grad_value_dtype == arith) return MSDA_OK;
-    if (grad_value_dtype != storage_dtype(dtype) || !storage_typed_grad_value_ok(dtype, p))
+    if (grad_value_dtype != storage_dtype(dtype) || !storage_typed_grad_value_ok(dtype, p, env_knobs()))
         return fail(MSDA_ERR_ARG, "msda backward: grad_value_dtype must be what msda_grad_value_dtype returns for this call%s");
     p.gv_storage = 1;
     return MSDA_OK;
 }
 
-int check_common(const void *value, const int64_t *shapes, const int64_t *lsi, int groups, int S,
-                 int M, int D, int L, int Lq)
+// The operator's inputs and sizes as Params.  The plain entry points are the temporal ones with frames = 1, window = 0 and no
+// frame table or temporal arrays (hence LB = 0, PB = 1).
+Params op_params(const void *value, const int64_t *shapes, const int64_t *lsi, const int32_t *ftab, const void *locA,
+                 const void *awA, const void *locB, const void *awB, int clips, int frames, int window, int S, int M, int D,
+                 int L, int Lq, int Pc, int Pt, const int64_t *shapes_host)
 {
-    if (!value || !shapes || !lsi) return fail(MSDA_ERR_ARG, "msda: null pointer argument%s");
-    if (groups < 0 || Lq < 0 || S <= 0 || M <= 0 || D <= 0 || L <= 0)
+    Params p;
+    memset(&p, 0, sizeof(p));
+    p.value = value; p.shapes = shapes; p.lsi = lsi; p.ftab = ftab;
+    p.locA = locA; p.awA = awA; p.locB = locB; p.awB = awB;
+    p.groups = clips * frames; p.frames = frames; p.window = window;
+    p.S = S; p.M = M; p.D = D; p.L = L; p.Lq = Lq;
+    p.LA = L; p.PA = Pc; p.LB = window * L; p.PB = window > 0 ? Pt : 1;
+    p.shapes_host = shapes_host;
+    return p;
+}
+
+// The checks of the forward and backward entry points in front of their empty-call test.  `fn` names the entry point in the
+// messages; the plain ones take any frames / window / points here (theirs are fixed, num_point is checked with the pointers).
+int check_sizes(const char *fn, bool temporal, const Params &p, int clips)
+{
+    if (!p.value || !p.shapes || !p.lsi) return fail(MSDA_ERR_ARG, "msda: null pointer argument%s");
+    if (clips < 0 || p.Lq < 0 || p.S <= 0 || p.M <= 0 || p.D <= 0 || p.L <= 0)
         return fail(MSDA_ERR_ARG, "msda: sizes must be positive%s");
+    if (temporal && (p.frames <= 0 || p.window < 0 || p.PA <= 0 || (p.window > 0 && p.PB <= 0)))
+        return fail(MSDA_ERR_ARG, "%s: bad frames/window/points", fn);
     return MSDA_OK;
 }
 
@@ -822,16 +950,6 @@ int set_value_strides(Params &p, const int64_t *vs)
     if (vs[0] < 0 || vs[1] < 0 || vs[2] <= 0 || vs[2] > 0x7fffffffLL)
         return fail(MSDA_ERR_ARG, "msda: bad value_strides%s");
     p.v_clip = vs[0]; p.v_head = vs[1]; p.v_pix = (int)vs[2];
-    return MSDA_OK;
-}
-
-int zero_grad_value(int grad_value_dtype, void *grad_value, int groups, int S, int M, int D, void *stream)
-{
-    if (grad_value_dtype < MSDA_F32 || grad_value_dtype > MSDA_F16) return fail(MSDA_ERR_DTYPE, "msda: unknown dtype code%s");
-    if (!grad_value) return fail(MSDA_ERR_ARG, "msda backward: null grad_value%s");
-    const size_t bytes = (size_t)groups * S * M * D * (size_t)elem_bytes(grad_value_dtype);
-    if (hipMemsetAsync(grad_value, 0, bytes, static_cast<hipStream_t>(stream)) != hipSuccess)
-        return fail(MSDA_ERR_HIP, "msda backward: hipMemsetAsync(grad_value) failed%s");
     return MSDA_OK;
 }
 
@@ -848,12 +966,13 @@ long long workspace_need(int batch, int num_query, int num_heads, int virtual_le
            (long long)batch * num_heads * virtual_levels * nblk * 8;
 }
 
-void attach_workspace(Params &p, void *workspace, long long bytes, int batch, int num_query, int num_heads, int vl)
+void attach_workspace(Params &p, const Knobs &k, void *workspace, long long bytes)
 {
+    const int batch = p.groups, num_query = p.Lq, num_heads = p.M, vl = p.LA + p.LB;
     p.workspace = (workspace && bytes >= MSDA_BWD_WORKSPACE_BYTES) ? static_cast<unsigned *>(workspace) : nullptr;
     p.bbox = nullptr;
     p.bsum = nullptr;
-    if (p.workspace && bytes >= workspace_need(batch, num_query, num_heads, vl) && knobs().bwd_cull != 0) {
+    if (p.workspace && bytes >= workspace_need(batch, num_query, num_heads, vl) && k.bwd_cull != 0) {
         p.bbox = reinterpret_cast<int *>(p.workspace) + MSDA_BWD_WORKSPACE_BYTES / 4;
         // block summaries only pay for long candidate ranges (and index (group, head, level) rows with 32 bits)
         if (num_query >= 2048 && (long long)batch * num_heads * vl < 0x7fffffffLL)
@@ -867,7 +986,7 @@ void attach_workspace(Params &p, void *workspace, long long bytes, int batch, in
 // grad_loc differs in the last bits when the queries are permuted).  grad_value: maxima, then route (b) -- the LDS-band
 // scatter with int64 bands, for fp32 / 16-bit calls the LDS scatter takes -- or route (a), the any-shape int64-atomic
 // scatter; both give the same bits (msda_det.h).  MSDA_DET_ROUTE (hooks) forces one: 1 = (a), 2 = (b).
-int run_det(int dtype, const Params &p_in, void *workspace, long long workspace_bytes, hipStream_t stream, int grads)
+int run_det(int dtype, const Params &p_in, const Knobs &k, void *workspace, long long workspace_bytes, hipStream_t stream, int grads)
 {
     if (dtype < MSDA_F32 || dtype > MSDA_F16_LOC32) return fail(MSDA_ERR_DTYPE, "msda: unknown dtype code%s");
     const long long need = det_workspace_bytes(p_in.groups / p_in.frames, p_in.frames, p_in.S, p_in.M, p_in.D);
@@ -877,35 +996,77 @@ int run_det(int dtype, const Params &p_in, void *workspace, long long workspace_
     p.workspace = nullptr; p.bbox = nullptr; p.bsum = nullptr;          // no tickets (static item stride), no culling records
     p.own_levels = p.L; p.rec_mask = 0; p.cull_points = 0;
     if (p.groups == 0 || p.Lq == 0) return MSDA_OK;
-    const bool band_ok = dtype != MSDA_F64 && scatter_applicable(p);
-    const int route = knobs().det_route;
-    if (route == 2 && !band_ok) return fail(MSDA_ERR_ARG, "msda backward: MSDA_DET_ROUTE=2 (LDS bands) does not take this call%s");
+    const bool band_ok = dtype != MSDA_F64 && scatter_applicable(p, k);
+    if (k.det_route == 2 && !band_ok) return fail(MSDA_ERR_ARG, "msda backward: MSDA_DET_ROUTE=2 (LDS bands) does not take this call%s");
+    int rc = MSDA_OK;
     if (grads & kGradSampling) {
         Params ps = p;
         ps.grad_value = nullptr; ps.gv_storage = 0;
-        int rc;
-        if (!knobs().force_generic && fast_path_takes(dtype, ps, true)) {
-            const int esz = elem_bytes(dtype), G = p.D / (16 / esz), RPW = kWave / G;
-            const int64_t blocks = (int64_t)p.groups * ((p.Lq + RPW - 1) / RPW) * p.M;
-            if (blocks > 0x7fffffffLL) return fail(MSDA_ERR_ARG, "msda: problem too large for one launch%s");
-            rc = launch_bwd_tile(dtype, G, false, ps, (unsigned)blocks, tile_lds_bytes(RPW, p.LA + p.LB, true), stream);
+        if (!k.force_generic && fast_path_takes(dtype, ps, k, true)) {
+            Shape s;                    // (p.bbox is null: the tile kernel's LDS without interval records)
+            rc = shape_of(dtype, p, true, s);
+            if (!rc) rc = launch_bwd_tile(dtype, s.G, false, ps, s.blocks, s.tile_lds, stream);
         } else {
             rc = launch_generic(dtype, ps, true, stream, kGradSampling);
         }
         if (rc) return rc;
     }
     DetArgs d;
-    int rc = launch_det_prepare(dtype, p, workspace, d, stream);
+    rc = launch_det_prepare(dtype, p, workspace, d, stream);
     if (rc) return rc;
-    if (band_ok && route != 1) {
-        unsigned grid = (unsigned)device_cus();      // persistent: one 1024-thread workgroup per CU
-        grid -= grid % 8;
-        rc = launch_scatter_lds_det(dtype, p.D / 4, p, grid, knobs().scatter_lds_kb * 1024, d, stream);
+    if (band_ok && k.det_route != 1) {
+        rc = launch_scatter_lds_det(dtype, p.D / 4, p, persistent_grid(), k.scatter_lds_kb * 1024, d, stream);
     } else {
         rc = launch_det_scatter_any(dtype, p, d, stream);
     }
     if (rc) return rc;
     return launch_det_convert(dtype, p, d, stream);
+}
+
+// The forward entry points; `temporal`: msda_temporal_forward (see check_sizes).
+int forward(const char *fn, bool temporal, int dtype, Params p, int clips, void *out, const int64_t *value_strides, void *stream)
+{
+    g_err[0] = 0; g_route[0] = 0;
+    int rc = check_sizes(fn, temporal, p, clips);
+    if (rc) return rc;
+    if (clips == 0 || p.Lq == 0) return MSDA_OK;
+    if (!p.locA || !p.awA || !out || p.PA <= 0 || (p.window > 0 && (!p.ftab || !p.locB || !p.awB)))
+        return fail(MSDA_ERR_ARG, temporal ? "%s: null pointer argument" : "%s: null pointer or non-positive num_point", fn);
+    p.out = out;
+    rc = set_value_strides(p, value_strides);
+    if (rc) return rc;
+    return run(dtype, p, call_knobs(false, dtype, p), false, static_cast<hipStream_t>(stream));
+}
+
+// The backward entry points; `grad_locB` / `grad_awB`: the temporal arrays' gradients (null for the plain ones).
+int backward(const char *fn, bool temporal, int grads, int dtype, Params p, int clips, const void *grad_out, void *grad_value,
+             int grad_value_dtype, void *grad_locA, void *grad_awA, void *grad_locB, void *grad_awB, void *workspace,
+             long long workspace_bytes, const int64_t *value_strides, void *stream)
+{
+    g_err[0] = 0; g_route[0] = 0;
+    if ((grads & ~(kGradAll | kGradDet)) || ((grads & kGradDet) && !(grads & kGradValue)))
+        return fail(MSDA_ERR_ARG, "msda backward: grads must be a mask of MSDA_GRAD_VALUE and MSDA_GRAD_SAMPLING (MSDA_GRAD_DETERMINISTIC only with MSDA_GRAD_VALUE)%s");
+    const bool det = (grads & kGradDet) != 0;
+    grads &= kGradAll;
+    if (grads == 0) return MSDA_OK;
+    const bool want_value = (grads & kGradValue) != 0, want_sampling = (grads & kGradSampling) != 0;
+    int rc = check_sizes(fn, temporal, p, clips);
+    if (rc) return rc;
+    if (clips == 0) return MSDA_OK;
+    if (p.Lq == 0) return want_value ? zero_grad_value(grad_value_dtype, grad_value, p.groups, p.S, p.M, p.D, stream) : MSDA_OK;
+    if (!p.locA || !p.awA || !grad_out || (want_value && !grad_value) || (want_sampling && (!grad_locA || !grad_awA)) || p.PA <= 0 ||
+        (p.window > 0 && (!p.ftab || !p.locB || !p.awB || (want_sampling && (!grad_locB || !grad_awB)))))
+        return fail(MSDA_ERR_ARG, temporal ? "%s: null pointer argument" : "%s: null pointer or non-positive num_point", fn);
+    p.grad_out = grad_out; p.grad_value = grad_value;
+    p.glocA = grad_locA; p.gawA = grad_awA; p.glocB = grad_locB; p.gawB = grad_awB;
+    const Knobs k = call_knobs(true, dtype, p);
+    attach_workspace(p, k, workspace, workspace_bytes);
+    rc = set_value_strides(p, value_strides);
+    if (rc) return rc;
+    rc = want_value ? set_grad_value_dtype(dtype, grad_value_dtype, p) : MSDA_OK;
+    if (rc) return rc;
+    if (det) return run_det(dtype, p, k, workspace, workspace_bytes, static_cast<hipStream_t>(stream), grads);
+    return run(dtype, p, k, true, static_cast<hipStream_t>(stream), grads);
 }
 
 int run_prep(int dtype, const PrepParams &p, bool bwd, void *stream)
@@ -938,11 +1099,8 @@ int msda_route_key(int backward, int dtype, int clips, int frames, int window, i
                    char *buf, int buf_len)
 {
     if (!buf || buf_len <= 0 || !spatial_shapes_host || clips <= 0 || frames <= 0) return fail(MSDA_ERR_ARG, "msda_route_key: bad arguments%s");
-    Params p;
-    memset(&p, 0, sizeof p);
-    p.groups = clips * frames; p.frames = frames; p.window = window; p.S = spatial_size; p.M = num_heads; p.D = channels;
-    p.L = num_levels; p.Lq = num_query; p.PA = num_curr_point; p.PB = window > 0 ? num_temp_point : 1;
-    p.shapes_host = spatial_shapes_host;
+    const Params p = op_params(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, clips, frames, window, spatial_size,
+                               num_heads, channels, num_levels, num_query, num_curr_point, num_temp_point, spatial_shapes_host);
     const int n = route_key(buf, buf_len, backward != 0, dtype, p);
     return n < 0 ? fail(MSDA_ERR_ARG, "msda_route_key: the key does not fit the buffer (or more than 16 levels)%s") : n;
 }
@@ -998,13 +1156,9 @@ int msda_grad_value_dtype(int dtype, int clips, int frames, int window, int spat
     if (clips <= 0 || frames <= 0 || window < 0 || spatial_size <= 0 || num_heads <= 0 || channels <= 0 || num_levels <= 0 ||
         num_query <= 0 || num_curr_point <= 0)
         return arith;
-    Params p;
-    memset(&p, 0, sizeof(p));
-    p.groups = clips * frames; p.frames = frames; p.window = window;
-    p.S = spatial_size; p.M = num_heads; p.D = channels; p.L = num_levels; p.Lq = num_query;
-    p.LA = num_levels; p.PA = num_curr_point; p.LB = window * num_levels; p.PB = window > 0 ? num_temp_point : 1;
-    p.shapes_host = spatial_shapes_host;
-    return storage_typed_grad_value_ok(dtype, p) ? storage_dtype(dtype) : arith;
+    const Params p = op_params(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, clips, frames, window, spatial_size,
+                               num_heads, channels, num_levels, num_query, num_curr_point, num_temp_point, spatial_shapes_host);
+    return storage_typed_grad_value_ok(dtype, p, env_knobs()) ? storage_dtype(dtype) : arith;
 }
 
 int msda_forward(int dtype, const void *value, const int64_t *spatial_shapes,
@@ -1013,24 +1167,10 @@ int msda_forward(int dtype, const void *value, const int64_t *spatial_shapes,
                  int num_query, int num_point, void *out, const int64_t *value_strides,
                  const int64_t *spatial_shapes_host, void *stream)
 {
-    g_err[0] = 0; g_route[0] = 0;
-    int rc = check_common(value, spatial_shapes, level_start_index, batch, spatial_size, num_heads,
-                          channels, num_levels, num_query);
-    if (rc) return rc;
-    if (batch == 0 || num_query == 0) return MSDA_OK;
-    if (!sampling_loc || !attn_weight || !out || num_point <= 0)
-        return fail(MSDA_ERR_ARG, "msda_forward: null pointer or non-positive num_point%s");
-    Params p;
-    memset(&p, 0, sizeof(p));
-    p.value = value; p.shapes = spatial_shapes; p.lsi = level_start_index;
-    p.locA = sampling_loc; p.awA = attn_weight; p.out = out;
-    p.groups = batch; p.frames = 1; p.window = 0;
-    p.S = spatial_size; p.M = num_heads; p.D = channels; p.L = num_levels; p.Lq = num_query;
-    p.LA = num_levels; p.PA = num_point; p.LB = 0; p.PB = 1;
-    p.shapes_host = spatial_shapes_host;
-    rc = set_value_strides(p, value_strides);
-    if (rc) return rc;
-    return run(dtype, p, false, static_cast<hipStream_t>(stream));
+    return forward("msda_forward", false, dtype,
+                   op_params(value, spatial_shapes, level_start_index, nullptr, sampling_loc, attn_weight, nullptr, nullptr, batch, 1,
+                             0, spatial_size, num_heads, channels, num_levels, num_query, num_point, 1, spatial_shapes_host),
+                   batch, out, value_strides, stream);
 }
 
 int msda_backward(int dtype, const void *value, const int64_t *spatial_shapes,
@@ -1057,38 +1197,11 @@ int msda_backward_grads(int grads, int dtype, const void *value, const int64_t *
                         void *workspace, long long workspace_bytes, const int64_t *value_strides,
                         const int64_t *spatial_shapes_host, void *stream)
 {
-    g_err[0] = 0; g_route[0] = 0;
-    if ((grads & ~(kGradAll | kGradDet)) || ((grads & kGradDet) && !(grads & kGradValue)))
-        return fail(MSDA_ERR_ARG, "msda backward: grads must be a mask of MSDA_GRAD_VALUE and MSDA_GRAD_SAMPLING (MSDA_GRAD_DETERMINISTIC only with MSDA_GRAD_VALUE)%s");
-    const bool det = (grads & kGradDet) != 0;
-    grads &= kGradAll;
-    if (grads == 0) return MSDA_OK;
-    const bool want_value = (grads & kGradValue) != 0, want_sampling = (grads & kGradSampling) != 0;
-    int rc = check_common(value, spatial_shapes, level_start_index, batch, spatial_size, num_heads,
-                          channels, num_levels, num_query);
-    if (rc) return rc;
-    if (batch == 0) return MSDA_OK;
-    if (num_query == 0)
-        return want_value ? zero_grad_value(grad_value_dtype, grad_value, batch, spatial_size, num_heads, channels, stream) : MSDA_OK;
-    if (!sampling_loc || !attn_weight || !grad_out || (want_value && !grad_value) ||
-        (want_sampling && (!grad_sampling_loc || !grad_attn_weight)) || num_point <= 0)
-        return fail(MSDA_ERR_ARG, "msda_backward: null pointer or non-positive num_point%s");
-    Params p;
-    memset(&p, 0, sizeof(p));
-    p.value = value; p.shapes = spatial_shapes; p.lsi = level_start_index;
-    p.locA = sampling_loc; p.awA = attn_weight; p.grad_out = grad_out;
-    p.grad_value = grad_value; p.glocA = grad_sampling_loc; p.gawA = grad_attn_weight;
-    attach_workspace(p, workspace, workspace_bytes, batch, num_query, num_heads, num_levels);
-    p.groups = batch; p.frames = 1; p.window = 0;
-    p.S = spatial_size; p.M = num_heads; p.D = channels; p.L = num_levels; p.Lq = num_query;
-    p.LA = num_levels; p.PA = num_point; p.LB = 0; p.PB = 1;
-    p.shapes_host = spatial_shapes_host;
-    rc = set_value_strides(p, value_strides);
-    if (rc) return rc;
-    rc = want_value ? set_grad_value_dtype(dtype, grad_value_dtype, p) : MSDA_OK;
-    if (rc) return rc;
-    if (det) return run_det(dtype, p, workspace, workspace_bytes, static_cast<hipStream_t>(stream), grads);
-    return run(dtype, p, true, static_cast<hipStream_t>(stream), grads);
+    return backward("msda_backward", false, grads, dtype,
+                    op_params(value, spatial_shapes, level_start_index, nullptr, sampling_loc, attn_weight, nullptr, nullptr, batch, 1,
+                              0, spatial_size, num_heads, channels, num_levels, num_query, num_point, 1, spatial_shapes_host),
+                    batch, grad_out, grad_value, grad_value_dtype, grad_sampling_loc, grad_attn_weight, nullptr, nullptr, workspace,
+                    workspace_bytes, value_strides, stream);
 }
 
 int msda_temporal_forward(int dtype, const void *value, const int64_t *spatial_shapes,
@@ -1100,27 +1213,11 @@ int msda_temporal_forward(int dtype, const void *value, const int64_t *spatial_s
                           int num_curr_point, int num_temp_point, void *out, const int64_t *value_strides,
                           const int64_t *spatial_shapes_host, void *stream)
 {
-    g_err[0] = 0; g_route[0] = 0;
-    int rc = check_common(value, spatial_shapes, level_start_index, clips, spatial_size, num_heads,
-                          channels, num_levels, num_query);
-    if (rc) return rc;
-    if (frames <= 0 || window < 0 || num_curr_point <= 0 || (window > 0 && num_temp_point <= 0))
-        return fail(MSDA_ERR_ARG, "msda_temporal_forward: bad frames/window/points%s");
-    if (clips == 0 || num_query == 0) return MSDA_OK;
-    if (!loc_curr || !aw_curr || !out || (window > 0 && (!frame_table || !loc_temp || !aw_temp)))
-        return fail(MSDA_ERR_ARG, "msda_temporal_forward: null pointer argument%s");
-    Params p;
-    memset(&p, 0, sizeof(p));
-    p.value = value; p.shapes = spatial_shapes; p.lsi = level_start_index; p.ftab = frame_table;
-    p.locA = loc_curr; p.awA = aw_curr; p.locB = loc_temp; p.awB = aw_temp; p.out = out;
-    p.groups = clips * frames; p.frames = frames; p.window = window;
-    p.S = spatial_size; p.M = num_heads; p.D = channels; p.L = num_levels; p.Lq = num_query;
-    p.LA = num_levels; p.PA = num_curr_point;
-    p.LB = window * num_levels; p.PB = window > 0 ? num_temp_point : 1;
-    p.shapes_host = spatial_shapes_host;
-    rc = set_value_strides(p, value_strides);
-    if (rc) return rc;
-    return run(dtype, p, false, static_cast<hipStream_t>(stream));
+    return forward("msda_temporal_forward", true, dtype,
+                   op_params(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, loc_temp, aw_temp, clips, frames,
+                             window, spatial_size, num_heads, channels, num_levels, num_query, num_curr_point, num_temp_point,
+                             spatial_shapes_host),
+                   clips, out, value_strides, stream);
 }
 
 int msda_temporal_backward(int dtype, const void *value, const int64_t *spatial_shapes,
@@ -1152,43 +1249,12 @@ int msda_temporal_backward_grads(int grads, int dtype, const void *value, const 
                                  void *grad_loc_temp, void *grad_aw_temp, void *workspace, long long workspace_bytes,
                                  const int64_t *value_strides, const int64_t *spatial_shapes_host, void *stream)
 {
-    g_err[0] = 0; g_route[0] = 0;
-    if ((grads & ~(kGradAll | kGradDet)) || ((grads & kGradDet) && !(grads & kGradValue)))
-        return fail(MSDA_ERR_ARG, "msda backward: grads must be a mask of MSDA_GRAD_VALUE and MSDA_GRAD_SAMPLING (MSDA_GRAD_DETERMINISTIC only with MSDA_GRAD_VALUE)%s");
-    const bool det = (grads & kGradDet) != 0;
-    grads &= kGradAll;
-    if (grads == 0) return MSDA_OK;
-    const bool want_value = (grads & kGradValue) != 0, want_sampling = (grads & kGradSampling) != 0;
-    int rc = check_common(value, spatial_shapes, level_start_index, clips, spatial_size, num_heads,
-                          channels, num_levels, num_query);
-    if (rc) return rc;
-    if (frames <= 0 || window < 0 || num_curr_point <= 0 || (window > 0 && num_temp_point <= 0))
-        return fail(MSDA_ERR_ARG, "msda_temporal_backward: bad frames/window/points%s");
-    if (clips == 0) return MSDA_OK;
-    if (num_query == 0)
-        return want_value ? zero_grad_value(grad_value_dtype, grad_value, clips * frames, spatial_size, num_heads, channels, stream)
-                          : MSDA_OK;
-    if (!loc_curr || !aw_curr || !grad_out || (want_value && !grad_value) || (want_sampling && (!grad_loc_curr || !grad_aw_curr)) ||
-        (window > 0 && (!frame_table || !loc_temp || !aw_temp || (want_sampling && (!grad_loc_temp || !grad_aw_temp)))))
-        return fail(MSDA_ERR_ARG, "msda_temporal_backward: null pointer argument%s");
-    Params p;
-    memset(&p, 0, sizeof(p));
-    p.value = value; p.shapes = spatial_shapes; p.lsi = level_start_index; p.ftab = frame_table;
-    p.locA = loc_curr; p.awA = aw_curr; p.locB = loc_temp; p.awB = aw_temp; p.grad_out = grad_out;
-    p.grad_value = grad_value; p.glocA = grad_loc_curr; p.gawA = grad_aw_curr;
-    p.glocB = grad_loc_temp; p.gawB = grad_aw_temp;
-    attach_workspace(p, workspace, workspace_bytes, clips * frames, num_query, num_heads, num_levels * (1 + window));
-    p.groups = clips * frames; p.frames = frames; p.window = window;
-    p.S = spatial_size; p.M = num_heads; p.D = channels; p.L = num_levels; p.Lq = num_query;
-    p.LA = num_levels; p.PA = num_curr_point;
-    p.LB = window * num_levels; p.PB = window > 0 ? num_temp_point : 1;
-    p.shapes_host = spatial_shapes_host;
-    rc = set_value_strides(p, value_strides);
-    if (rc) return rc;
-    rc = want_value ? set_grad_value_dtype(dtype, grad_value_dtype, p) : MSDA_OK;
-    if (rc) return rc;
-    if (det) return run_det(dtype, p, workspace, workspace_bytes, static_cast<hipStream_t>(stream), grads);
-    return run(dtype, p, true, static_cast<hipStream_t>(stream), grads);
+    return backward("msda_temporal_backward", true, grads, dtype,
+                    op_params(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, loc_temp, aw_temp, clips, frames,
+                              window, spatial_size, num_heads, channels, num_levels, num_query, num_curr_point, num_temp_point,
+                              spatial_shapes_host),
+                    clips, grad_out, grad_value, grad_value_dtype, grad_loc_curr, grad_aw_curr, grad_loc_temp, grad_aw_temp, workspace,
+                    workspace_bytes, value_strides, stream);
 }
 
 int msda_prep_forward(int dtype, const void *offsets_curr, const void *offsets_temp, const void *logits_curr,

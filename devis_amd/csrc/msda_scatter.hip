@@ -1271,32 +1271,16 @@ int launch_scatter_lds_det(int dtype, int G, const Params &p, unsigned grid, int
     });
 }
 
-int launch_scatter_grp(int dtype, bool storage_typed, const Params &p, unsigned grid, int dbg, hipStream_t stream)
+// `image_order`: the items in image order (the dispatcher's rule, msda_api.hip owner_image_order), else heaviest first
+int launch_scatter_grp(int dtype, bool storage_typed, const Params &p, unsigned grid, int dbg, bool image_order, hipStream_t stream)
 {
     return dispatch_types(dtype, [&](auto t, auto tl) {
         using T = typename decltype(t)::type;
         using TL = typename decltype(tl)::type;
-        // items in image order for long candidate ranges of a TEMPORAL call (the encoder's fused call: the frames of one band
-        // run side by side and share the rows and points of the queries near it), when the host knows the band count
-        // (MSDA_SCATTER_DBG = 256: the level-by-level order).  Plain calls keep the heaviest-first order: measured on one box,
-        // image order / level order: 800x1333 T = 6 one clip 2.76 / 2.86 ms, 360x640 T = 6 0.54 / 0.55, but the single-frame
-        // encoder call of BASELINE configs[1] (N = 8, bf16) 0.92 / 0.63 and the SwinL one (N = 6, fp16) 0.23 / 0.17 -- with
-        // `clip` outermost the batch is 8 serial tails.
-        // (round 4, after the per-item fixed costs shrank: at 360x640, Lq = 4820, image order is now the slower one, 0.555 / 0.529)
-        // (a pinned route, msda_pin_route scatter_order: 1 = level order (bit 256), 2 = image order wherever the bands can be sorted (bit 2048))
-        bool sorted = ((p.Lq >= 8192 && p.frames > 1) || (dbg & 2048)) && p.shapes_host != nullptr && (dbg & 256) == 0;
-        int bands = 0;
-        for (int l = 0; sorted && l < p.own_levels; ++l) {
-            const long long H = p.shapes_host[2 * l], W = p.shapes_host[2 * l + 1];
-            if (H <= 0 || W <= 0) { sorted = false; break; }         // (degenerate level: the device counts its bands differently)
-            const long long R = W > 0 ? std::min<long long>(H, kOwnPix / W) : 0;
-            bands += R > 0 ? (int)((H + R - 1) / R) : 1;
-        }
-        sorted = sorted && bands <= kOwnMaxSorted;
         if constexpr (sizeof(T) == 2) {
-            if (storage_typed) return sorted ? scatter_grp<T, TL, T, true>(p, grid, dbg, stream) : scatter_grp<T, TL, T, false>(p, grid, dbg, stream);
+            if (storage_typed) return image_order ? scatter_grp<T, TL, T, true>(p, grid, dbg, stream) : scatter_grp<T, TL, T, false>(p, grid, dbg, stream);
         }
-        return sorted ? scatter_grp<T, TL, float, true>(p, grid, dbg, stream) : scatter_grp<T, TL, float, false>(p, grid, dbg, stream);
+        return image_order ? scatter_grp<T, TL, float, true>(p, grid, dbg, stream) : scatter_grp<T, TL, float, false>(p, grid, dbg, stream);
     });
 }
 

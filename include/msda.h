@@ -16,8 +16,8 @@
  *     they never allocate and never synchronise, and are re-entrant (forward on the Python thread,
  *     backward on an autograd worker -- as in the reference).  The only process-wide state is caches
  *     keyed by HIP device id (compute-unit count, per-kernel LDS opt-in) and the test knobs below;
- *   - test / measurement knobs are environment variables (MSDA_FWD_SLAB, MSDA_BWD_MODE, ...; listed in
- *     devis_amd/csrc/msda_api.hip at `struct Knobs`).  They are IGNORED unless MSDA_ENABLE_HOOKS=1, and
+ *   - test / measurement knobs are environment variables (MSDA_FWD_RS, MSDA_BWD_MODE, ...; listed in
+ *     devis_amd/csrc/msda_api.hip in the table `kKnobs`).  They are IGNORED unless MSDA_ENABLE_HOOKS=1, and
  *     are read once -- at the first call or when msda_reload_knobs() is called -- never on the launch path;
  *   - return value: MSDA_OK (0) or a negative msda_status; on failure msda_last_error() returns a
  *     thread-local message.  Unlike the reference (errors only printf'd,
@@ -108,7 +108,7 @@ const char *msda_last_route(void);
 /*
  * Measured route table (ABI v12).  Which kernel family serves a call (tile / resident-slab / resident-window), with how many
  * tiles per wave, on which grid, and in which order the scatter deals its items is chosen from the call's sizes by rules
- * calibrated on a few pyramids (devis_amd/csrc/msda_api.hip, launch_fast).  A caller that has TIMED the
+ * calibrated on a few pyramids (devis_amd/csrc/msda_api.hip, plan_*).  A caller that has TIMED the
  * alternatives for a call shape pins the winner: from then on every call of that shape (any thread) takes it.  The reference
  * has nothing like it (one kernel per direction, ms_deform_attn_cuda.cu:61-75, 121-153); results never depend on a pin.
  *
