@@ -1,11 +1,14 @@
-"""devis_amd -- MI355X-native (gfx950 / CDNA4) multi-scale deformable attention for DeVIS.
+"""devis_amd -- MI355X-native (gfx950 / CDNA4) multi-scale deformable attention and deformable convolution for DeVIS.
 
-A from-scratch replacement for DeVIS's only native component, ``src/models/ops`` (the vendored
+A from-scratch replacement for DeVIS's native components: ``src/models/ops`` (the vendored
 Deformable-DETR CUDA extension ``MultiScaleDeformableAttention`` plus its Python wrappers), behind the
 same Python surface::
 
     from devis_amd.functions import MSDeformAttnFunction, ms_deform_attn_core_pytorch
     from devis_amd.modules import MSDeformAttn, TemporalMSDeformAttnEncoder, TemporalMSDeformAttnDecoder
+
+and the mask head's ``torchvision.ops.deform_conv2d`` (``devis_amd.deform_conv2d``, same signature; the module
+``devis_amd.modules.ModulatedDeformableConv2d``; C ABI ``include/mdcn.h``).
 
 Arithmetic lives in hand-written HIP kernels behind the C ABI of ``include/msda.h``
 (``devis_amd/csrc/*.hip``, one translation unit per kernel family -> ``devis_amd/libmsda_hip.so``); the Python here is the host side.
@@ -15,12 +18,13 @@ CPU tensors, and it raises if the HIP library cannot be loaded.
 """
 from .functions import (MSDeformAttnFunction, MSDeformAttnTemporalFunction,  # noqa: F401
                         ms_deform_attn_core_pytorch)
-from .modules import (MSDeformAttn, TemporalMSDeformAttnDecoder,  # noqa: F401
+from .modules import (ModulatedDeformableConv2d, MSDeformAttn, TemporalMSDeformAttnDecoder,  # noqa: F401
                       TemporalMSDeformAttnEncoder)
 from . import ops  # noqa: F401  (the operator as torch.library custom ops: torch.compile / torch.export)
-from .argument_builders import patch_transformer  # noqa: F401
+from .ops import deform_conv2d  # noqa: F401
+from .argument_builders import patch_mask_head, patch_transformer  # noqa: F401
 from .graphs import graphed, graph_stream, GraphedLayer  # noqa: F401
 from .tuning import tune  # noqa: F401
 
 __all__ = ["MSDeformAttnFunction", "MSDeformAttnTemporalFunction", "ms_deform_attn_core_pytorch",
-           "MSDeformAttn", "TemporalMSDeformAttnEncoder", "TemporalMSDeformAttnDecoder", "ops", "patch_transformer", "graphed", "graph_stream", "GraphedLayer", "tune"]
+           "MSDeformAttn", "TemporalMSDeformAttnEncoder", "TemporalMSDeformAttnDecoder", "ModulatedDeformableConv2d", "deform_conv2d", "ops", "patch_transformer", "patch_mask_head", "graphed", "graph_stream", "GraphedLayer", "tune"]

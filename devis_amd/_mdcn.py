@@ -1,0 +1,96 @@
+"""ctypes binding of include/mdcn.h: the deformable-convolution entry points of libmsda_hip.so (the library ``_native.load()``
+opens).  As in ``_native``: no fallback, a failing call raises, launches go to the current stream, and the library neither
+allocates nor synchronises -- the column buffers are torch tensors of the caller.
+"""
+import ctypes
+import threading
+
+import torch
+
+from . import _native
+
+MDCN_ABI_VERSION = 1
+GRAD_INPUT, GRAD_SAMPLING = 1, 2        # include/mdcn.h MDCN_GRAD_INPUT / MDCN_GRAD_SAMPLING
+# every symbol include/mdcn.h declares (tests check the library exports each of them)
+EXPORTED_SYMBOLS = ("mdcn_version", "mdcn_last_error", "mdcn_workspace_bytes", "mdcn_im2col", "mdcn_backward")
+_OFF32_CODE = {torch.bfloat16: 4, torch.float16: 5}     # MDCN_BF16_OFF32 / MDCN_F16_OFF32
+
+_vp, _ci = ctypes.c_void_p, ctypes.c_int
+_lib = None
+_lock = threading.Lock()
+
+
+class Shape(ctypes.Structure):
+    """include/mdcn.h ``mdcn_shape``."""
+    _fields_ = [(name, _ci) for name in ("N", "C", "H", "W", "Ho", "Wo", "Kh", "Kw", "stride_h", "stride_w", "pad_h", "pad_w",
+                                         "dil_h", "dil_w", "G")]
+
+
+def load():
+    """The library with the mdcn_* prototypes set; raises RuntimeError when it cannot be loaded or is another version."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    with _lock:
+        if _lib is not None:
+            return _lib
+        lib = _native.load()
+        for name in EXPORTED_SYMBOLS:
+            if not hasattr(lib, name):
+                raise RuntimeError("devis_amd: the HIP library does not export %s; rebuild with "
+                                   "python -m devis_amd.build --force" % name)
+        lib.mdcn_version.restype = _ci
+        lib.mdcn_last_error.restype = ctypes.c_char_p
+        if lib.mdcn_version() != MDCN_ABI_VERSION:
+            raise RuntimeError("devis_amd: mdcn ABI version mismatch (library %d, binding %d); rebuild with "
+                               "python -m devis_amd.build --force" % (lib.mdcn_version(), MDCN_ABI_VERSION))
+        shape_p = ctypes.POINTER(Shape)
+        lib.mdcn_workspace_bytes.restype = ctypes.c_longlong
+        lib.mdcn_workspace_bytes.argtypes = [_ci, shape_p, _ci]
+        lib.mdcn_im2col.restype = _ci
+        lib.mdcn_im2col.argtypes = [_ci, _vp, _vp, _vp, shape_p, _vp, _vp]
+        lib.mdcn_backward.restype = _ci
+        lib.mdcn_backward.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, shape_p, _vp, _vp, _vp, _vp]
+        _lib = lib
+    return _lib
+
+
+def _check(rc, what):
+    if rc < 0:
+        msg = load().mdcn_last_error().decode("utf-8", "replace")
+        raise RuntimeError("devis_amd: %s failed (status %d): %s" % (what, rc, msg))
+    return rc
+
+
+def type_code(dtype, offset_dtype):
+    """mdcn_dtype of a call whose input / columns are ``dtype`` and whose offset / mask are ``offset_dtype``: the same type,
+    or float32 beside a 16-bit input."""
+    if offset_dtype == dtype:
+        return _native.dtype_code(dtype)
+    if offset_dtype == torch.float32 and dtype in _OFF32_CODE:
+        return _OFF32_CODE[dtype]
+    raise RuntimeError("devis_amd: offset / mask must have input's dtype (or float32 beside a 16-bit input), got %s beside %s"
+                       % (offset_dtype, dtype))
+
+
+def workspace_bytes(code, shape, batch):
+    """Bytes of the column buffer of ``batch`` images (mdcn_workspace_bytes)."""
+    return _check(load().mdcn_workspace_bytes(code, ctypes.byref(shape), batch), "mdcn_workspace_bytes")
+
+
+def im2col(code, x_nhwc, offset, mask, shape, columns):
+    """mdcn_im2col on the current stream: ``x_nhwc`` [N, H, W, C], ``offset`` / ``mask`` (or None) NCHW -> ``columns``."""
+    with _native._on(x_nhwc.device):
+        rc = load().mdcn_im2col(code, _native._p(x_nhwc), _native._p(offset), _native._p(mask), ctypes.byref(shape),
+                                _native._p(columns), _native._stream(x_nhwc))
+    _check(rc, "mdcn_im2col")
+
+
+def backward(grads, code, x_nhwc, offset, mask, grad_columns, shape, grad_input_acc, grad_offset, grad_mask):
+    """mdcn_backward on the current stream for the gradient groups in ``grads``; outputs of a group that is not asked for
+    may be None.  ``grad_input_acc`` ([N, H, W, C] in the arithmetic type) is accumulated into."""
+    with _native._on(x_nhwc.device):
+        rc = load().mdcn_backward(grads, code, _native._p(x_nhwc), _native._p(offset), _native._p(mask),
+                                  _native._p(grad_columns), ctypes.byref(shape), _native._p(grad_input_acc),
+                                  _native._p(grad_offset), _native._p(grad_mask), _native._stream(x_nhwc))
+    _check(rc, "mdcn_backward")

@@ -184,3 +184,20 @@ def unpatch_transformer(deformable_transformer_module, previous_get_reference_po
         del top._devis_amd_prepare_data
     if devis_transformer_module is not None and isinstance(getattr(devis_transformer_module, "torch", None), _InterningTorch):
         devis_transformer_module.torch = devis_transformer_module.torch._real
+
+
+def patch_mask_head(deformable_segmentation_module):
+    """Opt-in: make the reference's mask head (``src.models.deformable_segmentation``) build its convolutions from
+    :class:`devis_amd.modules.ModulatedDeformableConv2d` -- the HIP operator instead of ``torchvision.ops.deform_conv2d``.  Call
+    it before the model is built: the mask head looks the class up by name when it is constructed; layers that already
+    exist keep their class.  State dicts are interchangeable (same parameter names).  Returns the replaced class (to undo
+    the patch; :func:`unpatch_mask_head`)."""
+    from .modules import ModulatedDeformableConv2d
+    previous = getattr(deformable_segmentation_module, "ModulatedDeformableConv2d")
+    deformable_segmentation_module.ModulatedDeformableConv2d = ModulatedDeformableConv2d
+    return previous
+
+
+def unpatch_mask_head(deformable_segmentation_module, previous_class):
+    """Undo :func:`patch_mask_head` (tests)."""
+    deformable_segmentation_module.ModulatedDeformableConv2d = previous_class

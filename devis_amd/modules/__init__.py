@@ -1,3 +1,4 @@
 # mirrors /root/reference/src/models/ops/modules/__init__.py:9 (same exported names)
 from .ms_deform_attn import (MSDeformAttn, TemporalMSDeformAttnBase,  # noqa: F401
                              TemporalMSDeformAttnDecoder, TemporalMSDeformAttnEncoder)
+from .deform_conv import ModulatedDeformableConv2d  # noqa: F401  (reference src/models/deformable_segmentation.py)

@@ -1,6 +1,6 @@
 """The operator as ``torch.library`` custom ops (namespace ``devis_amd``), for ``torch.compile`` and ``torch.export``.
 
-Eager code never dispatches through these: the autograd Functions of :mod:`devis_amd.functions` and the modules call the
+Eager attention code never dispatches through these (the deformable convolution, which has no other path, always does): the autograd Functions of :mod:`devis_amd.functions` and the modules call the
 host code directly and switch to the ops only while ``torch.compiler.is_compiling()`` (Dynamo tracing, or export).  To the
 compiler each op is one opaque node whose implementation is that same host code -- the same checks, the same kernels
 through the C ABI, the same numbers -- and whose fake implementation gives shapes and dtypes only:
@@ -14,6 +14,8 @@ through the C ABI, the same numbers -- and whose fake implementation gives shape
 ``prep_forward/backward``      ``MSDeformPrepFunction`` (no temporal part: ``loc_t`` / ``aw_t`` come back with 0 slots)
 ``prep_fused_forward/backward``  ``MSDeformPrepFusedFunction``
 ``frame_table``                the temporal modules' frame table ``[T, W]`` int32 (cache and deferred range checks)
+``deform_conv2d``              the mask head's modulated deformable convolution (:func:`deform_conv2d`, torchvision's
+                               signature); ``deform_conv2d_backward`` computes the gradients its ``grads`` mask names
 =============================  ==========================================================================================
 
 Everything that reads the host or keeps Python state -- the ``spatial_shapes`` host hint, the frame-table cache, the
@@ -33,6 +35,7 @@ import torch
 from torch import Tensor
 
 from . import _native
+from .functions import deform_conv as _D
 from .functions import ms_deform_attn_func as _F
 
 
@@ -412,3 +415,66 @@ def frame_table(offsets: List[Tensor], n_frames: int, device: torch.device) -> T
 def _(offsets, n_frames, device):
     _F._require(len(offsets) > 0, "frame_table needs the temporal offsets of at least one frame")
     return torch.empty((n_frames, offsets[0].shape[0]), dtype=torch.int32, device=device)
+
+
+# ---- modulated deformable convolution (include/mdcn.h) ---------------------------------------------------------------
+# Unlike the attention operator this one has a single path: eager calls dispatch through the op too.
+
+@_op("deform_conv2d")
+def deform_conv2d_op(input: Tensor, offset: Tensor, weight: Tensor, bias: Optional[Tensor], stride: List[int],
+                     padding: List[int], dilation: List[int], mask: Optional[Tensor]) -> Tensor:
+    """``deform_conv2d`` with pairs for stride / padding / dilation: [N, Co, Ho, Wo]."""
+    return _D._forward(input, offset, weight, bias, stride, padding, dilation, mask)
+
+
+@deform_conv2d_op.register_fake
+def _(input, offset, weight, bias, stride, padding, dilation, mask):
+    Ho, Wo, _ = _D.check_shapes(input, offset, weight, bias, stride, padding, dilation, mask)
+    return _empty(input, (input.shape[0], weight.shape[0], Ho, Wo))
+
+
+@_op("deform_conv2d_backward")
+def deform_conv2d_backward(grad_out: Tensor, input: Tensor, offset: Tensor, weight: Tensor, mask: Optional[Tensor],
+                           stride: List[int], padding: List[int], dilation: List[int], grads: int
+                           ) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(grad_input, grad_offset, grad_mask, grad_weight, grad_bias) for the gradients in ``grads`` (``NEED_*`` of
+    devis_amd/functions/deform_conv.py); the others are 0-element tensors."""
+    out = _D._backward(grad_out, input, offset, weight, mask, stride, padding, dilation, grads)
+    return _fill_slots(out, _fake_deform_conv2d_backward(grad_out, input, offset, weight, mask, stride, padding, dilation, grads))
+
+
+@deform_conv2d_backward.register_fake
+def _fake_deform_conv2d_backward(grad_out, input, offset, weight, mask, stride, padding, dilation, grads):
+    _D._require(0 <= grads <= _D.NEED_ALL, "grads must be a mask of the NEED_* bits")
+    has = lambda bit, t: t is not None and bool(grads & bit)    # noqa: E731
+    return (_empty(input, input.shape if has(_D.NEED_INPUT, input) else (0,)),
+            _empty(offset, offset.shape if has(_D.NEED_OFFSET, offset) else (0,)),
+            _empty(offset, mask.shape if has(_D.NEED_MASK, mask) else (0,)),
+            _empty(weight, weight.shape if has(_D.NEED_WEIGHT, weight) else (0,)),
+            _empty(weight, (weight.shape[0],) if grads & _D.NEED_BIAS else (0,)))
+
+
+def _setup_deform_conv2d(ctx, inputs, output):
+    input, offset, weight, bias, stride, padding, dilation, mask = inputs
+    ctx.geometry = (stride, padding, dilation)
+    ctx.save_for_backward(input, offset, weight, mask)
+
+
+def _backward_deform_conv2d(ctx, grad_out):
+    input, offset, weight, mask = ctx.saved_tensors
+    needs = ctx.needs_input_grad
+    grads = _D.grads_mask(needs[0], needs[1], needs[7] and mask is not None, needs[2], needs[3])
+    gi, go, gm, gw, gb = none_slots(deform_conv2d_backward(grad_out, input, offset, weight, mask, *ctx.geometry, grads))
+    return gi, go, gw, gb, None, None, None, gm
+
+
+deform_conv2d_op.register_autograd(_backward_deform_conv2d, setup_context=_setup_deform_conv2d)
+
+
+def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), mask=None):
+    """Modulated deformable convolution (DCNv2; DCNv1 with ``mask=None``) with the signature and semantics of
+    ``torchvision.ops.deform_conv2d`` on the HIP kernels of include/mdcn.h: one weight group (anything else raises
+    NotImplementedError), any number of offset groups, f32 / f64 / bf16 / f16 (``offset`` and ``mask`` may be float32 beside
+    a 16-bit ``input``).  GPU tensors only."""
+    return deform_conv2d_op(input, offset, weight, bias, list(_D._pair(stride, "stride")), list(_D._pair(padding, "padding")),
+                            list(_D._pair(dilation, "dilation")), mask)

@@ -1,0 +1,201 @@
+"""Times devis_amd.deform_conv2d on the six convolutions of the reference mask head at a 360x640 clip, N = 60
+(10 instances x 6 frames), forward and forward + backward, f32 and bf16, against the only other formulation that runs on
+the machine: the oracle's PyTorch gather formulation (tests/dcn_oracle.py) on the GPU in f32 -- and torchvision's
+operator as a third column where it can be imported.
+
+    python scripts/dcn_bench.py [--out profiles/dcn_bench.json] [--windows 5] [--iters 5] [--no-trace]
+
+Device events after warm-up; operator and baseline windows alternate; the median window is quoted.  "hbm_fraction" is the
+algorithmic bytes (input + offset + mask + columns written and read + output; backward: twice that plus the weight
+gradient's second read of the columns) over the time, as a fraction of 8 TB/s.  Unless --no-trace, one child run of this
+script under `rocprofv3 --kernel-trace --stats` splits the operator's time into the project's kernels (mdcn_*) and
+everything else (the GEMMs, layout copies).
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+LAYERS = [(264, 264, 12, 20), (264, 128, 12, 20), (136, 64, 23, 40), (72, 32, 45, 80), (32, 16, 90, 160), (16, 1, 90, 160)]
+N = 60
+HBM_BYTES_PER_S = 8e12
+
+
+def make(layer, dtype, dev):
+    C, Co, H, W = layer
+    gen = torch.Generator().manual_seed(C + Co)
+    x = torch.randn(N, C, H, W, generator=gen).to(dev, dtype)
+    off = (torch.rand(N, 18, H, W, generator=gen) * 4 - 2).to(dev)         # float32 offsets / mask beside either dtype
+    msk = (torch.rand(N, 9, H, W, generator=gen) * 2).to(dev)
+    w = (torch.randn(Co, C, 3, 3, generator=gen) / (C * 9) ** 0.5).to(dev, dtype)
+    g = torch.randn(N, Co, H, W, generator=gen).to(dev, dtype)
+    return x, off, msk, w, g
+
+
+def algorithmic_bytes(layer, dtype, backward):
+    C, Co, H, W = layer
+    P, es = N * H * W, torch.empty((), dtype=dtype).element_size()
+    fwd = P * C * es + P * 27 * 4 + 2 * P * 9 * C * es + P * Co * es
+    return fwd if not backward else 2 * fwd + P * 9 * C * es
+
+
+def stepper(fn, x, off, msk, w, g, backward):
+    if not backward:
+        def step():
+            with torch.no_grad():
+                fn(x, off, w, None, 1, 1, 1, msk)
+        return step
+    leaves = [t.detach().requires_grad_(True) for t in (x, off, msk, w)]
+
+    def step():
+        out = fn(leaves[0], leaves[1], leaves[3], None, 1, 1, 1, leaves[2])
+        torch.autograd.grad(out, leaves, g)
+    return step
+
+
+def window(step, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        step()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def time_alternating(steps, windows, iters):
+    """{name: median ms}; the candidates' windows alternate so that drift hits all of them alike."""
+    for step in steps.values():
+        for _ in range(2):
+            step()
+    torch.cuda.synchronize()
+    seen = {k: [] for k in steps}
+    for _ in range(windows):
+        for k, step in steps.items():
+            seen[k].append(window(step, iters))
+    return {k: statistics.median(v) for k, v in seen.items()}
+
+
+def candidates():
+    import devis_amd
+    import dcn_oracle
+    fns = {"hip": devis_amd.deform_conv2d, "pytorch": dcn_oracle.deform_conv2d}
+    try:
+        import torchvision.ops
+        fns["torchvision"] = torchvision.ops.deform_conv2d
+    except Exception:       # noqa: BLE001 -- not installed, or built for another torch: the column is left out
+        pass
+    return fns
+
+
+def bench(args):
+    dev = torch.device("cuda:0")
+    fns = candidates()
+    rows = []
+    for layer in LAYERS:
+        for dtype in (torch.float32, torch.bfloat16):
+            data = make(layer, dtype, dev)
+            f32 = make(layer, torch.float32, dev) if dtype != torch.float32 else data
+            for backward in (False, True):
+                steps = {k: stepper(fn, *(data if k == "hip" else f32), backward) for k, fn in fns.items()}
+                ms = time_alternating(steps, args.windows, args.iters)
+                row = {"layer": "C%d->%d %dx%d" % layer, "N": N, "dtype": str(dtype).replace("torch.", ""),
+                       "pass": "fwd+bwd" if backward else "fwd", "ms": round(ms["hip"], 4),
+                       "hbm_fraction": round(algorithmic_bytes(layer, dtype, backward) / (ms["hip"] * 1e-3) / HBM_BYTES_PER_S, 4),
+                       "pytorch_f32_ms": round(ms["pytorch"], 4), "speedup_vs_pytorch": round(ms["pytorch"] / ms["hip"], 2)}
+                if "torchvision" in ms:
+                    row["torchvision_f32_ms"] = round(ms["torchvision"], 4)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+            del data, f32
+            torch.cuda.empty_cache()
+    return rows
+
+
+def trace_child():
+    """What the rocprofv3 child runs: the operator alone, 3 forward + backward steps per layer and dtype."""
+    import devis_amd
+    dev = torch.device("cuda:0")
+    for layer in LAYERS:
+        for dtype in (torch.float32, torch.bfloat16):
+            step = stepper(devis_amd.deform_conv2d, *make(layer, dtype, dev), True)
+            for _ in range(3):
+                step()
+    torch.cuda.synchronize()
+
+
+def kernel_split():
+    """Share of the operator's kernel time in the project's kernels and in the rest, from one rocprofv3 run of a child."""
+    if not shutil.which("rocprofv3"):
+        return {"error": "rocprofv3 not found"}
+    tmp = tempfile.mkdtemp(prefix="dcn_trace_")
+    try:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--",
+               sys.executable, os.path.abspath(__file__), "--trace-child"]
+        done = subprocess.run(cmd, cwd=tmp, env=dict(os.environ, TMPDIR=tmp), stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                              timeout=280)
+        if done.returncode != 0:
+            return {"error": "rocprofv3 exit status %d" % done.returncode, "tail": done.stdout.decode("utf-8", "replace")[-400:]}
+        files = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
+        if not files:
+            return {"error": "no kernel_stats.csv"}
+        ours, rest, top = {}, 0, []
+        with open(files[0]) as f:
+            for r in csv.DictReader(f):
+                ns = int(r["TotalDurationNs"])
+                name = r["Name"]
+                if "mdcn_" in name:
+                    short = "mdcn_im2col_kernel" if "im2col" in name else "mdcn_backward_kernel"
+                    ours[short] = ours.get(short, 0) + ns
+                else:
+                    rest += ns
+                    top.append((ns, name[:80]))
+        total = sum(ours.values()) + rest
+        return {"total_kernel_ms": round(total / 1e6, 3), "project_kernels_share": round(sum(ours.values()) / total, 4),
+                "per_kernel_share": {k: round(v / total, 4) for k, v in ours.items()},
+                "other_kernels_share": round(rest / total, 4),
+                "largest_other_kernels": [{"name": n, "share": round(ns / total, 4)} for ns, n in sorted(top, reverse=True)[:5]]}
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--no-trace", action="store_true")
+    ap.add_argument("--trace-child", action="store_true")
+    args = ap.parse_args()
+    if args.trace_child:
+        trace_child()
+        return
+    rows = bench(args)
+    doc = {"device": torch.cuda.get_device_name(0), "N": N, "windows": args.windows, "iters": args.iters,
+           "baseline": "tests/dcn_oracle.py deform_conv2d on the GPU, f32", "rows": rows}
+    slower = [r for r in rows if r["speedup_vs_pytorch"] < 1]
+    doc["slower_than_pytorch"] = ["%s %s %s" % (r["layer"], r["dtype"], r["pass"]) for r in slower]
+    if not args.no_trace:
+        doc["kernel_split_fwd_bwd"] = kernel_split()
+    text = json.dumps(doc, indent=1)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    print(text)
+    sys.exit(1 if slower else 0)
+
+
+if __name__ == "__main__":
+    main()

@@ -16,9 +16,10 @@ class BuildWithHip(build_py):
         sys.path.insert(0, ROOT)
         from devis_amd import build as hip_build
         hip_build.ensure()                                      # raises when hipcc is missing and no library is there
-        inc = os.path.join(ROOT, "devis_amd", "include")        # the header travels inside the package (build.include_dir)
+        inc = os.path.join(ROOT, "devis_amd", "include")        # the headers travel inside the package (build.include_dir)
         os.makedirs(inc, exist_ok=True)
-        shutil.copy2(os.path.join(ROOT, "include", "msda.h"), os.path.join(inc, "msda.h"))
+        for header in ("msda.h", "mdcn.h"):
+            shutil.copy2(os.path.join(ROOT, "include", header), os.path.join(inc, header))
         try:
             super().run()
         finally:
@@ -27,7 +28,7 @@ class BuildWithHip(build_py):
 
 setup(
     name="devis-amd",
-    version="0.6.0",       # (also in pyproject.toml: setuptools < 61 does not read the [project] table)
+    version="0.7.0",       # (also in pyproject.toml: setuptools < 61 does not read the [project] table)
     packages=["devis_amd", "devis_amd.functions", "devis_amd.modules"],
     package_data={"devis_amd": ["libmsda_hip.so", "libmsda_hip.srchash", "csrc/*.hip", "csrc/*.h", "csrc/*.inc", "include/*.h", "routes.json"]},
     py_modules=["MultiScaleDeformableAttention"],
