@@ -36,6 +36,10 @@ def sample_columns(input, offset, kernel_size, stride=(1, 1), padding=(0, 0), di
     wo = torch.arange(Wo, device=dev).to(dt).view(1, 1, 1, 1, Wo)
     y = ho * sh - ph + i * dh + off[:, :, :, 0]         # [N, G, K, Ho, Wo]
     x = wo * sw - pw + j * dw + off[:, :, :, 1]
+    # the range test as include/mdcn.h states it: false for a NaN coordinate, whose tap then contributes nothing and has zero
+    # gradients (NaN * 0 below would be NaN; +-inf - floor(+-inf) too)
+    inside = (y > -1) & (y < H) & (x > -1) & (x < W)
+    y, x = torch.where(inside, y, torch.zeros_like(y)), torch.where(inside, x, torch.zeros_like(x))
     y0, x0 = torch.floor(y).detach(), torch.floor(x).detach()
     flat = input.reshape(N, G, C // G, H * W)
     total = torch.zeros((N, G, C // G, K, Ho, Wo), dtype=dt, device=dev)
@@ -43,7 +47,7 @@ def sample_columns(input, offset, kernel_size, stride=(1, 1), padding=(0, 0), di
         for b in (0, 1):
             yc, xc = y0 + a, x0 + b
             wgt = ((y - y0) if a else (1 - (y - y0))) * ((x - x0) if b else (1 - (x - x0)))
-            valid = (yc >= 0) & (yc <= H - 1) & (xc >= 0) & (xc <= W - 1)
+            valid = inside & (yc >= 0) & (yc <= H - 1) & (xc >= 0) & (xc <= W - 1)
             idx = (yc.clamp(0, H - 1) * W + xc.clamp(0, W - 1)).long().view(N, G, 1, K * Ho * Wo)
             got = torch.gather(flat, 3, idx.expand(N, G, C // G, K * Ho * Wo)).view(N, G, C // G, K, Ho, Wo)
             total = total + got * (wgt * valid.to(dt)).unsqueeze(2)

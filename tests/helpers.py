@@ -192,3 +192,180 @@ def level_rows(x, d):
     """Rows of a [N, S', ...] array that belong to a level, in level order -- the compact layout's rows."""
     shapes, lsi = np.asarray(d["shapes"]), np.asarray(d["lsi"])
     return np.concatenate([x[:, s:s + h * w] for (h, w), s in zip(shapes.tolist(), lsi.tolist())], 1)
+
+
+PLACEMENTS = ("on_grid", "edges", "nonfinite", "huge", "all_out", "piled", "weights")
+POW2 = [(32, 64), (16, 32), (8, 16), (4, 8), (2, 2), (1, 1)]       # power-of-two levels: every placed border coordinate is dyadic
+POW2_4 = POW2[:4]                                                   # S = 2720, four levels (decoder- and encoder-shaped calls)
+HUGE = (1e30, -1e30, 3e9, -3e9, 65504.0, -65504.0, 1e-45, -0.0)     # the first six are out of range for every level and dtype
+
+
+def _exact(c, n, whole=None):
+    """The placed normalised coordinates `c` on levels of size `n`: the kernels' fp32 `c * n - 0.5` equals the fp64 value (kernel
+    and fp64 oracle decide range and cell alike), they survive bf16 / f16 storage where the level is at most 64 wide, and the
+    pixel coordinates marked `whole` are integers."""
+    c, n = np.asarray(c, np.float64), np.asarray(n, np.float64)
+    px = c * n - 0.5
+    assert np.array_equal((c.astype(np.float32) * n.astype(np.float32) - np.float32(0.5)).astype(np.float64), px)
+    assert np.array_equal(c.astype(np.float32).astype(np.float64), c)
+    if n.max() <= 64:
+        for t in (torch.bfloat16, torch.float16):
+            assert np.array_equal(torch.from_numpy(c).to(t).double().numpy(), c), t
+    if whole is not None:
+        assert np.array_equal(px[whole], np.round(px[whole]))
+
+
+def _block_run(rng, Lq, blocks=2):
+    """Start of a run of `blocks` whole 64-query blocks (the culling records' block summaries), or None if that is over Lq / 6."""
+    if Lq < 6 * 64 * blocks:
+        return None
+    return 64 * int(rng.integers(0, Lq // 64 - blocks + 1))
+
+
+def place(d, kind, seed, whole=False):
+    """The call of input dict `d` (make_inputs / make_temporal_inputs) with part of its sampling locations and attention weights
+    overwritten by values random draws do not produce.  Returns (call, masks): masks["placed"], ["out"], ["zero_w"] map each
+    location key ("loc", or "loc_c" and "loc_t") to a bool array over its points [B, Lq, M, LL, P] -- the points written, those of
+    them that are outside the range test BY CONSTRUCTION (their grad_loc / grad_attn are exactly 0), and those whose weight is
+    exactly 0 (their grad_loc is) -- and masks["levels"], ["frames"], ["call"] name what `all_out` emptied (grad_value exactly 0
+    there).  Except for `all_out` at most a third of the queries are touched; the rest stay as drawn.  kind:
+      on_grid    x*W - 0.5 and / or y*H - 0.5 exactly integer, over every row and column index of every level
+      edges      pixel coordinates in (-1, 0) (bottom / right taps only), in (H-1, H) (top / left taps only), exactly -1 and exactly H
+                 (excluded), in every combination of the two axes: map corners with one tap inside included
+      nonfinite  NaN, +inf, -inf in x, in y, in both: in one point of a group, in every point of a group, in whole query rows (and,
+                 with enough queries, two whole blocks of 64 consecutive queries)
+      huge       +-1e30, +-3e9, +-65504 (outside), 1e-45 and -0.0 (inside), in x, in y, in both
+      all_out    no point in range for one (query, head) (with enough queries: two blocks of 64 queries), for one level, and for one
+                 source frame of a temporal call; whole=True: for the entire call
+      piled      every point of a run of consecutive queries in one pixel cell, then in the four cells around one grid corner
+      weights    whole queries with weights exactly 0, with negative weights, and with weights that sum to 3
+    on_grid and edges take power-of-two level sizes (POW2): their coordinates are dyadic, which _exact asserts."""
+    assert kind in PLACEMENTS, kind
+    rng = np.random.default_rng(seed)
+    shapes = np.asarray(d["shapes"], dtype=np.int64)
+    L = len(shapes)
+    if kind in ("on_grid", "edges"):
+        assert all(int(v) & (int(v) - 1) == 0 for v in shapes.reshape(-1)), "on_grid / edges take power-of-two levels"
+    r = dict(d)
+    masks = dict(placed={}, out={}, zero_w={}, levels=[], frames=[], call=bool(whole and kind == "all_out"))
+    pairs = (("loc", "aw"),) if "loc" in d else (("loc_c", "aw_c"), ("loc_t", "aw_t"))
+    level = int(rng.integers(0, L))                                      # all_out: the emptied level and source frame
+    frame = int(rng.integers(0, d["ftab"].shape[0])) if "ftab" in d else None
+    run = _block_run(rng, d[pairs[0][0]].shape[1])                       # nonfinite, all_out: the same blocks in every location array
+    for lk, ak in pairs:
+        loc, aw = np.array(d[lk], dtype=np.float64), np.array(d[ak], dtype=np.float64)
+        B, Lq, M, LL, P, _ = loc.shape
+        H = np.tile(shapes[:, 0], LL // L).astype(np.float64)[:, None]      # [LL, 1]: broadcasts over [B, Lq, M, LL, P]
+        W = np.tile(shapes[:, 1], LL // L).astype(np.float64)[:, None]
+        full = np.zeros((B, Lq, M, LL, P), dtype=bool)
+        nq = max(1, Lq // 3)
+        qs = rng.permutation(Lq)[:nq]
+        pl, ou, zw = full.copy(), full.copy(), full.copy()
+        if kind in ("on_grid", "edges"):
+            pl[:, qs] = True
+            k = (np.cumsum(pl[:, :, :, :1].reshape(-1)) - 1).reshape(B, Lq, M, 1, P)      # running index of the placed points of a level
+            k = np.broadcast_to(k, pl.shape)
+            if kind == "on_grid":
+                i, j = k % H, (7 * k + 3) % W
+                fy, fx = np.where(k // 64 % 4 == 3, 0.25, 0.0), np.where(k // 64 % 4 == 1, 0.25, 0.0)      # (the first 64: both whole)
+                h_im, w_im = i + fy, j + fx
+                for n in range(LL):                                            # every row and column index, on the integer
+                    sel = pl[:, :, :, n]
+                    assert set(i[:, :, :, n][sel & (fy[:, :, :, n] == 0)]) == set(range(int(H[n, 0])))
+                    assert set(j[:, :, :, n][sel & (fx[:, :, :, n] == 0)]) == set(range(int(W[n, 0])))
+                wy, wx = pl & (fy == 0), pl & (fx == 0)
+            else:
+                combos = np.array([(a, b) for a in range(5) for b in range(5) if (a, b) != (4, 4)])       # 24 of them
+                assert pl[:, :, :, 0].sum() >= len(combos)
+                ky, kx = combos[k % len(combos), 0], combos[k % len(combos), 1]
+
+                def coord(kk, n):      # 0: in (-1, 0)  1: in (n-1, n)  2: exactly -1  3: exactly n  4: inside, a quarter into a cell
+                    inside = (5 * k) % np.maximum(n - 1, 1) + 0.25
+                    return np.select([kk == 0, kk == 1, kk == 2, kk == 3], [-0.25 + 0 * n, n - 0.75, -1.0 + 0 * n, n + 0.0], inside)
+                h_im, w_im = coord(ky, H), coord(kx, W)
+                ou = pl & ((ky == 2) | (ky == 3) | (kx == 2) | (kx == 3))
+                wy, wx = pl & (ky >= 2) & (ky <= 3), pl & (kx >= 2) & (kx <= 3)
+            cand = np.stack([(w_im + 0.5) / W, (h_im + 0.5) / H], -1)
+            Hf, Wf = np.broadcast_to(H, pl.shape), np.broadcast_to(W, pl.shape)
+            _exact(cand[..., 1][pl], Hf[pl], wy[pl])
+            _exact(cand[..., 0][pl], Wf[pl], wx[pl])
+            loc = np.where(pl[..., None], cand, loc)
+        elif kind in ("nonfinite", "huge"):
+            vals = np.array([np.nan, np.inf, -np.inf] if kind == "nonfinite" else HUGE)
+            if kind == "nonfinite":
+                if run is not None:                                            # whole query rows: two whole blocks of 64 queries
+                    rest = np.array([q for q in rng.permutation(Lq) if not run <= q < run + 128][:nq - 128])
+                    rows, qs = np.arange(run, run + 128), rest
+                else:
+                    rows, qs = qs[:max(1, nq // 3)], qs[max(1, nq // 3):]
+                pl[:, rows] = True
+                some, groups = qs[:len(qs) // 2], qs[len(qs) // 2:]
+                pl[:, some, :, :, 0] = True                                    # one point of every group of these queries
+                g = (np.arange(M)[:, None] + np.arange(LL)[None, :]) % 2 == 0
+                pl[:, groups] |= g[None, None, :, :, None]                     # every point of half of the groups of these
+                ou = pl.copy()
+            else:
+                pl[:, qs, :, :, ::2] = True
+            k = (np.cumsum(pl.reshape(-1)) - 1).reshape(pl.shape)                # running index of the placed points
+            v, where = vals[k % len(vals)], (k // len(vals)) % 3              # where: 0 = x, 1 = y, 2 = both
+            if kind == "huge":
+                ou = pl & (k % len(vals) < 6)
+            loc[..., 0] = np.where(pl & (where != 1), v, loc[..., 0])
+            loc[..., 1] = np.where(pl & (where != 0), v, loc[..., 1])
+        elif kind == "all_out":
+            if whole:
+                pl[:] = True
+            else:
+                pl[:, int(qs[0]), int(rng.integers(0, M))] = True              # (a) one query and head
+                if run is not None:
+                    pl[:, run:run + 128] = True
+                pl[:, :, :, level::L] = True                                   # (b) one level, in every window slot
+                if frame is not None:                                          # (c) one source frame (of every clip)
+                    T = d["ftab"].shape[0]
+                    for b in range(B):
+                        if lk == "loc_c":
+                            pl[b] |= (b % T == frame)
+                        else:
+                            for w, f in enumerate(d["ftab"][b % T]):
+                                if f == frame:
+                                    pl[b, :, :, w * L:(w + 1) * L] = True
+            ou = pl.copy()
+            how = rng.integers(0, 4, size=pl.shape)                            # one coordinate leaves the map, the other stays as drawn
+            loc[..., 0] = np.where(pl & (how < 2), np.where(how == 0, -3.0, 5.0), loc[..., 0])
+            loc[..., 1] = np.where(pl & (how >= 2), np.where(how == 2, -3.0, 5.0), loc[..., 1])
+        elif kind == "piled":
+            n = max(2, nq) if Lq >= 2 else 1
+            q0 = int(rng.integers(0, Lq - n + 1))
+            pl[:, q0:q0 + n] = True
+            i0, j0 = np.floor(rng.random(H.shape) * H), np.floor(rng.random(W.shape) * W)      # one cell / corner per level slot
+            fr = 0.1 + 0.8 * rng.random(pl.shape + (2,))
+            around = np.zeros(pl.shape + (2,))
+            around[:, q0 + n // 2:q0 + n] = rng.integers(0, 2, size=around[:, q0 + n // 2:q0 + n].shape)       # second half: four cells
+            cand = np.stack([(j0 + fr[..., 0] - around[..., 0] + 0.5) / W, (i0 + fr[..., 1] - around[..., 1] + 0.5) / H], -1)
+            loc = np.where(pl[..., None], cand, loc)
+        elif kind == "weights":
+            third = max(1, nq // 3)
+            zero, neg, triple = qs[:third], qs[third:2 * third], qs[2 * third:]
+            pl[:, qs] = True
+            zw[:, zero] = True
+            aw[:, zero] = 0.0
+            aw[:, neg] = -aw[:, neg]
+            aw[:, triple] = 3.0 * aw[:, triple]
+        if not (kind == "all_out"):
+            assert pl.any(axis=(0, 2, 3, 4)).sum() <= max(1, Lq // 3) or Lq < 3, kind
+        r[lk], r[ak] = loc.astype(d[lk].dtype), aw.astype(d[ak].dtype)
+        masks["placed"][lk], masks["out"][lk], masks["zero_w"][lk] = pl, ou, zw
+    if kind == "all_out" and not whole:
+        masks["levels"] = [level]
+        if frame is not None:
+            T = d["ftab"].shape[0]
+            masks["frames"] = [b for b in range(d["value"].shape[0]) if b % T == frame]
+    return r, masks
+
+
+def out_moved(d, masks, to=-10.0):
+    """`d` with every location that `masks` marks as out of range replaced by (`to`, `to`): no output may change by a bit."""
+    r = dict(d)
+    for lk, m in masks["out"].items():
+        r[lk] = np.where(m[..., None], np.asarray(to, d[lk].dtype), d[lk])
+    return r

@@ -127,12 +127,14 @@ def test_chunked_under_a_small_workspace_bound_gives_the_same_result(monkeypatch
 
 def _border_inputs(dtype):
     """One 1x1 tap per output pixel of a 6x7 map, its offset chosen per pixel: rows put the point in (-1, 0), on integers,
-    on H-1, in (H-1, H), at H exactly, and outside by a pixel and by 1e9."""
+    on H-1, in (H-1, H), at H exactly, outside by a pixel and by 1e9, and on NaN, +inf and -inf: in the row, in the column and
+    in both (a pixel's row entry i meets column entries i, i + 1 and i + 2)."""
     H, W = 6, 7
     tensors, geometry = make_inputs(N=1, C=8, Co=3, H=H, W=W, kernel=1, padding=0, dtype=dtype, seed=3)
     x, off, w, b, m, g = tensors
-    ys = torch.tensor([-0.5, 0.0, 2.0, H - 1.0, H - 0.25, -1.5, float(H), 1e9, -1e9, 2.5])
-    xs = torch.tensor([-0.75, 0.0, 3.0, W - 1.0, W - 0.5, -2.0, float(W), 3e9, -3e9, 1.25])
+    nan, inf = float("nan"), float("inf")
+    ys = torch.tensor([-0.5, 0.0, 2.0, H - 1.0, H - 0.25, -1.5, float(H), 1e9, -1e9, 2.5, nan, inf, -inf, 1.5])
+    xs = torch.tensor([-0.75, 0.0, 3.0, W - 1.0, W - 0.5, -2.0, float(W), 3e9, -3e9, 1.25, 2.5, nan, inf, -inf])
     off = off.double()
     for ho in range(H):
         for wo in range(W):
@@ -143,21 +145,52 @@ def _border_inputs(dtype):
     return (x, off.to(tensors[1].dtype), w, b, m, g), geometry
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.float64, torch.bfloat16], ids=["f32", "f64", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64, torch.bfloat16, torch.float16], ids=["f32", "f64", "bf16", "f16"])
 def test_points_on_and_beyond_the_border(dtype):
     tensors, geometry = _border_inputs(dtype)
     got, want = hip(tensors, geometry), oracle(tensors, geometry)
+    assert all(bool(torch.isfinite(t).all()) for t in got + want if t is not None)
     assert_close(got, want, TOL[dtype], "border")
     # a point at or beyond one pixel outside contributes nothing and has zero gradients, exactly
     x, off = tensors[0], tensors[1].double()
     H, W = x.shape[2:]
     ho, wo = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
     y, xx = off[0, 0] + ho, off[0, 1] + wo
-    outside = (y <= -1) | (y >= H) | (xx <= -1) | (xx >= W)
-    assert int(outside.sum()) >= 8
+    outside = ~((y > -1) & (y < H) & (xx > -1) & (xx < W))                      # (with NaN: outside)
+    assert int(outside.sum()) >= 8 and int((y.isnan() | xx.isnan()).sum()) >= 5 and int((y.isinf() | xx.isinf()).sum()) >= 8
     bias = tensors[3].to(DEV).view(-1, 1)
     assert torch.equal(got[0][0][:, outside.to(DEV)], bias.expand(-1, int(outside.sum())))
     assert float(got[2][0][:, outside.to(DEV)].abs().max()) == 0 and float(got[3][0][:, outside.to(DEV)].abs().max()) == 0
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+def test_a_non_finite_tap_of_a_3x3_kernel_stays_in_its_own_tap(dtype):
+    """NaN, +inf and -inf row and column offsets in single taps of a 3x3 kernel over two groups of two channels, and in every tap
+    of one pixel: the tap contributes nothing and its grad_offset / grad_mask are exactly 0, and neither the wavefront reduction nor
+    the team padding of mdcn_backward_kernel carries it anywhere -- every output is finite, matches the oracle, and keeps its bits
+    when those taps point far outside the map instead (grad_input: float atomics, to rounding)."""
+    tensors, geometry = make_inputs(N=2, C=4, Co=5, H=6, W=7, G=2, dtype=dtype, seed=13)
+    x, off, w, b, m, g = tensors
+    off, far = off.clone(), off.clone()
+    bad = torch.zeros_like(m, dtype=torch.bool)                                 # [N, G*K, Ho, Wo]
+    vals = [float("nan"), float("inf"), float("-inf")]
+    taps = [(t % 2, t, t % 6, (2 * t + 1) % 7) for t in range(18)] + [(0, k, 3, 3) for k in range(9)]
+    for i, (n, t, ho, wo) in enumerate(taps):
+        where = (i // 3) % 3                                                    # 0: row, 1: column, 2: both
+        bad[n, t, ho, wo] = True
+        for axis in ((0,), (1,), (0, 1))[where]:
+            off[n, 2 * t + axis, ho, wo] = vals[i % 3]
+        far[n, 2 * t, ho, wo] = far[n, 2 * t + 1, ho, wo] = -100.0
+    got, want = hip((x, off, w, b, m, g), geometry), oracle((x, off, w, b, m, g), geometry)
+    assert all(bool(torch.isfinite(t).all()) for t in got + want)
+    assert_close(got, want, TOL[dtype], "non-finite taps")
+    sel = bad.to(DEV)
+    assert float(got[3][sel].abs().max()) == 0                                  # grad_mask, grad_offset of both axes
+    assert float(got[2].view(2, 18, 2, 6, 7)[:, :, 0][sel].abs().max()) == 0 and float(got[2].view(2, 18, 2, 6, 7)[:, :, 1][sel].abs().max()) == 0
+    moved = hip((x, far, w, b, m, g), geometry)
+    for i in (0, 2, 3, 4, 5):
+        assert torch.equal(got[i], moved[i]), NAMES[i]
+    assert float((got[1] - moved[1]).abs().max()) <= TOL[dtype] * max(1.0, float(moved[1].abs().max()))
 
 
 def test_scatter_writes_nothing_outside_grad_input():

@@ -56,11 +56,11 @@ ROUTES = {
 SEEN = set()
 
 
-def _mark(label, route):
+def _mark(label, route, seen=SEEN):
     """The route of `label` ran (called once the case's results have passed their checks): it counts as reached."""
     must, must_not = ROUTES[label]
     assert all(s in route for s in must) and not any(s in route for s in must_not), (label, route)
-    SEEN.add(label)
+    seen.add(label)
 
 
 # ---- inputs ---------------------------------------------------------------------------------------------------------------------
