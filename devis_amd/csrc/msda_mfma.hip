@@ -27,6 +27,8 @@
 //   (4) G rows straight from memory into the B-operand layout (8 coalesced row segments per wave), split in registers;
 //   (5) per pixel tile the 2-3 products; (6) the cells are written back to zero.
 // At the end of an item the waves' accumulators are added through the LDS and stored as 128-byte rows; grad_value of these
+// Item -> head = item % M: with M = 8 an XCD only ever works on ONE head.  That is on purpose (other orders: L2 hits 1.99 M -> 0.5 M per
+// launch, 1-2 % slower; the L2 channels are evenly loaded either way -- profiles/NEGATIVE_RESULTS.md R7-1).
 // levels is OVERWRITTEN (include/msda.h), in fp32 or in the storage type.  The owner-computes scatter runs with
 // Params::own_levels = first level handled here and never sees these levels.
 #include "msda_common.h"

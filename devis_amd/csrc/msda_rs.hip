@@ -174,13 +174,22 @@ msda_fwd_rs_kernel(const Params p, int slab_bytes, int parts)
     const int l0 = sh.l0;
 
     // workgroup -> (clip, head, part of the clip's tiles); wave -> up to NT tiles, 16 apart.  Blocks are dealt
-    // round-robin to the 8 XCDs; each XCD takes a CONTIGUOUS run of (clip, head, part) triples, i.e. whole clips:
-    // the parts of one (clip, head) share their slab and gathers in one L2, and -- unlike a head-per-XCD
-    // mapping -- every XCD touches all heads, so the 1 KiB head pitch of the dense layout does not pin address
-    // bits 7..9 and starve the L2 channels (speed only; results do not depend on placement)
+    // round-robin to the 8 XCDs; each XCD takes a CONTIGUOUS run of (clip, head slot, part) triples, i.e. whole clips:
+    // the parts of one (clip, head) share their slab and gathers in one L2, and every XCD touches all heads.
+    // Head slot h of a clip is head (2 h) mod M (+ 1 in the second half): 0 2 4 6 | 1 3 5 7.  With 8 parts on 32 CUs an
+    // XCD has four (clip, head) pairs in flight; in the dense [N, S, M, 32] fp32 layout a head is bits 7..9 of the
+    // address, and four ALTERNATE heads at one time cost the forward 6-7 % less than four neighbouring ones (0.351 ->
+    // 0.328 ms, two thirds of what rows padded by one head slot gain).  Not through the L2
+    // channels: TCC_REQ is even over all 128 of them (max / mean 1.005) in either order and with bits 7..9 pinned
+    // (scripts/ubench/l2_channel_probe.hip).  The gather pass keeps the plain order: it lost 1-3 % with every order tried.
+    // Only where that was measured: 4-byte types in the dense layout (in a 2-byte type two neighbouring heads share a
+    // 128-byte line, and padded rows have no such pitch); otherwise, and for odd M, the plain order.
+    // (speed only; results do not depend on where a workgroup runs)
     const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u;
     const unsigned lin = xcd * (nwg / 8u) + min(xcd, nwg % 8u) + blockIdx.x / 8u;
-    const int part = (int)(lin % (unsigned)parts), m = (int)((lin / (unsigned)parts) % (unsigned)p.M);
+    const int part = (int)(lin % (unsigned)parts), slot = (int)((lin / (unsigned)parts) % (unsigned)p.M);
+    const bool alternate = !kHalf && !(p.M & 1) && p.v_pix == p.M * D && p.v_head == D;
+    const int m = alternate ? (2 * slot) % p.M + (2 * slot) / p.M : slot;
     const int clip = (int)(lin / ((unsigned)parts * (unsigned)p.M));
     const int tiles_per_group = (p.Lq + RPW - 1) / RPW, tiles_per_clip = p.frames * tiles_per_group;
     const int tpw = (tiles_per_clip + parts - 1) / parts;
@@ -401,7 +410,7 @@ msda_bwd_rs_kernel(const Params p, int slab_bytes, int parts, int frame_split)
     const RsShared sh = rs_setup(p, lds_raw, slab_bytes, (int)sizeof(T));
     const int l0 = sh.l0;
 
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u;       // clip-major XCD mapping, as in the forward
+    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u;       // clip-major XCD mapping, heads in their plain order (see the forward)
     const unsigned lin = xcd * (nwg / 8u) + min(xcd, nwg % 8u) + blockIdx.x / 8u;
     // frame_split (round 4): a workgroup = (clip, head, SOURCE FRAME, part of the clip's tiles) instead of (clip, head, part)
     // walking the frames: nothing is carried from one source frame to the next in this pass, so the frame loop can be a grid

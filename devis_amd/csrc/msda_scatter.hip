@@ -47,6 +47,9 @@ namespace {
 //   The grid is persistent (one 1024-thread workgroup per CU striding over the items) because the
 //   number of bands depends on spatial_shapes, which lives in device memory (no host sync allowed);
 //   item % M = head keeps the head -> XCD affinity of the gather kernels.
+//   (Measured: with the heads rotated over the XCDs, or all heads of a (clip, frame, band) on one XCD at a time, the owner-computes
+//   kernel's L2 hit rate falls 0.74 -> 0.30 and it runs 5 % longer; the L2 channels are evenly loaded either way -- profiles/
+//   NEGATIVE_RESULTS.md R7-1.)
 constexpr int kScatterThreads = 1024;
 constexpr int kScatterList = 3072;         // capacity of the survivor list (12 KiB of the 16 KiB LDS left by the band)
 
