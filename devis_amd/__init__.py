@@ -22,9 +22,10 @@ from .modules import (ModulatedDeformableConv2d, MSDeformAttn, TemporalMSDeformA
                       TemporalMSDeformAttnEncoder)
 from . import ops  # noqa: F401  (the operator as torch.library custom ops: torch.compile / torch.export)
 from .ops import deform_conv2d  # noqa: F401
+from .functions.deform_conv import reproducible_grad_input, reproducible_grad_input_enabled  # noqa: F401
 from .argument_builders import patch_mask_head, patch_transformer  # noqa: F401
 from .graphs import graphed, graph_stream, GraphedLayer  # noqa: F401
 from .tuning import tune  # noqa: F401
 
 __all__ = ["MSDeformAttnFunction", "MSDeformAttnTemporalFunction", "ms_deform_attn_core_pytorch",
-           "MSDeformAttn", "TemporalMSDeformAttnEncoder", "TemporalMSDeformAttnDecoder", "ModulatedDeformableConv2d", "deform_conv2d", "ops", "patch_transformer", "patch_mask_head", "graphed", "graph_stream", "GraphedLayer", "tune"]
+           "MSDeformAttn", "TemporalMSDeformAttnEncoder", "TemporalMSDeformAttnDecoder", "ModulatedDeformableConv2d", "deform_conv2d", "reproducible_grad_input", "reproducible_grad_input_enabled", "ops", "patch_transformer", "patch_mask_head", "graphed", "graph_stream", "GraphedLayer", "tune"]

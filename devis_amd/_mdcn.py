@@ -9,10 +9,11 @@ import torch
 
 from . import _native
 
-MDCN_ABI_VERSION = 1
+MDCN_ABI_VERSION = 2
 GRAD_INPUT, GRAD_SAMPLING = 1, 2        # include/mdcn.h MDCN_GRAD_INPUT / MDCN_GRAD_SAMPLING
 # every symbol include/mdcn.h declares (tests check the library exports each of them)
-EXPORTED_SYMBOLS = ("mdcn_version", "mdcn_last_error", "mdcn_workspace_bytes", "mdcn_im2col", "mdcn_backward")
+EXPORTED_SYMBOLS = ("mdcn_version", "mdcn_last_error", "mdcn_workspace_bytes", "mdcn_im2col", "mdcn_backward",
+                    "mdcn_fixed_workspace_bytes", "mdcn_backward_input_fixed")
 _OFF32_CODE = {torch.bfloat16: 4, torch.float16: 5}     # MDCN_BF16_OFF32 / MDCN_F16_OFF32
 
 _vp, _ci = ctypes.c_void_p, ctypes.c_int
@@ -51,6 +52,10 @@ def load():
         lib.mdcn_im2col.argtypes = [_ci, _vp, _vp, _vp, shape_p, _vp, _vp]
         lib.mdcn_backward.restype = _ci
         lib.mdcn_backward.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, shape_p, _vp, _vp, _vp, _vp]
+        lib.mdcn_fixed_workspace_bytes.restype = ctypes.c_longlong
+        lib.mdcn_fixed_workspace_bytes.argtypes = [_ci, shape_p, _ci]
+        lib.mdcn_backward_input_fixed.restype = _ci
+        lib.mdcn_backward_input_fixed.argtypes = [_ci, _vp, _vp, _vp, shape_p, _vp, _vp, _vp]
         _lib = lib
     return _lib
 
@@ -94,3 +99,19 @@ def backward(grads, code, x_nhwc, offset, mask, grad_columns, shape, grad_input_
                                   _native._p(grad_columns), ctypes.byref(shape), _native._p(grad_input_acc),
                                   _native._p(grad_offset), _native._p(grad_mask), _native._stream(x_nhwc))
     _check(rc, "mdcn_backward")
+
+
+def fixed_workspace_bytes(code, shape, batch):
+    """Bytes of the workspace of :func:`backward_input_fixed` for ``batch`` images (mdcn_fixed_workspace_bytes)."""
+    return _check(load().mdcn_fixed_workspace_bytes(code, ctypes.byref(shape), batch), "mdcn_fixed_workspace_bytes")
+
+
+def backward_input_fixed(code, offset, mask, grad_columns, shape, workspace, grad_input):
+    """mdcn_backward_input_fixed on the current stream: the order-independent grad_input of ``shape.N`` images, fully
+    written into ``grad_input`` ([N, H, W, C] in the arithmetic type).  ``workspace`` is a tensor of at least
+    :func:`fixed_workspace_bytes` bytes; it need not be initialised."""
+    with _native._on(grad_columns.device):
+        rc = load().mdcn_backward_input_fixed(code, _native._p(offset), _native._p(mask), _native._p(grad_columns),
+                                              ctypes.byref(shape), _native._p(workspace), _native._p(grad_input),
+                                              _native._stream(grad_columns))
+    _check(rc, "mdcn_backward_input_fixed")

@@ -2,6 +2,12 @@
 channels-last copy of the input, the batch-chunk loop under the workspace bound, and the GEMMs with the weights
 (``torch`` -> rocBLAS) around the two HIP kernels.  The custom ops of :mod:`devis_amd.ops` run exactly this code.
 
+``grad_input`` is by default a sum of float atomics, whose last bits depend on the order the adds arrive in.
+:class:`reproducible_grad_input` opts in to the order-independent fixed-point sum of include/mdcn.h
+(``mdcn_backward_input_fixed``): bitwise the same from run to run, for an image alone or in a batch, under any chunking.
+That mode holds one more buffer of 8 + 1/2 bytes per element of the chunk's ``grad_input`` (int64 accumulators and class
+nibbles); the other gradients are computed exactly as without it.
+
 There is no CPU path and no eager fallback: CPU tensors raise, a failing kernel call raises.
 """
 import warnings
@@ -14,11 +20,63 @@ from .. import _mdcn
 # so that the buffer stays under it (one image is the smallest chunk, whatever its size); the forward holds one such
 # buffer, a backward that computes grad_weight two (columns and grad_columns).  A constant, never derived from free memory:
 # the chunking -- and with it the order of grad_weight's sum over chunks -- is the same on every run.
+# (With reproducible_grad_input a backward also holds the fixed-point workspace of one chunk, 8 + 1/2 bytes per element of
+# the chunk's grad_input; the chunk size is still chosen from the column bound alone.)
 WORKSPACE_BYTES = 256 << 20
 
 # which gradients a backward computes (the `grads` argument of the backward op)
 NEED_INPUT, NEED_OFFSET, NEED_MASK, NEED_WEIGHT, NEED_BIAS = 1, 2, 4, 8, 16
 NEED_ALL = 31
+# Beside the NEED_* bits the `grads` argument may carry what a caller pinned for this call (the module's
+# ``reproducible_grad_input`` attribute, the operator's keyword): grad_input by the fixed-point sum / by float atomics,
+# whatever the process-wide switch says.  Neither bit set: the switch decides, when the backward runs.
+PIN_FIXED, PIN_FLOAT = 32, 64
+PIN_BITS = PIN_FIXED | PIN_FLOAT
+
+_reproducible = False
+
+
+class reproducible_grad_input:
+    """Opt in to (or, with ``enabled=False``, out of) the order-independent ``grad_input`` of ``deform_conv2d``.
+
+    A plain call ``reproducible_grad_input()`` sets the process-wide default; ``with reproducible_grad_input():`` restores
+    the previous value on exit, and nests.  The switch is read when a backward RUNS, as
+    ``torch.use_deterministic_algorithms`` is: the ``with`` block has to span the backward pass.  With it on, a backward
+    that needs ``grad_input`` does not raise or warn under ``torch.use_deterministic_algorithms(True)``, and ``grad_input``
+    comes from the fixed-point path whether or not that flag is set."""
+
+    def __init__(self, enabled=True):
+        global _reproducible
+        self.previous = _reproducible
+        _reproducible = bool(enabled)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        global _reproducible
+        _reproducible = self.previous
+        return False
+
+
+def reproducible_grad_input_enabled():
+    """The process-wide switch of :class:`reproducible_grad_input`."""
+    return _reproducible
+
+
+def pin_bits(pinned):
+    """None / True / False (what a caller pinned for one call) -> the PIN_* bits of the backward's `grads`."""
+    return 0 if pinned is None else (PIN_FIXED if pinned else PIN_FLOAT)
+
+
+def input_mode(grads):
+    """`grads` -> (its NEED_* bits, whether grad_input comes from the fixed-point path): what was pinned for the call,
+    else the process-wide switch as it stands now."""
+    pinned = grads & PIN_BITS
+    _require(pinned != PIN_BITS, "grads pins grad_input to both of its paths")
+    need = grads & NEED_ALL
+    fixed = bool(need & NEED_INPUT) and (pinned == PIN_FIXED or (not pinned and _reproducible))
+    return need, fixed
 
 
 def _require(cond, msg):
@@ -93,11 +151,13 @@ def _check_device(named):
 def alert_nondeterministic(grads):
     """grad_input is a sum of float atomics, so it depends on the order the adds arrive in: under
     ``torch.use_deterministic_algorithms(True)`` asking for it raises (warns with ``warn_only=True``), as PyTorch's own
-    non-deterministic operators do.  The other four gradients are reproducible bit for bit."""
+    non-deterministic operators do.  The other four gradients are reproducible bit for bit.  (Not called when
+    grad_input comes from the fixed-point path: see :func:`input_mode`.)"""
     if grads & NEED_INPUT and torch.are_deterministic_algorithms_enabled():
         msg = ("devis_amd::deform_conv2d_backward does not have a deterministic implementation of grad_input, but you set "
                "'torch.use_deterministic_algorithms(True%s)'. You can turn off determinism just for this operation, or detach "
-               "the input (the other gradients are deterministic).")
+               "the input (the other gradients are deterministic). An order-independent grad_input is opt-in: "
+               "devis_amd.reproducible_grad_input(), or reproducible_grad_input=True on the ModulatedDeformableConv2d layer.")
         if torch.is_deterministic_algorithms_warn_only_enabled():
             warnings.warn(msg % ", warn_only=True", UserWarning, stacklevel=2)
         else:
@@ -148,8 +208,14 @@ def _forward(input, offset, weight, bias, stride, padding, dilation, mask):
 
 def _backward(grad_out, input, offset, weight, mask, stride, padding, dilation, grads=NEED_ALL):
     """(grad_input, grad_offset, grad_mask, grad_weight, grad_bias) for the gradients in ``grads``; the others are
-    neither allocated nor computed and come back None (grad_mask also without a mask)."""
-    alert_nondeterministic(grads)
+    neither allocated nor computed and come back None (grad_mask also without a mask).  ``grads`` may carry a PIN_* bit;
+    grad_input then, or with :class:`reproducible_grad_input` on, is the fixed-point sum of ``mdcn_backward_input_fixed``:
+    chunks are whole images and its quanta are per image, so the chunking does not show in it (given the same
+    grad_columns: a row of that GEMM is a sum over Co alone, and rocBLAS gave it the same bits for every chunk size
+    tests/test_dcn_reproducible_gpu.py tries; the library's own guarantee starts at grad_columns)."""
+    grads, fixed = input_mode(grads)
+    if not fixed:
+        alert_nondeterministic(grads)
     _check_device([("input", input), ("grad_out", grad_out)])
     shape, code, x, offset, mask, w2 = _prepare(input, offset, weight, None, stride, padding, dilation, mask)
     N, C, H, W = input.shape
@@ -162,15 +228,18 @@ def _backward(grad_out, input, offset, weight, mask, stride, padding, dilation, 
     want_in = bool(grads & NEED_INPUT)
     want_s = bool(grads & NEED_OFFSET) or (bool(grads & NEED_MASK) and mask is not None)
     want_w, want_b = bool(grads & NEED_WEIGHT), bool(grads & NEED_BIAS)
-    kernel_grads = (_mdcn.GRAD_INPUT if want_in else 0) | (_mdcn.GRAD_SAMPLING if want_s else 0)
+    kernel_grads = (_mdcn.GRAD_INPUT if want_in and not fixed else 0) | (_mdcn.GRAD_SAMPLING if want_s else 0)
 
-    gin_acc = torch.zeros((N, H, W, C), dtype=acc, device=dev) if want_in else None
+    gin_acc = None
+    if want_in:     # the float atomics add into zeros; the fixed-point path writes every element
+        gin_acc = (torch.empty if fixed else torch.zeros)((N, H, W, C), dtype=acc, device=dev)
     goff = torch.empty_like(offset) if want_s else None
     gmsk = torch.empty_like(mask) if want_s and mask is not None else None
     gw_acc = torch.zeros((Co, KC), dtype=acc, device=dev) if want_w else None
-    if N > 0 and (kernel_grads or want_w):
+    if N > 0 and (kernel_grads or fixed or want_w):
         step = chunk_images(code, shape, N)
-        gcols = torch.empty((step * P, KC), dtype=dt, device=dev) if kernel_grads else None
+        gcols = torch.empty((step * P, KC), dtype=dt, device=dev) if kernel_grads or fixed else None
+        fixed_ws = torch.empty(_mdcn.fixed_workspace_bytes(code, shape, step), dtype=torch.uint8, device=dev) if fixed else None
         cols = torch.empty((step * P, KC), dtype=dt, device=dev) if want_w else None
         for n0 in range(0, N, step):
             nb = min(step, N - n0)
@@ -178,11 +247,14 @@ def _backward(grad_out, input, offset, weight, mask, stride, padding, dilation, 
             sl = slice(n0, n0 + nb)
             go = grad_out[sl].permute(0, 2, 3, 1).reshape(nb * P, Co)      # [pixels, Co] (a copy unless channels-last)
             mk = None if mask is None else mask[sl]
-            if kernel_grads:
+            if kernel_grads or fixed:
                 torch.mm(go, w2, out=gcols[:nb * P])
+            if kernel_grads:
                 _mdcn.backward(kernel_grads, code, x[sl], offset[sl], mk, gcols, shape,
-                               None if gin_acc is None else gin_acc[sl], None if goff is None else goff[sl],
+                               gin_acc[sl] if kernel_grads & _mdcn.GRAD_INPUT else None, None if goff is None else goff[sl],
                                None if gmsk is None else gmsk[sl])
+            if fixed:
+                _mdcn.backward_input_fixed(code, offset[sl], mk, gcols, shape, fixed_ws, gin_acc[sl])
             if want_w:
                 _mdcn.im2col(code, x[sl], offset[sl], mk, shape, cols)
                 part = torch.mm(go.t(), cols[:nb * P])

@@ -4,6 +4,10 @@ class of the same name) on :func:`devis_amd.ops.deform_conv2d` instead of ``torc
 Same constructor, same parameter names (``offset_conv``, ``modulator_conv``, ``regular_conv``) and the same initialisation
 (offset and modulator convolutions zero: a fresh layer is a plain convolution), so reference checkpoints load with
 ``strict=True``.
+
+``reproducible_grad_input`` (an attribute, not a parameter or buffer: it is in no state dict) chooses how the layer's
+backward sums grad_input: None follows :class:`devis_amd.reproducible_grad_input`, True / False pins this layer to the
+order-independent fixed-point sum / to float atomics.
 """
 import torch
 from torch import nn
@@ -12,6 +16,8 @@ from .. import ops
 
 
 class ModulatedDeformableConv2d(nn.Module):
+    reproducible_grad_input = None      # set on an instance to override the process-wide switch for that layer
+
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=False):
         super().__init__()
         self.stride = stride
@@ -38,4 +44,5 @@ class ModulatedDeformableConv2d(nn.Module):
             offset, modulator = offset.float(), modulator.float()
         modulator = 2. * torch.sigmoid(modulator)
         # (the reference passes only `padding` on to the operator; its mask head never sets another stride than 1)
-        return ops.deform_conv2d(x, offset, weight, bias, stride=self.stride, padding=self.padding, mask=modulator)
+        return ops.deform_conv2d(x, offset, weight, bias, stride=self.stride, padding=self.padding, mask=modulator,
+                                 reproducible_grad_input=self.reproducible_grad_input)

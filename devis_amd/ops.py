@@ -16,6 +16,9 @@ through the C ABI, the same numbers -- and whose fake implementation gives shape
 ``frame_table``                the temporal modules' frame table ``[T, W]`` int32 (cache and deferred range checks)
 ``deform_conv2d``              the mask head's modulated deformable convolution (:func:`deform_conv2d`, torchvision's
                                signature); ``deform_conv2d_backward`` computes the gradients its ``grads`` mask names
+``deform_conv2d_pinned``       the same forward for a call that pins how its backward sums grad_input (the module's
+                               ``reproducible_grad_input`` attribute): a constant of the graph, handed to the backward op
+                               as a PIN_* bit of ``grads``
 =============================  ==========================================================================================
 
 Everything that reads the host or keeps Python state -- the ``spatial_shapes`` host hint, the frame-table cache, the
@@ -445,7 +448,7 @@ def deform_conv2d_backward(grad_out: Tensor, input: Tensor, offset: Tensor, weig
 
 @deform_conv2d_backward.register_fake
 def _fake_deform_conv2d_backward(grad_out, input, offset, weight, mask, stride, padding, dilation, grads):
-    _D._require(0 <= grads <= _D.NEED_ALL, "grads must be a mask of the NEED_* bits")
+    _D._require(0 <= grads <= (_D.NEED_ALL | _D.PIN_BITS), "grads must be a mask of the NEED_* bits, with at most one PIN_* bit beside them")
     has = lambda bit, t: t is not None and bool(grads & bit)    # noqa: E731
     return (_empty(input, input.shape if has(_D.NEED_INPUT, input) else (0,)),
             _empty(offset, offset.shape if has(_D.NEED_OFFSET, offset) else (0,)),
@@ -464,6 +467,7 @@ def _backward_deform_conv2d(ctx, grad_out):
     input, offset, weight, mask = ctx.saved_tensors
     needs = ctx.needs_input_grad
     grads = _D.grads_mask(needs[0], needs[1], needs[7] and mask is not None, needs[2], needs[3])
+    grads |= _D.pin_bits(getattr(ctx, "pinned", None))
     gi, go, gm, gw, gb = none_slots(deform_conv2d_backward(grad_out, input, offset, weight, mask, *ctx.geometry, grads))
     return gi, go, gw, gb, None, None, None, gm
 
@@ -471,10 +475,46 @@ def _backward_deform_conv2d(ctx, grad_out):
 deform_conv2d_op.register_autograd(_backward_deform_conv2d, setup_context=_setup_deform_conv2d)
 
 
-def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), mask=None):
+# The process-wide switch of reproducible_grad_input is read inside the backward op, when it runs.  What ONE call pins has to
+# be part of the graph instead (Python state around a call does not survive tracing): a forward op of its own carries it.
+@_op("deform_conv2d_pinned")
+def deform_conv2d_pinned_op(input: Tensor, offset: Tensor, weight: Tensor, bias: Optional[Tensor], stride: List[int],
+                            padding: List[int], dilation: List[int], mask: Optional[Tensor],
+                            reproducible_grad_input: bool) -> Tensor:
+    """``deform_conv2d_op`` for a call whose backward sums grad_input in fixed point (True) or with float atomics (False)
+    whatever the process-wide switch says.  The forward is the same."""
+    return _D._forward(input, offset, weight, bias, stride, padding, dilation, mask)
+
+
+@deform_conv2d_pinned_op.register_fake
+def _(input, offset, weight, bias, stride, padding, dilation, mask, reproducible_grad_input):
+    Ho, Wo, _ = _D.check_shapes(input, offset, weight, bias, stride, padding, dilation, mask)
+    return _empty(input, (input.shape[0], weight.shape[0], Ho, Wo))
+
+
+def _setup_deform_conv2d_pinned(ctx, inputs, output):
+    _setup_deform_conv2d(ctx, inputs[:8], output)
+    ctx.pinned = bool(inputs[8])
+
+
+def _backward_deform_conv2d_pinned(ctx, grad_out):
+    return _backward_deform_conv2d(ctx, grad_out) + (None,)
+
+
+deform_conv2d_pinned_op.register_autograd(_backward_deform_conv2d_pinned, setup_context=_setup_deform_conv2d_pinned)
+
+
+def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), mask=None, *,
+                  reproducible_grad_input=None):
     """Modulated deformable convolution (DCNv2; DCNv1 with ``mask=None``) with the signature and semantics of
     ``torchvision.ops.deform_conv2d`` on the HIP kernels of include/mdcn.h: one weight group (anything else raises
     NotImplementedError), any number of offset groups, f32 / f64 / bf16 / f16 (``offset`` and ``mask`` may be float32 beside
-    a 16-bit ``input``).  GPU tensors only."""
-    return deform_conv2d_op(input, offset, weight, bias, list(_D._pair(stride, "stride")), list(_D._pair(padding, "padding")),
-                            list(_D._pair(dilation, "dilation")), mask)
+    a 16-bit ``input``).  GPU tensors only.
+
+    ``reproducible_grad_input`` (not torchvision's): None leaves the choice of grad_input's sum to
+    :class:`devis_amd.reproducible_grad_input` when the backward runs; True / False pins this call to the order-independent
+    fixed-point sum / to float atomics."""
+    geometry = (list(_D._pair(stride, "stride")), list(_D._pair(padding, "padding")), list(_D._pair(dilation, "dilation")))
+    if reproducible_grad_input is None:
+        return deform_conv2d_op(input, offset, weight, bias, *geometry, mask)
+    return deform_conv2d_pinned_op(input, offset, weight, bias, *geometry, mask, bool(reproducible_grad_input))

@@ -7,6 +7,7 @@
  *   forward    mdcn_im2col   input, offset, mask -> columns [pixels, K*C]          out          = columns @ weight^T (+ bias)
  *   backward   (caller)      grad_columns [pixels, K*C] = grad_out @ weight        grad_weight  = grad_out^T @ columns
  *              mdcn_backward grad_columns, input, offset, mask -> grad_offset, grad_mask, and grad_input (accumulated)
+ *              mdcn_backward_input_fixed   grad_columns, offset, mask -> grad_input as an order-independent fixed-point sum
  *
  * Semantics (those of torchvision.ops.deform_conv2d, one weight group): tap k = i*Kw + j of output pixel (ho, wo)
  * samples channel c (offset group g = c / (C/G)) at
@@ -34,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MDCN_ABI_VERSION 1
+#define MDCN_ABI_VERSION 2
 
 typedef enum mdcn_status { MDCN_OK = 0, MDCN_ERR_ARGUMENT = -1, MDCN_ERR_HIP = -2 } mdcn_status;
 
@@ -77,6 +78,50 @@ int mdcn_im2col(int dtype, const void *input, const void *offset, const void *ma
 int mdcn_backward(int grads, int dtype, const void *input, const void *offset, const void *mask,
                   const void *grad_columns, const mdcn_shape *shape, void *grad_input_acc, void *grad_offset,
                   void *grad_mask, void *stream);
+
+/* ---- order-independent grad_input ---------------------------------------------------------------------------------
+ * mdcn_backward's grad_input is a sum of float atomics: its last bits depend on the order the adds arrive in.  The entry
+ * below computes the same sum so that every element depends only on the multiset of its terms.
+ *
+ * The term of (image n, output pixel (ho, wo), tap k, corner q, channel c of offset group g) is
+ *     t = (grad_columns[pix, k*C + c] * mask[n, g*K + k, ho, wo]) * w_q
+ * evaluated left to right in the arithmetic type with round-to-nearest products and no contraction (without a mask the
+ * first factor is grad_columns alone); w_q is the corner's bilinear weight exactly as mdcn_backward forms it:
+ * (1-ly)(1-lx), (1-ly)lx, ly(1-lx), ly lx for the fractional parts ly, lx of the sampling position.
+ *     grad_input[n, y, x, c] = (sum over the element's terms of  rne(t / q_n))  * q_n
+ * rne = round to nearest, ties to even, to an integer; the sum is exact (int64); the product with q_n is one rounding to
+ * the arithmetic type.  The quantum is one per image: q_n = 2^e, the smallest power of two with
+ *     A_n * G_n * bound <= 2^62 * q_n   (refined by up to three halvings while that still holds),
+ * A_n = the largest finite |mask| of image n (1 without a mask), G_n = the largest finite |grad_columns| of image n,
+ * bound = Ho*Wo*Kh*Kw: a tap's four corners are four different pixels, so an element receives at most one term per
+ * (output pixel, tap), and bilinear weights are at most 1 -- no sum overflows.
+ * Precision.  After the halvings A_n * G_n * bound > 2^61 * q_n, so q_n < A_n * G_n * bound * 2^-61: a term is off by at
+ * most q_n / 2 < A_n * G_n * bound * 2^-62, and an element by at most (the terms it receives) * q_n / 2
+ * <= A_n * G_n * bound^2 * 2^-62, before its one rounding to the arithmetic type.  The quantum grows with the map: at
+ * 90x160 outputs and a 3x3 kernel (bound < 2^17) that is q_n / 2 < A_n * G_n * 2^-45 per term and A_n * G_n * 2^-28 per
+ * element at the very most.  For fp32 arithmetic a term of magnitude A_n * G_n carries an ulp of 2^-24 of it, so the
+ * quantisation is below the rounding the float-atomic sum makes at every add.  For MDCN_F64 it is not: a double's ulp is
+ * 2^-53 of its magnitude, and q_n / 2 is coarser than that once bound exceeds about 2^9 (an 8x8 map with a 3x3 kernel) --
+ * on larger maps the fixed-point fp64 result is reproducible but LESS precise than the fp64 float-atomic sum (still about
+ * 2^-28 of A_n * G_n or better at the sizes above).
+ * A non-finite term adds nothing to the sum; the element becomes what IEEE summation gives (NaN with a NaN term or with
+ * infinities of both signs, else the infinity) and no other element is touched.
+ * So the bits of grad_input[n] depend on image n's own tensors only: not on the run, the launch geometry, the batch the
+ * image sits in, or how the caller cuts the batch into calls. */
+
+/* Bytes of the workspace of mdcn_backward_input_fixed for `batch` images: the int64 accumulators [batch, H, W, C], one
+ * class nibble per element (packed eight to a 32-bit word) and two 64-bit maxima per image, each of the three rounded up
+ * to a multiple of 256 bytes; negative on a bad argument.  (shape->N is ignored.)  Host arithmetic only. */
+long long mdcn_fixed_workspace_bytes(int dtype, const mdcn_shape *shape, int batch);
+
+/* grad_input of mdcn_im2col as defined above, in three enqueued passes (maxima, scatter, conversion).
+ *   grad_columns   [N*Ho*Wo, Kh*Kw*C], storage type; offset, mask (NULL: no modulation) as for mdcn_im2col;
+ *   workspace      at least mdcn_fixed_workspace_bytes(dtype, shape, shape->N) bytes, 256-byte aligned, uninitialised:
+ *                  the library zeroes what it needs;
+ *   grad_input     [N, H, W, C] in the ARITHMETIC type (float; double for MDCN_F64), fully written.
+ * There is no `input` pointer: grad_input does not depend on the input's values.  N == 0 is a no-op. */
+int mdcn_backward_input_fixed(int dtype, const void *offset, const void *mask, const void *grad_columns,
+                              const mdcn_shape *shape, void *workspace, void *grad_input, void *stream);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,11 @@ the machine: the oracle's PyTorch gather formulation (tests/dcn_oracle.py) on th
 operator as a third column where it can be imported.
 
     python scripts/dcn_bench.py [--out profiles/dcn_bench.json] [--windows 5] [--iters 5] [--no-trace]
+    python scripts/dcn_bench.py --reproducible [--out profiles/dcn_reproducible.json] ...
+
+--reproducible times something else: forward + backward of the operator with grad_input by float atomics (the default)
+and by the order-independent fixed-point sum (devis_amd.reproducible_grad_input), in alternating windows, and the forward
+alone to take it off both; the rocprofv3 child then runs the fixed-point backward, so the split shows its three passes.
 
 Device events after warm-up; operator and baseline windows alternate; the median window is quoted.  "hbm_fraction" is the
 algorithmic bytes (input + offset + mask + columns written and read + output; backward: twice that plus the weight
@@ -13,9 +18,11 @@ everything else (the GEMMs, layout copies).
 """
 import argparse
 import csv
+import functools
 import glob
 import json
 import os
+import re
 import shutil
 import statistics
 import subprocess
@@ -124,26 +131,53 @@ def bench(args):
     return rows
 
 
-def trace_child():
+def bench_reproducible(args):
+    """Rows of forward + backward with grad_input by float atomics and by the fixed-point sum, the backward taken as the
+    difference to the forward alone."""
+    import devis_amd
+    dev = torch.device("cuda:0")
+    pinned = functools.partial(devis_amd.deform_conv2d, reproducible_grad_input=True)
+    rows = []
+    for layer in LAYERS:
+        for dtype in (torch.float32, torch.bfloat16):
+            data = make(layer, dtype, dev)
+            steps = {"fwd": stepper(devis_amd.deform_conv2d, *data, False), "default": stepper(devis_amd.deform_conv2d, *data, True),
+                     "reproducible": stepper(pinned, *data, True)}
+            ms = time_alternating(steps, args.windows, args.iters)
+            bwd, bwd_fixed = ms["default"] - ms["fwd"], ms["reproducible"] - ms["fwd"]
+            row = {"layer": "C%d->%d %dx%d" % layer, "N": N, "dtype": str(dtype).replace("torch.", ""),
+                   "fwd_ms": round(ms["fwd"], 4), "fwd_bwd_ms": round(ms["default"], 4),
+                   "fwd_bwd_reproducible_ms": round(ms["reproducible"], 4),
+                   "fwd_bwd_factor": round(ms["reproducible"] / ms["default"], 2),
+                   "bwd_ms": round(bwd, 4), "bwd_reproducible_ms": round(bwd_fixed, 4), "bwd_factor": round(bwd_fixed / bwd, 2)}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del data, steps
+            torch.cuda.empty_cache()
+    return rows
+
+
+def trace_child(reproducible=False):
     """What the rocprofv3 child runs: the operator alone, 3 forward + backward steps per layer and dtype."""
     import devis_amd
     dev = torch.device("cuda:0")
+    fn = functools.partial(devis_amd.deform_conv2d, reproducible_grad_input=True) if reproducible else devis_amd.deform_conv2d
     for layer in LAYERS:
         for dtype in (torch.float32, torch.bfloat16):
-            step = stepper(devis_amd.deform_conv2d, *make(layer, dtype, dev), True)
+            step = stepper(fn, *make(layer, dtype, dev), True)
             for _ in range(3):
                 step()
     torch.cuda.synchronize()
 
 
-def kernel_split():
+def kernel_split(reproducible=False):
     """Share of the operator's kernel time in the project's kernels and in the rest, from one rocprofv3 run of a child."""
     if not shutil.which("rocprofv3"):
         return {"error": "rocprofv3 not found"}
     tmp = tempfile.mkdtemp(prefix="dcn_trace_")
     try:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--",
-               sys.executable, os.path.abspath(__file__), "--trace-child"]
+               sys.executable, os.path.abspath(__file__), "--trace-child"] + (["--reproducible"] if reproducible else [])
         done = subprocess.run(cmd, cwd=tmp, env=dict(os.environ, TMPDIR=tmp), stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                               timeout=280)
         if done.returncode != 0:
@@ -157,7 +191,7 @@ def kernel_split():
                 ns = int(r["TotalDurationNs"])
                 name = r["Name"]
                 if "mdcn_" in name:
-                    short = "mdcn_im2col_kernel" if "im2col" in name else "mdcn_backward_kernel"
+                    short = re.search(r"mdcn_\w+?_kernel", name).group(0)
                     ours[short] = ours.get(short, 0) + ns
                 else:
                     rest += ns
@@ -178,9 +212,23 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--no-trace", action="store_true")
     ap.add_argument("--trace-child", action="store_true")
+    ap.add_argument("--reproducible", action="store_true",
+                    help="time the order-independent grad_input against the default backward instead of the baselines")
     args = ap.parse_args()
     if args.trace_child:
-        trace_child()
+        trace_child(args.reproducible)
+        return
+    if args.reproducible:
+        doc = {"device": torch.cuda.get_device_name(0), "N": N, "windows": args.windows, "iters": args.iters,
+               "what": "deform_conv2d forward + backward, grad_input by float atomics (default) and by the fixed-point sum "
+                       "(reproducible_grad_input); bwd = fwd+bwd minus fwd", "rows": bench_reproducible(args)}
+        if not args.no_trace:
+            doc["kernel_split_fwd_bwd_reproducible"] = kernel_split(True)
+        text = json.dumps(doc, indent=1)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        print(text)
         return
     rows = bench(args)
     doc = {"device": torch.cuda.get_device_name(0), "N": N, "windows": args.windows, "iters": args.iters,
