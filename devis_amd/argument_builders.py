@@ -201,3 +201,20 @@ def patch_mask_head(deformable_segmentation_module):
 def unpatch_mask_head(deformable_segmentation_module, previous_class):
     """Undo :func:`patch_mask_head` (tests)."""
     deformable_segmentation_module.ModulatedDeformableConv2d = previous_class
+
+
+def patch_attention_maps(deformable_segmentation_module):
+    """Opt-in: make the reference's segmentation models (``src.models.deformable_segmentation``) build their
+    ``bbox_attention`` from :class:`devis_amd.modules.MultiScaleMHAttentionMap` -- the fused HIP operator instead of
+    einsum, masked_fill and softmax.  Call it before the model is built: the class is looked up by name at construction.
+    State dicts are interchangeable (same parameter names).  Returns the replaced class (to undo the patch;
+    :func:`unpatch_attention_maps`).  :func:`patch_mask_head` is a separate choice."""
+    from .modules import MultiScaleMHAttentionMap
+    previous = getattr(deformable_segmentation_module, "MultiScaleMHAttentionMap")
+    deformable_segmentation_module.MultiScaleMHAttentionMap = MultiScaleMHAttentionMap
+    return previous
+
+
+def unpatch_attention_maps(deformable_segmentation_module, previous_class):
+    """Undo :func:`patch_attention_maps` (tests)."""
+    deformable_segmentation_module.MultiScaleMHAttentionMap = previous_class

@@ -2,3 +2,4 @@
 from .ms_deform_attn_func import (MSDeformAttnFunction, MSDeformAttnTemporalFunction,  # noqa: F401
                                   ms_deform_attn_core_pytorch, project_value,
                                   MSDeformPrepFunction, MSDeformPrepFusedFunction)
+from .attention_maps import AttentionMapsFunction  # noqa: F401  (the mask head's attention maps: include/attmap.h)

@@ -19,6 +19,8 @@ through the C ABI, the same numbers -- and whose fake implementation gives shape
 ``deform_conv2d_pinned``       the same forward for a call that pins how its backward sums grad_input (the module's
                                ``reproducible_grad_input`` attribute): a constant of the graph, handed to the backward op
                                as a PIN_* bit of ``grads``
+``attention_maps``             the mask head's attention maps (:func:`attention_maps`; include/attmap.h);
+                               ``attention_maps_backward`` computes the gradients its ``grads`` mask names
 =============================  ==========================================================================================
 
 Everything that reads the host or keeps Python state -- the ``spatial_shapes`` host hint, the frame-table cache, the
@@ -38,6 +40,7 @@ import torch
 from torch import Tensor
 
 from . import _native
+from .functions import attention_maps as _A
 from .functions import deform_conv as _D
 from .functions import ms_deform_attn_func as _F
 
@@ -518,3 +521,62 @@ def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0
     if reproducible_grad_input is None:
         return deform_conv2d_op(input, offset, weight, bias, *geometry, mask)
     return deform_conv2d_pinned_op(input, offset, weight, bias, *geometry, mask, bool(reproducible_grad_input))
+
+
+# ---- the mask head's attention maps (include/attmap.h) ---------------------------------------------------------------
+
+@_op("attention_maps")
+def attention_maps_op(q: Tensor, k: Tensor, mask: Optional[Tensor], num_heads: int, scale: float,
+                      out_dtype: Optional[torch.dtype] = None) -> Tensor:
+    """``attention_maps`` with every argument given: [B, Q, n, H, W]."""
+    return _A._forward(q, k, mask, num_heads, scale, out_dtype)
+
+
+@attention_maps_op.register_fake
+def _(q, k, mask, num_heads, scale, out_dtype=None):
+    B, Q, n, c, H, W, odt = _A.check_shapes(q, k, mask, num_heads, out_dtype)
+    return _empty(q, (B, Q, n, H, W), odt)
+
+
+@_op("attention_maps_backward")
+def attention_maps_backward(grad_out: Tensor, q: Tensor, k: Tensor, out: Tensor, num_heads: int, scale: float,
+                            grads: int) -> tuple[Tensor, Tensor]:
+    """(grad_q, grad_k) for the gradients in ``grads`` (``NEED_*`` of devis_amd/functions/attention_maps.py); the other
+    is a 0-element tensor."""
+    res = _A._backward(grad_out, q, k, out, num_heads, scale, grads)
+    return _fill_slots(res, _fake_attention_maps_backward(grad_out, q, k, out, num_heads, scale, grads))
+
+
+@attention_maps_backward.register_fake
+def _fake_attention_maps_backward(grad_out, q, k, out, num_heads, scale, grads):
+    _A._require(0 <= grads <= _A.NEED_ALL, "grads must be a mask of NEED_Q and NEED_K")
+    return (_empty(q, q.shape if grads & _A.NEED_Q else (0,)), _empty(k, k.shape if grads & _A.NEED_K else (0,)))
+
+
+def _setup_attention_maps(ctx, inputs, output):
+    q, k, mask, num_heads, scale = inputs[:5]
+    ctx.num_heads, ctx.scale = num_heads, scale
+    ctx.save_for_backward(q, k, output)
+
+
+def _backward_attention_maps(ctx, grad_out):
+    q, k, out = ctx.saved_tensors
+    grads = _A.grads_mask(ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+    gq, gk = none_slots(attention_maps_backward(grad_out, q, k, out, ctx.num_heads, ctx.scale, grads))
+    return gq, gk, None, None, None, None
+
+
+attention_maps_op.register_autograd(_backward_attention_maps, setup_context=_setup_attention_maps)
+
+
+def attention_maps(q, k, mask=None, *, num_heads, scale=None, out_dtype=None):
+    """The attention maps of DeVIS's mask head (``MultiScaleMHAttentionMap``, one level) on the fused HIP kernels of
+    include/attmap.h: ``softmax`` over all heads and pixels of ``scale * einsum("bqnc,bnchw->bqnhw", q, k)``, with the
+    pixels where ``mask`` [B, H, W] is True at -inf.  ``q`` [B, Q, n*c], ``k`` [B, n*c, H, W] (f32 / f64 / bf16 / f16, the same
+    for both) -> [B, Q, n, H, W] in ``out_dtype``: the inputs' dtype, or float32 beside 16-bit inputs.  ``scale`` defaults to
+    ``c ** -0.5``.  A masked pixel is exactly 0; a row whose pixels are all masked is NaN.  GPU tensors only.  Every result is
+    bitwise reproducible."""
+    scale = _A.default_scale(q, num_heads) if scale is None else float(scale)
+    if torch.compiler.is_compiling():
+        return attention_maps_op(q, k, mask, num_heads, scale, out_dtype)
+    return _A.AttentionMapsFunction.apply(q, k, mask, num_heads, scale, out_dtype)
