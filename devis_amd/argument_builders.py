@@ -218,3 +218,22 @@ def patch_attention_maps(deformable_segmentation_module):
 def unpatch_attention_maps(deformable_segmentation_module, previous_class):
     """Undo :func:`patch_attention_maps` (tests)."""
     deformable_segmentation_module.MultiScaleMHAttentionMap = previous_class
+
+
+def patch_mask_head_stages(deformable_segmentation_module):
+    """Opt-in: make the reference's segmentation models (``src.models.deformable_segmentation``) build their ``mask_head``
+    from :class:`devis_amd.modules.MaskHeadConv` -- GroupNorm, ReLU, upsampling, the FPN add and the concatenation of the
+    attention maps as one fused HIP operator per stage, and the deformable convolutions as
+    :class:`devis_amd.modules.ModulatedDeformableConv2d`.  Call it before the model is built: the class is looked up by
+    name at construction.  State dicts are interchangeable (same parameter names).  Returns the replaced class (to undo the
+    patch; :func:`unpatch_mask_head_stages`).  :func:`patch_mask_head` and :func:`patch_attention_maps` are separate
+    choices."""
+    from .modules import MaskHeadConv
+    previous = getattr(deformable_segmentation_module, "MaskHeadConv")
+    deformable_segmentation_module.MaskHeadConv = MaskHeadConv
+    return previous
+
+
+def unpatch_mask_head_stages(deformable_segmentation_module, previous_class):
+    """Undo :func:`patch_mask_head_stages` (tests)."""
+    deformable_segmentation_module.MaskHeadConv = previous_class

@@ -3,3 +3,4 @@ from .ms_deform_attn_func import (MSDeformAttnFunction, MSDeformAttnTemporalFunc
                                   ms_deform_attn_core_pytorch, project_value,
                                   MSDeformPrepFunction, MSDeformPrepFusedFunction)
 from .attention_maps import AttentionMapsFunction  # noqa: F401  (the mask head's attention maps: include/attmap.h)
+from .mask_head_stage import MaskHeadStageFunction  # noqa: F401  (one stage of the mask head's glue: include/mhstage.h)

@@ -3,3 +3,4 @@ from .ms_deform_attn import (MSDeformAttn, TemporalMSDeformAttnBase,  # noqa: F4
                              TemporalMSDeformAttnDecoder, TemporalMSDeformAttnEncoder)
 from .deform_conv import ModulatedDeformableConv2d  # noqa: F401  (reference src/models/deformable_segmentation.py)
 from .attention_maps import MultiScaleMHAttentionMap  # noqa: F401  (reference src/models/deformable_segmentation.py)
+from .mask_head import MaskHeadConv  # noqa: F401  (reference src/models/deformable_segmentation.py)

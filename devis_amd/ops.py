@@ -21,6 +21,9 @@ through the C ABI, the same numbers -- and whose fake implementation gives shape
                                as a PIN_* bit of ``grads``
 ``attention_maps``             the mask head's attention maps (:func:`attention_maps`; include/attmap.h);
                                ``attention_maps_backward`` computes the gradients its ``grads`` mask names
+``mask_head_stage``            one GroupNorm-ReLU-upsample-merge stage of the mask head (:func:`mask_head_stage`;
+                               include/mhstage.h) -> (out in channels-last memory, mean, rstd);
+                               ``mask_head_stage_backward`` computes the gradients its ``grads`` mask names
 =============================  ==========================================================================================
 
 Everything that reads the host or keeps Python state -- the ``spatial_shapes`` host hint, the frame-table cache, the
@@ -42,6 +45,7 @@ from torch import Tensor
 from . import _native
 from .functions import attention_maps as _A
 from .functions import deform_conv as _D
+from .functions import mask_head_stage as _S
 from .functions import ms_deform_attn_func as _F
 
 
@@ -580,3 +584,80 @@ def attention_maps(q, k, mask=None, *, num_heads, scale=None, out_dtype=None):
     if torch.compiler.is_compiling():
         return attention_maps_op(q, k, mask, num_heads, scale, out_dtype)
     return _A.AttentionMapsFunction.apply(q, k, mask, num_heads, scale, out_dtype)
+
+
+# ---- one stage of the mask head's glue (include/mhstage.h) -------------------------------------------------------------
+
+@_op("mask_head_stage")
+def mask_head_stage_op(x: Tensor, num_groups: int, weight: Tensor, bias: Tensor, eps: float, skip: Optional[Tensor],
+                       skip_index: Optional[Tensor], extra: Optional[Tensor],
+                       out_dtype: Optional[torch.dtype] = None) -> tuple[Tensor, Tensor, Tensor]:
+    """``mask_head_stage`` with every argument given: (out [N, C+E, H, W] in channels-last memory, mean, rstd [N, G])."""
+    return _S._forward(x, num_groups, weight, bias, eps, skip, skip_index, extra, out_dtype)
+
+
+@mask_head_stage_op.register_fake
+def _(x, num_groups, weight, bias, eps, skip, skip_index, extra, out_dtype=None):
+    N, F, C, G, E, h, w, H, W, odt = _S.check_shapes(x, num_groups, weight, bias, skip, skip_index, extra, out_dtype)
+    acc = _native.acc_dtype(x.dtype)
+    out = torch.empty((N, C + E, H, W), dtype=odt, device=x.device, memory_format=torch.channels_last)
+    return out, _empty(x, (N, G), acc), _empty(x, (N, G), acc)
+
+
+@_op("mask_head_stage_backward")
+def mask_head_stage_backward(grad_out: Tensor, x: Tensor, weight: Tensor, bias: Tensor, mean: Tensor, rstd: Tensor,
+                             skip_index: Optional[Tensor], num_groups: int, num_skip: int,
+                             grads: int) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(grad_x, grad_weight, grad_bias, grad_skip) for the gradients in ``grads`` (``NEED_*`` of
+    devis_amd/functions/mask_head_stage.py); the others are 0-element tensors.  ``num_skip`` is F."""
+    res = _S._backward(grad_out, x, weight, bias, mean, rstd, skip_index, num_groups, num_skip, grads)
+    return _fill_slots(res, _fake_mask_head_stage_backward(grad_out, x, weight, bias, mean, rstd, skip_index, num_groups,
+                                                           num_skip, grads))
+
+
+@mask_head_stage_backward.register_fake
+def _fake_mask_head_stage_backward(grad_out, x, weight, bias, mean, rstd, skip_index, num_groups, num_skip, grads):
+    _S._require(0 <= grads <= _S.NEED_ALL, "grads must be a mask of the NEED_* bits")
+    C, H, W = x.shape[1], grad_out.shape[2], grad_out.shape[3]
+    return (_empty(x, x.shape if grads & _S.NEED_X else (0,)), _empty(weight, weight.shape if grads & _S.NEED_WEIGHT else (0,)),
+            _empty(bias, bias.shape if grads & _S.NEED_BIAS else (0,)),
+            _empty(x, (num_skip, C, H, W) if grads & _S.NEED_SKIP else (0,)))
+
+
+def _setup_mask_head_stage(ctx, inputs, output):
+    x, num_groups, weight, bias, eps, skip, skip_index, extra = inputs[:8]
+    ctx.num_groups = num_groups
+    ctx.num_skip = 0 if skip is None else skip.shape[0]
+    ctx.extra_dtype = None if extra is None else extra.dtype
+    ctx.save_for_backward(x, weight, bias, output[1], output[2], skip_index)
+
+
+def _backward_mask_head_stage(ctx, grad_out, grad_mean, grad_rstd):
+    x, weight, bias, mean, rstd, skip_index = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    grads = _S.grads_mask(need[0], need[2], need[3], need[5], need[7])
+    gx, gw, gb, gs = none_slots(mask_head_stage_backward(grad_out, x, weight, bias, mean, rstd, skip_index, ctx.num_groups,
+                                                         ctx.num_skip, grads))
+    ge = _S.grad_extra_of(grad_out, x.shape[1], ctx.extra_dtype) if grads & _S.NEED_EXTRA else None
+    return gx, None, gw, gb, None, gs, None, ge, None
+
+
+mask_head_stage_op.register_autograd(_backward_mask_head_stage, setup_context=_setup_mask_head_stage)
+
+
+def mask_head_stage(x, num_groups, weight, bias, eps=1e-5, *, skip=None, skip_index=None, extra=None, out_dtype=None):
+    """One stage of the glue of DeVIS's mask head (``MaskHeadConv``, between two of its convolutions) on the fused HIP
+    kernels of include/mhstage.h::
+
+        y   = relu(group_norm(x, num_groups, weight, bias, eps))                     x [N, C, h, w]
+        y   = F.interpolate(y, size=(H, W), mode="nearest") + skip[skip_index]       skip [F, C, H, W], skip_index [N]
+        out = cat([y, extra], 1)                                                     extra [N, E, H, W]
+
+    ``skip``, ``skip_index`` (None: the identity, F == N) and ``extra`` are optional; (H, W) comes from ``skip``, else from
+    ``extra``, else it is (h, w).  x and skip are f32 / f64 / bf16 / f16 alike; weight / bias, extra and ``out_dtype`` are
+    that dtype, or float32 beside a 16-bit x.  ``out`` has the logical shape [N, C+E, H, W] in channels-last memory,
+    always.  ``skip_index`` values outside [0, F) are the caller's contract (a device tensor is not read on the host).  GPU
+    tensors only.  out and every gradient are bitwise reproducible."""
+    if torch.compiler.is_compiling():
+        return mask_head_stage_op(x, num_groups, weight, bias, float(eps), skip, skip_index, extra, out_dtype)[0]
+    return _S.MaskHeadStageFunction.apply(x, num_groups, weight, bias, float(eps), skip, skip_index, extra, out_dtype)
