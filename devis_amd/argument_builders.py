@@ -237,3 +237,50 @@ def patch_mask_head_stages(deformable_segmentation_module):
 def unpatch_mask_head_stages(deformable_segmentation_module, previous_class):
     """Undo :func:`patch_mask_head_stages` (tests)."""
     deformable_segmentation_module.MaskHeadConv = previous_class
+
+
+def pad_masks(masks):
+    """The targets' mask stacks ``[n_i, H_i, W_i]`` as one zero-padded ``[B, max n, max H, max W]`` tensor in their own
+    dtype (bool stays bool): what the reference's nested tensor holds, without its padding mask."""
+    size = [max(m.shape[d] for m in masks) for d in range(3)]
+    out = masks[0].new_zeros([len(masks)] + size)
+    for slot, m in zip(out, masks):
+        slot[:m.shape[0], :m.shape[1], :m.shape[2]].copy_(m)
+    return out
+
+
+def loss_masks(self, outputs, targets, indices, num_boxes):
+    """A drop-in for the reference's ``SetCriterion.loss_masks`` (``self`` is the criterion) on :func:`devis_amd.mask_losses`:
+    the same choice of target masks -- image matchings ``(src, tgt)`` and DeVIS's ``(src, tgt, mask)`` ones, whose
+    predictions are filtered by the first clip's mask when that mask selects nothing -- and the same padding of the targets
+    to the largest size, but the bool targets stay bool and the logits stay small: resampling, focal loss and dice loss are
+    one operator.  Returns ``{"loss_mask", "loss_dice"}``."""
+    from .ops import mask_losses
+    assert "pred_masks" in outputs
+    src_masks = outputs["pred_masks"]
+    if len(indices[0]) == 3:
+        keep = indices[0][2]
+        if not torch.any(keep):
+            tgt_idx = self._get_tgt_permutation_masked_idx(indices)
+            src_masks = src_masks[keep]
+        else:
+            tgt_idx = self._get_tgt_permutation_idx(indices, True)
+    else:
+        tgt_idx = self._get_tgt_permutation_idx(indices)        # (the predictions are [N, 1, h, w] here: taken as they are)
+    target_masks = pad_masks([t["masks"] for t in targets])[tgt_idx]
+    return mask_losses(src_masks, target_masks, num_boxes)
+
+
+def patch_mask_losses(criterion_module):
+    """Opt-in: make the reference's criterion (``src.models.criterion``) compute its mask losses with :func:`loss_masks` --
+    the fused HIP operator instead of interpolate, sigmoid_focal_loss and dice_loss.  Takes effect at once, also for
+    criteria that already exist (the method is looked up on the class).  Returns the replaced function (to undo the patch;
+    :func:`unpatch_mask_losses`).  The other patches are separate choices."""
+    previous = criterion_module.SetCriterion.loss_masks
+    criterion_module.SetCriterion.loss_masks = loss_masks
+    return previous
+
+
+def unpatch_mask_losses(criterion_module, previous):
+    """Undo :func:`patch_mask_losses` (tests)."""
+    criterion_module.SetCriterion.loss_masks = previous

@@ -42,7 +42,7 @@ HIPCC_FLAGS = [
 
 
 def include_dir():
-    """Directory of msda.h, mdcn.h, attmap.h and mhstage.h: <repo>/include (the canonical copy, next to the package) or, for a relocated package,
+    """Directory of msda.h, mdcn.h, attmap.h, mhstage.h and maskloss.h: <repo>/include (the canonical copy, next to the package) or, for a relocated package,
     a copy shipped inside it (devis_amd/include)."""
     for d in (os.path.join(ROOT, "include"), os.path.join(HERE, "include")):
         if os.path.exists(os.path.join(d, "msda.h")):
@@ -57,7 +57,7 @@ def sources():
 def _headers():
     inc = include_dir()
     return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc"))) + \
-        ([os.path.join(inc, "msda.h"), os.path.join(inc, "mdcn.h"), os.path.join(inc, "attmap.h"), os.path.join(inc, "mhstage.h")] if inc else [])
+        ([os.path.join(inc, "msda.h"), os.path.join(inc, "mdcn.h"), os.path.join(inc, "attmap.h"), os.path.join(inc, "mhstage.h"), os.path.join(inc, "maskloss.h")] if inc else [])
 
 
 def _lib_override():

@@ -24,6 +24,8 @@ through the C ABI, the same numbers -- and whose fake implementation gives shape
 ``mask_head_stage``            one GroupNorm-ReLU-upsample-merge stage of the mask head (:func:`mask_head_stage`;
                                include/mhstage.h) -> (out in channels-last memory, mean, rstd);
                                ``mask_head_stage_backward`` computes the gradients its ``grads`` mask names
+``mask_loss_terms``            the mask loss (:func:`mask_loss_terms`; include/maskloss.h) -> (focal [N], dice [N], the
+                               [N, 3] sums the backward needs); ``mask_loss_terms_backward`` computes grad_src
 =============================  ==========================================================================================
 
 Everything that reads the host or keeps Python state -- the ``spatial_shapes`` host hint, the frame-table cache, the
@@ -46,6 +48,7 @@ from . import _native
 from .functions import attention_maps as _A
 from .functions import deform_conv as _D
 from .functions import mask_head_stage as _S
+from .functions import mask_losses as _L
 from .functions import ms_deform_attn_func as _F
 
 
@@ -661,3 +664,82 @@ def mask_head_stage(x, num_groups, weight, bias, eps=1e-5, *, skip=None, skip_in
     if torch.compiler.is_compiling():
         return mask_head_stage_op(x, num_groups, weight, bias, float(eps), skip, skip_index, extra, out_dtype)[0]
     return _S.MaskHeadStageFunction.apply(x, num_groups, weight, bias, float(eps), skip, skip_index, extra, out_dtype)
+
+
+# ---- the mask loss (include/maskloss.h) --------------------------------------------------------------------------------
+
+@_op("mask_loss_terms")
+def mask_loss_terms_op(src: Tensor, target: Tensor, alpha: float, gamma: float) -> tuple[Tensor, Tensor, Tensor]:
+    """``mask_loss_terms`` on [N, h, w] logits with every argument given: (focal [N], dice [N], sums [N, 3])."""
+    return _L._forward(src, target, alpha, gamma)
+
+
+@mask_loss_terms_op.register_fake
+def _(src, target, alpha, gamma):
+    N = _L.check_shapes(src, target)[0]
+    _L.check_gamma(gamma)
+    acc = _native.acc_dtype(src.dtype)
+    return _empty(src, (N,), acc), _empty(src, (N,), acc), _empty(src, (N, 3), acc)
+
+
+@_op("mask_loss_terms_backward")
+def mask_loss_terms_backward(grad_focal: Tensor, grad_dice: Tensor, src: Tensor, target: Tensor, sums: Tensor,
+                             alpha: float, gamma: float) -> Tensor:
+    """grad_src [N, h, w] in src's dtype."""
+    return _L._backward(grad_focal, grad_dice, src, target, sums, alpha, gamma)
+
+
+@mask_loss_terms_backward.register_fake
+def _(grad_focal, grad_dice, src, target, sums, alpha, gamma):
+    return _empty(src, src.shape)
+
+
+def _setup_mask_loss_terms(ctx, inputs, output):
+    src, target, alpha, gamma = inputs
+    ctx.alpha, ctx.gamma = alpha, gamma
+    ctx.save_for_backward(src, target, output[2])
+
+
+def _backward_mask_loss_terms(ctx, grad_focal, grad_dice, grad_sums):
+    if not ctx.needs_input_grad[0]:
+        return None, None, None, None
+    src, target, sums = ctx.saved_tensors
+    return mask_loss_terms_backward(grad_focal, grad_dice, src, target, sums, ctx.alpha, ctx.gamma), None, None, None
+
+
+mask_loss_terms_op.register_autograd(_backward_mask_loss_terms, setup_context=_setup_mask_loss_terms)
+
+
+def mask_loss_terms(src_masks, target_masks, alpha=0.25, gamma=2.0):
+    """The per-instance terms of DeVIS's mask loss (``SetCriterion.loss_masks``) on the fused HIP kernels of
+    include/maskloss.h::
+
+        x     = F.interpolate(src_masks[:, None], size=(H, W), mode="bilinear", align_corners=False)[:, 0].flatten(1)
+        t     = target_masks.flatten(1).to(x)
+        focal = sigmoid_focal_loss(x, t, alpha, gamma) without its reduction over instances: the mean over pixels, [N]
+        dice  = 1 - (2 * (x.sigmoid() * t).sum(1) + 1) / (x.sigmoid().sum(1) + t.sum(1) + 1)                     [N]
+
+    ``src_masks`` [N, h, w] or [N, 1, h, w] logits (f32 / f64 / bf16 / f16), ``target_masks`` [N, H, W]: bool or uint8
+    (nonzero is 1; one byte per pixel is all the operator reads), or floating -- float32 or the logits' dtype -- taken as it
+    is.  The results are float32 (float64 for float64 logits), also under autocast, which leaves the logits as they are.
+    ``alpha < 0`` switches the class weighting off; ``gamma`` is 0, 1 or larger than 1 (ValueError otherwise).  Only
+    ``src_masks`` has a gradient; a floating target that requires one raises.  Nothing of the target's resolution is
+    allocated, forward or backward.  GPU tensors only.  Every result is bitwise reproducible."""
+    gamma = _L.check_gamma(gamma)
+    if src_masks.dim() == 4:
+        _L._require(src_masks.shape[1] == 1, "mask_loss_terms: src_masks must be [N, h, w] or [N, 1, h, w], got %s"
+                    % (tuple(src_masks.shape),))
+        src_masks = src_masks[:, 0]
+    _L._require(not (target_masks.is_floating_point() and target_masks.requires_grad),
+                "mask_loss_terms: target_masks has no gradient (detach it)")
+    if torch.compiler.is_compiling():
+        return mask_loss_terms_op(src_masks, target_masks, float(alpha), gamma)[:2]
+    return _L.MaskLossTermsFunction.apply(src_masks, target_masks, float(alpha), gamma)
+
+
+def mask_losses(src_masks, target_masks, num_boxes, alpha=0.25, gamma=2.0):
+    """DeVIS's pair of mask losses from the matched logit maps and their targets: ``{"loss_mask": sum of the focal terms /
+    num_boxes, "loss_dice": sum of the dice terms / num_boxes}`` of :func:`mask_loss_terms`.  ``num_boxes`` is a number or a
+    tensor, as in the reference; the two tiny reductions stay in torch."""
+    focal, dice = mask_loss_terms(src_masks, target_masks, alpha, gamma)
+    return {"loss_mask": focal.sum() / num_boxes, "loss_dice": dice.sum() / num_boxes}
