@@ -487,3 +487,32 @@ def test_split_k_weight_gradient_on_16_bit_inputs_is_as_accurate_as_one_gemm():
     rounded = rms((torch.bmm(g[:28 * 1024].view(28, 1024, -1).transpose(1, 2), x[:28 * 1024].view(28, 1024, -1)).sum(0, dtype=torch.float32)
                    + (g[28 * 1024:].t() @ x[28 * 1024:]).float()).to(torch.bfloat16))
     assert rounded > single * 1.2                                   # what round 5 shipped: measurably worse
+
+
+def test_grad_value_dtype_of_operands_that_are_not_16_byte_aligned_is_answered_on_the_host(monkeypatch):
+    """A 16-bit `value` or `grad_out` view at an odd storage offset takes grad_value in the arithmetic type (the library would
+    refuse the storage type there: csrc/msda_api.hip fast_path_takes), and float64 never has another: all three answers come
+    from the pointers and dtypes alone, without the library."""
+    from devis_amd import _native
+
+    def no_library():
+        raise AssertionError("grad_value_dtype loaded the library")
+    monkeypatch.setattr(_native, "load", no_library)
+    S, M, D, Lq, L, P = 40, 8, 32, 10, 2, 4
+    shapes = torch.tensor([[4, 8], [2, 4]])
+
+    def view(dtype, k, shape):
+        n = int(np.prod(shape))
+        t = torch.zeros(n + 16, dtype=dtype)
+        t = t[(-t.data_ptr() % 16) // t.element_size():]            # (a 16-byte boundary, wherever the allocator put the buffer)
+        return t[k:k + n].view(shape)
+    for dtype in (torch.bfloat16, torch.float16):
+        value = view(dtype, 1, (2, S, M, D))
+        assert value.is_contiguous() and value.data_ptr() % 16 == 2
+        assert _native.grad_value_dtype(value, shapes, Lq, L, P) == torch.float32
+        value, grad_out = view(dtype, 0, (2, S, M, D)), view(dtype, 4, (2, Lq, M * D))
+        assert value.data_ptr() % 16 == 0 and grad_out.data_ptr() % 16 == 8
+        assert _native.grad_value_dtype(value, shapes, Lq, L, P, grad_out=grad_out) == torch.float32
+        assert _native.grad_value_dtype(value, shapes, Lq, L, P, clips=1, window=1, Pt=4, grad_out=grad_out) == torch.float32
+    for k in (0, 1):
+        assert _native.grad_value_dtype(view(torch.float64, k, (2, S, M, D)), shapes, Lq, L, P) == torch.float64

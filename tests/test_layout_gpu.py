@@ -97,22 +97,28 @@ def _np(t):
     return None if t is None else t.double().cpu().numpy()
 
 
-def run_op(r, dtype, grads=3, step=None):
+def _in_place(name, t):
+    return t
+
+
+def run_op(r, dtype, grads=3, step=None, place=_in_place):
     """msda_forward / msda_backward(_grads) on a (relaid) plain call, batch rows in chunks of `step` (the im2col_step loop of
-    ms_deform_attn_cuda.cu:61-75).  grad_value starts as NaN.  Returns the outputs and the (forward, backward) routes."""
+    ms_deform_attn_cuda.cu:61-75).  grad_value starts as NaN.  Returns the outputs and the (forward, backward) routes.
+    `place(name, tensor)` returns the tensor the library is handed for operand or output `name` (tests/test_unaligned_gpu.py:
+    the same numbers in other memory); by default the tensor itself."""
     from devis_amd import _native
-    v, loc, aw, go = (_t(r[k], dtype).contiguous() for k in ("value", "loc", "aw", "grad_out"))
+    v, loc, aw, go = (place(k, _t(r[k], dtype).contiguous()) for k in ("value", "loc", "aw", "grad_out"))
     shapes, lsi = _t(r["shapes"]), _t(r["lsi"])
     N, S, M, D = v.shape
     _, Lq, _, L, P, _ = loc.shape
     step = step or N
-    out = torch.full((N, Lq, M * D), float("nan"), dtype=dtype, device=DEV)
+    out = place("out", torch.full((N, Lq, M * D), float("nan"), dtype=dtype, device=DEV))
     for n in range(0, N, step):
         _native.forward(v[n:n + step], shapes, lsi, loc[n:n + step], aw[n:n + step], out[n:n + step])
     rf = _native.last_route()
-    gv = torch.full(v.shape, float("nan"), device=DEV,
-                    dtype=_native.grad_value_dtype(v[:step], shapes, Lq, L, P, grad_out=go)) if grads & 1 else None
-    gl, ga = (torch.full_like(x, float("nan")) for x in (loc, aw)) if grads & 2 else (None, None)
+    gv = place("grad_value", torch.full(v.shape, float("nan"), device=DEV,
+                                        dtype=_native.grad_value_dtype(v[:step], shapes, Lq, L, P, grad_out=go))) if grads & 1 else None
+    gl, ga = (place(k, torch.full_like(x, float("nan"))) for k, x in (("grad_loc", loc), ("grad_aw", aw))) if grads & 2 else (None, None)
     c = lambda x, n: None if x is None else x[n:n + step]                  # noqa: E731
     for n in range(0, N, step):
         args = (v[n:n + step], shapes, lsi, loc[n:n + step], aw[n:n + step], go[n:n + step], c(gv, n), c(gl, n), c(ga, n))
@@ -125,20 +131,23 @@ def run_op(r, dtype, grads=3, step=None):
     return [_np(x) for x in (out, gv, gl, ga)], (rf, rb)
 
 
-def run_temporal(r, dtype, clips=1, grads=3):
-    """msda_temporal_forward / msda_temporal_backward(_grads) on a (relaid) fused temporal call; grad_value starts as NaN."""
+def run_temporal(r, dtype, clips=1, grads=3, place=_in_place):
+    """msda_temporal_forward / msda_temporal_backward(_grads) on a (relaid) fused temporal call; grad_value starts as NaN.
+    `place`: as for run_op."""
     from devis_amd import _native
-    v, lc, ac, lt, at, go = (_t(r[k], dtype).contiguous() for k in ("value", "loc_c", "aw_c", "loc_t", "aw_t", "grad_out"))
+    v, lc, ac, lt, at, go = (place(k, _t(r[k], dtype).contiguous()) for k in ("value", "loc_c", "aw_c", "loc_t", "aw_t", "grad_out"))
     shapes, lsi, ftab = _t(r["shapes"]), _t(r["lsi"]), _t(r["ftab"])
     G, S, M, D = v.shape
     _, Lq, _, L, Pc, _ = lc.shape
     W, Pt = ftab.shape[1], lt.shape[4]
-    out = torch.full((G, Lq, M * D), float("nan"), dtype=dtype, device=DEV)
+    out = place("out", torch.full((G, Lq, M * D), float("nan"), dtype=dtype, device=DEV))
     _native.temporal_forward(v, shapes, lsi, ftab, lc, ac, lt, at, clips, out)
     rf = _native.last_route()
-    gv = torch.full(v.shape, float("nan"), device=DEV, dtype=_native.grad_value_dtype(v, shapes, Lq, L, Pc, clips=clips, window=W,
-                                                                                       Pt=Pt, grad_out=go)) if grads & 1 else None
-    gs = [torch.full_like(x, float("nan")) for x in (lc, ac, lt, at)] if grads & 2 else [None] * 4
+    gv = place("grad_value", torch.full(v.shape, float("nan"), device=DEV,
+                                        dtype=_native.grad_value_dtype(v, shapes, Lq, L, Pc, clips=clips, window=W, Pt=Pt,
+                                                                       grad_out=go))) if grads & 1 else None
+    gs = [place("grad_" + k, torch.full_like(x, float("nan")))
+          for k, x in (("loc_c", lc), ("aw_c", ac), ("loc_t", lt), ("aw_t", at))] if grads & 2 else [None] * 4
     if grads == 3:
         _native.temporal_backward(v, shapes, lsi, ftab, lc, ac, lt, at, go, clips, gv, *gs)
     else:
