@@ -3,11 +3,10 @@ opens).  As in ``_mdcn``: no fallback, a failing call raises, launches go to the
 allocates nor synchronises -- outputs and workspaces are torch tensors of the caller.
 """
 import ctypes
-import threading
 
 import torch
 
-from . import _native
+from . import _binding, _native
 
 ATTMAP_ABI_VERSION = 1
 GRAD_Q, GRAD_K = 1, 2       # include/attmap.h ATTMAP_GRAD_Q / ATTMAP_GRAD_K
@@ -15,8 +14,6 @@ GRAD_Q, GRAD_K = 1, 2       # include/attmap.h ATTMAP_GRAD_Q / ATTMAP_GRAD_K
 EXPORTED_SYMBOLS = ("attmap_version", "attmap_last_error", "attmap_workspace_bytes", "attmap_forward", "attmap_backward")
 
 _vp, _ci = ctypes.c_void_p, ctypes.c_int
-_lib = None
-_lock = threading.Lock()
 
 
 class Shape(ctypes.Structure):
@@ -24,40 +21,18 @@ class Shape(ctypes.Structure):
     _fields_ = [(name, _ci) for name in ("B", "Q", "n", "c", "H", "W")]
 
 
-def load():
-    """The library with the attmap_* prototypes set; raises RuntimeError when it cannot be loaded or is another version."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is not None:
-            return _lib
-        lib = _native.load()
-        for name in EXPORTED_SYMBOLS:
-            if not hasattr(lib, name):
-                raise RuntimeError("devis_amd: the HIP library does not export %s; rebuild with "
-                                   "python -m devis_amd.build --force" % name)
-        lib.attmap_version.restype = _ci
-        lib.attmap_last_error.restype = ctypes.c_char_p
-        if lib.attmap_version() != ATTMAP_ABI_VERSION:
-            raise RuntimeError("devis_amd: attmap ABI version mismatch (library %d, binding %d); rebuild with "
-                               "python -m devis_amd.build --force" % (lib.attmap_version(), ATTMAP_ABI_VERSION))
-        shape_p = ctypes.POINTER(Shape)
-        lib.attmap_workspace_bytes.restype = ctypes.c_longlong
-        lib.attmap_workspace_bytes.argtypes = [_ci, shape_p]
-        lib.attmap_forward.restype = _ci
-        lib.attmap_forward.argtypes = [_ci, _ci, _vp, _vp, _vp, shape_p, ctypes.c_double, _vp, _vp, _vp]
-        lib.attmap_backward.restype = _ci
-        lib.attmap_backward.argtypes = [_ci, _ci, _ci, _vp, _vp, shape_p, ctypes.c_double, _vp, _vp, _vp]
-        _lib = lib
-    return _lib
+def _prototypes(lib):
+    shape_p = ctypes.POINTER(Shape)
+    lib.attmap_workspace_bytes.restype = ctypes.c_longlong
+    lib.attmap_workspace_bytes.argtypes = [_ci, shape_p]
+    lib.attmap_forward.restype = _ci
+    lib.attmap_forward.argtypes = [_ci, _ci, _vp, _vp, _vp, shape_p, ctypes.c_double, _vp, _vp, _vp]
+    lib.attmap_backward.restype = _ci
+    lib.attmap_backward.argtypes = [_ci, _ci, _ci, _vp, _vp, shape_p, ctypes.c_double, _vp, _vp, _vp]
 
 
-def _check(rc, what):
-    if rc < 0:
-        msg = load().attmap_last_error().decode("utf-8", "replace")
-        raise RuntimeError("devis_amd: %s failed (status %d): %s" % (what, rc, msg))
-    return rc
+# load(): the library with the attmap_* prototypes set; raises RuntimeError when it cannot be loaded or is another version
+load, _check = _binding.bind("attmap", ATTMAP_ABI_VERSION, EXPORTED_SYMBOLS, _prototypes)
 
 
 def out_dtype(dtype, requested):

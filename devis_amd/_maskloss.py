@@ -3,11 +3,10 @@ opens).  As in ``_mhstage``: no fallback, a failing call raises, launches go to 
 allocates nor synchronises -- outputs and workspaces are torch tensors of the caller.
 """
 import ctypes
-import threading
 
 import torch
 
-from . import _native
+from . import _binding, _native
 
 MASKLOSS_ABI_VERSION = 1
 TARGET_U8, TARGET_SAME, TARGET_F32 = 0, 1, 2        # include/maskloss.h MASKLOSS_TARGET_*
@@ -17,8 +16,6 @@ EXPORTED_SYMBOLS = ("maskloss_version", "maskloss_last_error", "maskloss_tile", 
                     "maskloss_forward", "maskloss_backward")
 
 _vp, _ci, _cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-_lib = None
-_lock = threading.Lock()
 
 
 class Shape(ctypes.Structure):
@@ -26,42 +23,20 @@ class Shape(ctypes.Structure):
     _fields_ = [(name, _ci) for name in ("N", "h", "w", "H", "W")]
 
 
-def load():
-    """The library with the maskloss_* prototypes set; raises RuntimeError when it cannot be loaded or is another version."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is not None:
-            return _lib
-        lib = _native.load()
-        for name in EXPORTED_SYMBOLS:
-            if not hasattr(lib, name):
-                raise RuntimeError("devis_amd: the HIP library does not export %s; rebuild with "
-                                   "python -m devis_amd.build --force" % name)
-        lib.maskloss_version.restype = _ci
-        lib.maskloss_last_error.restype = ctypes.c_char_p
-        if lib.maskloss_version() != MASKLOSS_ABI_VERSION:
-            raise RuntimeError("devis_amd: maskloss ABI version mismatch (library %d, binding %d); rebuild with "
-                               "python -m devis_amd.build --force" % (lib.maskloss_version(), MASKLOSS_ABI_VERSION))
-        shape_p = ctypes.POINTER(Shape)
-        lib.maskloss_tile.restype = _ci
-        lib.maskloss_tile.argtypes = [_ci]
-        lib.maskloss_workspace_bytes.restype = ctypes.c_longlong
-        lib.maskloss_workspace_bytes.argtypes = [_ci, shape_p]
-        lib.maskloss_forward.restype = _ci
-        lib.maskloss_forward.argtypes = [_ci, _ci, _vp, _vp, shape_p, _cd, _cd, _vp, _vp, _vp, _vp, _vp]
-        lib.maskloss_backward.restype = _ci
-        lib.maskloss_backward.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, _vp, shape_p, _cd, _cd, _vp, _vp]
-        _lib = lib
-    return _lib
+def _prototypes(lib):
+    shape_p = ctypes.POINTER(Shape)
+    lib.maskloss_tile.restype = _ci
+    lib.maskloss_tile.argtypes = [_ci]
+    lib.maskloss_workspace_bytes.restype = ctypes.c_longlong
+    lib.maskloss_workspace_bytes.argtypes = [_ci, shape_p]
+    lib.maskloss_forward.restype = _ci
+    lib.maskloss_forward.argtypes = [_ci, _ci, _vp, _vp, shape_p, _cd, _cd, _vp, _vp, _vp, _vp, _vp]
+    lib.maskloss_backward.restype = _ci
+    lib.maskloss_backward.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, _vp, shape_p, _cd, _cd, _vp, _vp]
 
 
-def _check(rc, what):
-    if rc < 0:
-        msg = load().maskloss_last_error().decode("utf-8", "replace")
-        raise RuntimeError("devis_amd: %s failed (status %d): %s" % (what, rc, msg))
-    return rc
+# load(): the library with the maskloss_* prototypes set; raises RuntimeError when it cannot be loaded or is another version
+load, _check = _binding.bind("maskloss", MASKLOSS_ABI_VERSION, EXPORTED_SYMBOLS, _prototypes)
 
 
 def tile(which):

@@ -3,11 +3,10 @@ opens).  As in ``_native``: no fallback, a failing call raises, launches go to t
 allocates nor synchronises -- the column buffers are torch tensors of the caller.
 """
 import ctypes
-import threading
 
 import torch
 
-from . import _native
+from . import _binding, _native
 
 MDCN_ABI_VERSION = 2
 GRAD_INPUT, GRAD_SAMPLING = 1, 2        # include/mdcn.h MDCN_GRAD_INPUT / MDCN_GRAD_SAMPLING
@@ -17,8 +16,6 @@ EXPORTED_SYMBOLS = ("mdcn_version", "mdcn_last_error", "mdcn_workspace_bytes", "
 _OFF32_CODE = {torch.bfloat16: 4, torch.float16: 5}     # MDCN_BF16_OFF32 / MDCN_F16_OFF32
 
 _vp, _ci = ctypes.c_void_p, ctypes.c_int
-_lib = None
-_lock = threading.Lock()
 
 
 class Shape(ctypes.Structure):
@@ -27,44 +24,22 @@ class Shape(ctypes.Structure):
                                          "dil_h", "dil_w", "G")]
 
 
-def load():
-    """The library with the mdcn_* prototypes set; raises RuntimeError when it cannot be loaded or is another version."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is not None:
-            return _lib
-        lib = _native.load()
-        for name in EXPORTED_SYMBOLS:
-            if not hasattr(lib, name):
-                raise RuntimeError("devis_amd: the HIP library does not export %s; rebuild with "
-                                   "python -m devis_amd.build --force" % name)
-        lib.mdcn_version.restype = _ci
-        lib.mdcn_last_error.restype = ctypes.c_char_p
-        if lib.mdcn_version() != MDCN_ABI_VERSION:
-            raise RuntimeError("devis_amd: mdcn ABI version mismatch (library %d, binding %d); rebuild with "
-                               "python -m devis_amd.build --force" % (lib.mdcn_version(), MDCN_ABI_VERSION))
-        shape_p = ctypes.POINTER(Shape)
-        lib.mdcn_workspace_bytes.restype = ctypes.c_longlong
-        lib.mdcn_workspace_bytes.argtypes = [_ci, shape_p, _ci]
-        lib.mdcn_im2col.restype = _ci
-        lib.mdcn_im2col.argtypes = [_ci, _vp, _vp, _vp, shape_p, _vp, _vp]
-        lib.mdcn_backward.restype = _ci
-        lib.mdcn_backward.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, shape_p, _vp, _vp, _vp, _vp]
-        lib.mdcn_fixed_workspace_bytes.restype = ctypes.c_longlong
-        lib.mdcn_fixed_workspace_bytes.argtypes = [_ci, shape_p, _ci]
-        lib.mdcn_backward_input_fixed.restype = _ci
-        lib.mdcn_backward_input_fixed.argtypes = [_ci, _vp, _vp, _vp, shape_p, _vp, _vp, _vp]
-        _lib = lib
-    return _lib
+def _prototypes(lib):
+    shape_p = ctypes.POINTER(Shape)
+    lib.mdcn_workspace_bytes.restype = ctypes.c_longlong
+    lib.mdcn_workspace_bytes.argtypes = [_ci, shape_p, _ci]
+    lib.mdcn_im2col.restype = _ci
+    lib.mdcn_im2col.argtypes = [_ci, _vp, _vp, _vp, shape_p, _vp, _vp]
+    lib.mdcn_backward.restype = _ci
+    lib.mdcn_backward.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, shape_p, _vp, _vp, _vp, _vp]
+    lib.mdcn_fixed_workspace_bytes.restype = ctypes.c_longlong
+    lib.mdcn_fixed_workspace_bytes.argtypes = [_ci, shape_p, _ci]
+    lib.mdcn_backward_input_fixed.restype = _ci
+    lib.mdcn_backward_input_fixed.argtypes = [_ci, _vp, _vp, _vp, shape_p, _vp, _vp, _vp]
 
 
-def _check(rc, what):
-    if rc < 0:
-        msg = load().mdcn_last_error().decode("utf-8", "replace")
-        raise RuntimeError("devis_amd: %s failed (status %d): %s" % (what, rc, msg))
-    return rc
+# load(): the library with the mdcn_* prototypes set; raises RuntimeError when it cannot be loaded or is another version
+load, _check = _binding.bind("mdcn", MDCN_ABI_VERSION, EXPORTED_SYMBOLS, _prototypes)
 
 
 def type_code(dtype, offset_dtype):

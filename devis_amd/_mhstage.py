@@ -3,11 +3,10 @@ opens).  As in ``_attmap``: no fallback, a failing call raises, launches go to t
 allocates nor synchronises -- outputs and workspaces are torch tensors of the caller.
 """
 import ctypes
-import threading
 
 import torch
 
-from . import _native
+from . import _binding, _native
 
 MHSTAGE_ABI_VERSION = 1
 GRAD_X, GRAD_WEIGHT, GRAD_BIAS, GRAD_SKIP = 1, 2, 4, 8      # include/mhstage.h MHSTAGE_GRAD_*
@@ -18,8 +17,6 @@ EXPORTED_SYMBOLS = ("mhstage_version", "mhstage_last_error", "mhstage_tile", "mh
                     "mhstage_backward")
 
 _vp, _ci = ctypes.c_void_p, ctypes.c_int
-_lib = None
-_lock = threading.Lock()
 
 
 class Shape(ctypes.Structure):
@@ -27,44 +24,22 @@ class Shape(ctypes.Structure):
     _fields_ = [(name, _ci) for name in ("N", "F", "C", "G", "E", "h", "w", "H", "W")]
 
 
-def load():
-    """The library with the mhstage_* prototypes set; raises RuntimeError when it cannot be loaded or is another version."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is not None:
-            return _lib
-        lib = _native.load()
-        for name in EXPORTED_SYMBOLS:
-            if not hasattr(lib, name):
-                raise RuntimeError("devis_amd: the HIP library does not export %s; rebuild with "
-                                   "python -m devis_amd.build --force" % name)
-        lib.mhstage_version.restype = _ci
-        lib.mhstage_last_error.restype = ctypes.c_char_p
-        if lib.mhstage_version() != MHSTAGE_ABI_VERSION:
-            raise RuntimeError("devis_amd: mhstage ABI version mismatch (library %d, binding %d); rebuild with "
-                               "python -m devis_amd.build --force" % (lib.mhstage_version(), MHSTAGE_ABI_VERSION))
-        shape_p = ctypes.POINTER(Shape)
-        lib.mhstage_tile.restype = _ci
-        lib.mhstage_tile.argtypes = [_ci]
-        lib.mhstage_workspace_bytes.restype = ctypes.c_longlong
-        lib.mhstage_workspace_bytes.argtypes = [_ci, shape_p]
-        lib.mhstage_forward.restype = _ci
-        lib.mhstage_forward.argtypes = [_ci, _ci, _ci, _ci, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _ci, _vp, shape_p,
-                                        _vp, _vp, _vp, _vp, _vp]
-        lib.mhstage_backward.restype = _ci
-        lib.mhstage_backward.argtypes = [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, shape_p,
-                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-        _lib = lib
-    return _lib
+def _prototypes(lib):
+    shape_p = ctypes.POINTER(Shape)
+    lib.mhstage_tile.restype = _ci
+    lib.mhstage_tile.argtypes = [_ci]
+    lib.mhstage_workspace_bytes.restype = ctypes.c_longlong
+    lib.mhstage_workspace_bytes.argtypes = [_ci, shape_p]
+    lib.mhstage_forward.restype = _ci
+    lib.mhstage_forward.argtypes = [_ci, _ci, _ci, _ci, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _ci, _vp, shape_p,
+                                    _vp, _vp, _vp, _vp, _vp]
+    lib.mhstage_backward.restype = _ci
+    lib.mhstage_backward.argtypes = [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, shape_p,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]
 
 
-def _check(rc, what):
-    if rc < 0:
-        msg = load().mhstage_last_error().decode("utf-8", "replace")
-        raise RuntimeError("devis_amd: %s failed (status %d): %s" % (what, rc, msg))
-    return rc
+# load(): the library with the mhstage_* prototypes set; raises RuntimeError when it cannot be loaded or is another version
+load, _check = _binding.bind("mhstage", MHSTAGE_ABI_VERSION, EXPORTED_SYMBOLS, _prototypes)
 
 
 def tile(which):

@@ -57,7 +57,7 @@ def sources():
 def _headers():
     inc = include_dir()
     return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc"))) + \
-        ([os.path.join(inc, "msda.h"), os.path.join(inc, "mdcn.h"), os.path.join(inc, "attmap.h"), os.path.join(inc, "mhstage.h"), os.path.join(inc, "maskloss.h")] if inc else [])
+        (sorted(glob.glob(os.path.join(inc, "*.h"))) if inc else [])
 
 
 def _lib_override():

@@ -7,58 +7,22 @@
 // each lane keeps kTQ x PPL logits in registers, so a value of k is used kTQ times.  The (pre-scaled) queries of the tile sit
 // in LDS and are read as broadcasts.  Query tiles are the fastest grid dimension: the workgroups that read one tile of k run
 // together and share it through the caches.
-#include "mdcn_common.h"    // the storage types (Acc, to_acc, from_acc)
+#include "op_common.h"
 #include "attmap.h"
 
 namespace attmap {
 
-using mdcn::Acc;
-using mdcn::from_acc;
-using mdcn::to_acc;
+using namespace devis;
+
+static_assert(ATTMAP_OK == kOk && ATTMAP_ERR_ARGUMENT == kErrArgument && ATTMAP_ERR_HIP == kErrHip, "status codes");
+static_assert(ATTMAP_F32 == kF32 && ATTMAP_F64 == kF64 && ATTMAP_BF16 == kBF16 && ATTMAP_F16 == kF16, "dtype codes");
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kTQ = 8;              // queries per workgroup (a multiple of kWaves)
 constexpr int kMaxC = 512;          // kTQ * c arithmetic values of LDS: 32 KiB for doubles at the bound
 
-thread_local char g_err[512] = "";
-
-int fail(const char *fmt, long long a = 0, long long b = 0)
-{
-    snprintf(g_err, sizeof(g_err), fmt, a, b);
-    return ATTMAP_ERR_ARGUMENT;
-}
-
-int check_launch(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return ATTMAP_OK;
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return ATTMAP_ERR_HIP;
-}
-
-__device__ __forceinline__ float ex(float v) { return expf(v); }
-__device__ __forceinline__ double ex(double v) { return exp(v); }
-__device__ __forceinline__ float mad(float a, float b, float c) { return fmaf(a, b, c); }
-__device__ __forceinline__ double mad(double a, double b, double c) { return fma(a, b, c); }
-__device__ __forceinline__ float mx(float a, float b) { return fmaxf(a, b); }
-__device__ __forceinline__ double mx(double a, double b) { return fmax(a, b); }
-__device__ __forceinline__ float neg_inf(float) { return -INFINITY; }
-__device__ __forceinline__ double neg_inf(double) { return -(double)INFINITY; }
-
-// butterflies over the 64 lanes: every lane ends with the same bits (max and IEEE add are commutative)
-template <typename A> __device__ __forceinline__ A wave_max(A v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = mx(v, __shfl_xor(v, d, 64));
-    return v;
-}
-template <typename A> __device__ __forceinline__ A wave_sum(A v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
+thread_local Status err;     // attmap_last_error()
 
 // ---- forward -----------------------------------------------------------------------------------------------------------
 // WRITE = false: pass 1, the tile's (maximum, sum of exp) per query -> ws[((row * n + h) * tiles + tile) * 2 + {0, 1}].
@@ -116,7 +80,7 @@ __global__ __launch_bounds__(kThreads) void attmap_fwd_kernel(const T *__restric
         for (int t = 0; t < kTQ; ++t) {
             const A qv = sq[cc * kTQ + t];
 #pragma unroll
-            for (int j = 0; j < PPL; ++j) acc[t][j] = mad(qv, kv[j], acc[t][j]);
+            for (int j = 0; j < PPL; ++j) acc[t][j] = fma_of(qv, kv[j], acc[t][j]);
         }
     }
 #pragma unroll
@@ -130,7 +94,7 @@ __global__ __launch_bounds__(kThreads) void attmap_fwd_kernel(const T *__restric
         for (int t = 0; t < kTQ; ++t) {
             A m = acc[t][0];
 #pragma unroll
-            for (int j = 1; j < PPL; ++j) m = mx(m, acc[t][j]);
+            for (int j = 1; j < PPL; ++j) m = max_of(m, acc[t][j]);
             m = wave_max(m);
             if (lane == 0) red[t * kWaves + wave] = m;
         }
@@ -140,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void attmap_fwd_kernel(const T *__restric
         for (int t = 0; t < kTQ; ++t) {
             A m = red[t * kWaves];
 #pragma unroll
-            for (int w = 1; w < kWaves; ++w) m = mx(m, red[t * kWaves + w]);
+            for (int w = 1; w < kWaves; ++w) m = max_of(m, red[t * kWaves + w]);
             safe[t] = m;
         }
         __syncthreads();
@@ -149,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void attmap_fwd_kernel(const T *__restric
             const A m = safe[t] == ninf ? (A)0 : safe[t];
             A sum = (A)0;
 #pragma unroll
-            for (int j = 0; j < PPL; ++j) sum += ex(acc[t][j] - m);
+            for (int j = 0; j < PPL; ++j) sum += exp_of(acc[t][j] - m);
             sum = wave_sum(sum);
             if (lane == 0) red[t * kWaves + wave] = sum;
             if (tid == t) row[t * 2] = safe[t];
@@ -171,11 +135,11 @@ __global__ __launch_bounds__(kThreads) void attmap_fwd_kernel(const T *__restric
         const int qi = min(q0 + t, s.Q - 1);
         const A *wp = ws + ((long long)b * s.Q + qi) * parts * 2;
         A m = ninf;
-        for (int i = lane; i < parts; i += 64) m = mx(m, wp[2 * i]);
+        for (int i = lane; i < parts; i += 64) m = max_of(m, wp[2 * i]);
         m = wave_max(m);
         const A safe = m == ninf ? (A)0 : m;
         A sum = (A)0;
-        for (int i = lane; i < parts; i += 64) sum += wp[2 * i + 1] * ex(wp[2 * i] - safe);
+        for (int i = lane; i < parts; i += 64) sum += wp[2 * i + 1] * exp_of(wp[2 * i] - safe);
         sum = wave_sum(sum);
         if (lane == 0) {
             row[t * 2] = m;                 // -inf for a fully masked row: exp(-inf - -inf) is the NaN the row is defined as
@@ -191,7 +155,7 @@ __global__ __launch_bounds__(kThreads) void attmap_fwd_kernel(const T *__restric
 #pragma unroll
         for (int j = 0; j < PPL; ++j) {
             const int pix = tile * (kThreads * PPL) + j * kThreads + tid;
-            if (pix < P) from_acc(o[pix], ex(acc[t][j] - m) * inv);
+            if (pix < P) from_acc(o[pix], exp_of(acc[t][j] - m) * inv);
         }
     }
 }
@@ -224,7 +188,7 @@ __global__ __launch_bounds__(kThreads) void attmap_bwd_kernel(const TO *__restri
     if (!WRITE) {
         A sum = (A)0;
 #pragma unroll
-        for (int j = 0; j < PPL; ++j) sum = mad(g[j], o[j], sum);
+        for (int j = 0; j < PPL; ++j) sum = fma_of(g[j], o[j], sum);
         sum = wave_sum(sum);
         if (lane == 0) red[wave] = sum;
         __syncthreads();
@@ -256,18 +220,6 @@ __global__ __launch_bounds__(kThreads) void attmap_bwd_kernel(const TO *__restri
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------
-int elem_size(int dtype)
-{
-    switch (dtype) {
-    case ATTMAP_F32: return 4;
-    case ATTMAP_F64: return 8;
-    case ATTMAP_BF16: case ATTMAP_F16: return 2;
-    default: return 0;
-    }
-}
-
-int acc_size(int dtype) { return dtype == ATTMAP_F64 ? 8 : 4; }
-
 // pixels per lane: large maps amortise a tile's reductions (and its reads of the queries) over four pixels a lane; small
 // ones keep one, for more workgroups
 int fwd_ppl(long long P) { return P >= 2048 ? 4 : 1; }
@@ -276,20 +228,20 @@ int tiles_of(long long P, int ppl) { return (int)((P + (long long)kThreads * ppl
 
 int check_shape(const attmap_shape *s)
 {
-    if (!s) return fail("null pointer: shape");
+    if (!s) return err.fail("null pointer: shape");
     if (s->B < 0 || s->Q < 0 || s->n <= 0 || s->c <= 0 || s->H <= 0 || s->W <= 0)
-        return fail("sizes must be positive (B and Q may be 0)");
-    if (s->B > 65535 || s->n > 65535) return fail("B = %lld and n = %lld must not exceed 65535", s->B, s->n);
-    if (s->c > kMaxC) return fail("c = %lld channels per head exceed the bound of %lld", s->c, kMaxC);
-    if ((long long)s->H * s->W > 0x7fffffffLL) return fail("H * W = %lld does not fit 31 bits", (long long)s->H * s->W);
+        return err.fail("sizes must be positive (B and Q may be 0)");
+    if (s->B > 65535 || s->n > 65535) return err.fail("B = %lld and n = %lld must not exceed 65535", s->B, s->n);
+    if (s->c > kMaxC) return err.fail("c = %lld channels per head exceed the bound of %lld", s->c, kMaxC);
+    if ((long long)s->H * s->W > 0x7fffffffLL) return err.fail("H * W = %lld does not fit 31 bits", (long long)s->H * s->W);
     return ATTMAP_OK;
 }
 
 int check_types(int dtype, int out_dtype)
 {
-    if (!elem_size(dtype)) return fail("bad dtype code %lld", dtype);
+    if (!elem_size(dtype)) return err.fail("bad dtype code %lld", dtype);
     if (out_dtype != dtype && !(out_dtype == ATTMAP_F32 && elem_size(dtype) == 2))
-        return fail("out_dtype %lld must be dtype %lld itself, or ATTMAP_F32 beside a 16-bit dtype", out_dtype, dtype);
+        return err.fail("out_dtype %lld must be dtype %lld itself, or ATTMAP_F32 beside a 16-bit dtype", out_dtype, dtype);
     return ATTMAP_OK;
 }
 
@@ -300,9 +252,9 @@ int launch_forward(const void *q, const void *k, const unsigned char *mask, cons
     typedef typename Acc<T>::type A;
     const long long P = (long long)s.H * s.W;
     const int ppl = fwd_ppl(P), tiles = tiles_of(P, ppl);
-    const long long gx = (long long)((s.Q + kTQ - 1) / kTQ) * tiles;
-    if (gx > 0x7fffffffLL) return fail("too many workgroups for one launch (%lld)", gx);
-    const dim3 grid((unsigned)gx, (unsigned)s.n, (unsigned)s.B), block(kThreads);
+    unsigned gx;
+    if (err.grid_of((long long)((s.Q + kTQ - 1) / kTQ) * tiles, &gx)) return ATTMAP_ERR_ARGUMENT;
+    const dim3 grid(gx, (unsigned)s.n, (unsigned)s.B), block(kThreads);
     const size_t lds = ((size_t)s.c * kTQ + kTQ * kWaves + kTQ * 2) * sizeof(A);
 #define ATTMAP_FWD(PPL, WRITE)                                                                                          \
     hipLaunchKernelGGL((attmap_fwd_kernel<T, TO, PPL, WRITE>), grid, block, lds, st, (const T *)q, (const T *)k, mask,   \
@@ -310,7 +262,7 @@ int launch_forward(const void *q, const void *k, const unsigned char *mask, cons
     if (ppl == 4) { ATTMAP_FWD(4, false); ATTMAP_FWD(4, true); }
     else { ATTMAP_FWD(1, false); ATTMAP_FWD(1, true); }
 #undef ATTMAP_FWD
-    return check_launch("attmap_fwd_kernel");
+    return err.check_launch("attmap_fwd_kernel");
 }
 
 template <typename T, typename TO>
@@ -319,16 +271,16 @@ int launch_backward(const void *out, const void *gout, const attmap_shape &s, do
     typedef typename Acc<T>::type A;
     const long long P = (long long)s.H * s.W;
     const int ppl = bwd_ppl(P), tiles = tiles_of(P, ppl);
-    const long long gx = (long long)s.B * s.Q * s.n * tiles;
-    if (gx > 0x7fffffffLL) return fail("too many workgroups for one launch (%lld)", gx);
-    const dim3 grid((unsigned)gx), block(kThreads);
+    unsigned gx;
+    if (err.grid_of((long long)s.B * s.Q * s.n * tiles, &gx)) return ATTMAP_ERR_ARGUMENT;
+    const dim3 grid(gx), block(kThreads);
 #define ATTMAP_BWD(PPL, WRITE)                                                                                          \
     hipLaunchKernelGGL((attmap_bwd_kernel<T, TO, PPL, WRITE>), grid, block, 0, st, (const TO *)out, (const TO *)gout,    \
                        (A *)ws, (T *)dl, s, (A)scale, tiles)
     if (ppl == 8) { ATTMAP_BWD(8, false); ATTMAP_BWD(8, true); }
     else { ATTMAP_BWD(1, false); ATTMAP_BWD(1, true); }
 #undef ATTMAP_BWD
-    return check_launch("attmap_bwd_kernel");
+    return err.check_launch("attmap_bwd_kernel");
 }
 
 }  // namespace attmap
@@ -339,12 +291,12 @@ extern "C" {
 
 int attmap_version(void) { return ATTMAP_ABI_VERSION; }
 
-const char *attmap_last_error(void) { return g_err; }
+const char *attmap_last_error(void) { return err.msg; }
 
 long long attmap_workspace_bytes(int dtype, const attmap_shape *shape)
 {
-    g_err[0] = 0;
-    if (!elem_size(dtype)) return fail("bad dtype code %lld", dtype);
+    err.clear();
+    if (!elem_size(dtype)) return err.fail("bad dtype code %lld", dtype);
     if (check_shape(shape) != ATTMAP_OK) return ATTMAP_ERR_ARGUMENT;
     const long long P = (long long)shape->H * shape->W;
     // the forward's partials: the backward's tiles are no smaller and it keeps one value per tile
@@ -355,46 +307,30 @@ long long attmap_workspace_bytes(int dtype, const attmap_shape *shape)
 int attmap_forward(int dtype, int out_dtype, const void *q, const void *k, const unsigned char *mask,
                    const attmap_shape *shape, double scale, void *workspace, void *out, void *stream)
 {
-    g_err[0] = 0;
+    err.clear();
     if (check_types(dtype, out_dtype) != ATTMAP_OK || check_shape(shape) != ATTMAP_OK) return ATTMAP_ERR_ARGUMENT;
     if (shape->B == 0 || shape->Q == 0) return ATTMAP_OK;
-    if (!q || !k || !workspace || !out) return fail("null pointer: q, k, workspace and out are required");
+    if (!q || !k || !workspace || !out) return err.fail("null pointer: q, k, workspace and out are required");
     hipStream_t st = (hipStream_t)stream;
-    const bool wide = out_dtype != dtype;
-    switch (dtype) {
-    case ATTMAP_F32: return launch_forward<float, float>(q, k, mask, *shape, scale, workspace, out, st);
-    case ATTMAP_F64: return launch_forward<double, double>(q, k, mask, *shape, scale, workspace, out, st);
-    case ATTMAP_BF16:
-        return wide ? launch_forward<__hip_bfloat16, float>(q, k, mask, *shape, scale, workspace, out, st)
-                    : launch_forward<__hip_bfloat16, __hip_bfloat16>(q, k, mask, *shape, scale, workspace, out, st);
-    default:
-        return wide ? launch_forward<__half, float>(q, k, mask, *shape, scale, workspace, out, st)
-                    : launch_forward<__half, __half>(q, k, mask, *shape, scale, workspace, out, st);
-    }
+    return dispatch(dtype, out_dtype != dtype, [&](auto t, auto to) {
+        return launch_forward<type_of<decltype(t)>, type_of<decltype(to)>>(q, k, mask, *shape, scale, workspace, out, st);
+    });
 }
 
 int attmap_backward(int grads, int dtype, int out_dtype, const void *out, const void *grad_out, const attmap_shape *shape,
                     double scale, void *workspace, void *dl, void *stream)
 {
-    g_err[0] = 0;
+    err.clear();
     if (check_types(dtype, out_dtype) != ATTMAP_OK) return ATTMAP_ERR_ARGUMENT;
     if (grads < 0 || grads > (ATTMAP_GRAD_Q | ATTMAP_GRAD_K))
-        return fail("grads = %lld is not a mask of ATTMAP_GRAD_Q and ATTMAP_GRAD_K", grads);
+        return err.fail("grads = %lld is not a mask of ATTMAP_GRAD_Q and ATTMAP_GRAD_K", grads);
     if (check_shape(shape) != ATTMAP_OK) return ATTMAP_ERR_ARGUMENT;
     if (shape->B == 0 || shape->Q == 0 || grads == 0) return ATTMAP_OK;
-    if (!out || !grad_out || !workspace || !dl) return fail("null pointer: out, grad_out, workspace and dl are required");
+    if (!out || !grad_out || !workspace || !dl) return err.fail("null pointer: out, grad_out, workspace and dl are required");
     hipStream_t st = (hipStream_t)stream;
-    const bool wide = out_dtype != dtype;
-    switch (dtype) {
-    case ATTMAP_F32: return launch_backward<float, float>(out, grad_out, *shape, scale, workspace, dl, st);
-    case ATTMAP_F64: return launch_backward<double, double>(out, grad_out, *shape, scale, workspace, dl, st);
-    case ATTMAP_BF16:
-        return wide ? launch_backward<__hip_bfloat16, float>(out, grad_out, *shape, scale, workspace, dl, st)
-                    : launch_backward<__hip_bfloat16, __hip_bfloat16>(out, grad_out, *shape, scale, workspace, dl, st);
-    default:
-        return wide ? launch_backward<__half, float>(out, grad_out, *shape, scale, workspace, dl, st)
-                    : launch_backward<__half, __half>(out, grad_out, *shape, scale, workspace, dl, st);
-    }
+    return dispatch(dtype, out_dtype != dtype, [&](auto t, auto to) {
+        return launch_backward<type_of<decltype(t)>, type_of<decltype(to)>>(out, grad_out, *shape, scale, workspace, dl, st);
+    });
 }
 
 }  // extern "C"

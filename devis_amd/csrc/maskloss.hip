@@ -5,14 +5,15 @@
 //
 // The kernels are templates of the storage type of src alone.  The target kind and how gamma is applied are kernel
 // arguments: wave-uniform branches, not compile-time variants.
-#include "mdcn_common.h"    // the storage types (Acc, to_acc, from_acc); fp contraction off
+#include "op_common.h"       // (fp contraction off)
 #include "maskloss.h"
 
 namespace maskloss {
 
-using mdcn::Acc;
-using mdcn::from_acc;
-using mdcn::to_acc;
+using namespace devis;
+
+static_assert(MASKLOSS_OK == kOk && MASKLOSS_ERR_ARGUMENT == kErrArgument && MASKLOSS_ERR_HIP == kErrHip, "status codes");
+static_assert(MASKLOSS_F32 == kF32 && MASKLOSS_F64 == kF64 && MASKLOSS_BF16 == kBF16 && MASKLOSS_F16 == kF16, "dtype codes");
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -25,28 +26,7 @@ static_assert(kBY * kBX == kThreads, "one source pixel per lane");
 
 enum { kGammaZero = 0, kGammaOne = 1, kGammaTwo = 2, kGammaPow = 3 };
 
-thread_local char g_err[512] = "";
-
-int fail(const char *fmt, long long a = 0, long long b = 0)
-{
-    snprintf(g_err, sizeof(g_err), fmt, a, b);
-    return MASKLOSS_ERR_ARGUMENT;
-}
-
-int check_launch(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return MASKLOSS_OK;
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return MASKLOSS_ERR_HIP;
-}
-
-__device__ __forceinline__ float exp_of(float v) { return expf(v); }
-__device__ __forceinline__ double exp_of(double v) { return exp(v); }
-__device__ __forceinline__ float log1p_of(float v) { return log1pf(v); }
-__device__ __forceinline__ double log1p_of(double v) { return log1p(v); }
-__device__ __forceinline__ float pow_of(float a, float b) { return powf(a, b); }
-__device__ __forceinline__ double pow_of(double a, double b) { return pow(a, b); }
+thread_local Status err;     // maskloss_last_error()
 
 // ---- the resampling rule (include/maskloss.h), per axis, in the arithmetic type ---------------------------------------
 template <typename A> struct Tap {
@@ -139,14 +119,6 @@ template <typename T> __device__ __forceinline__ typename Acc<T>::type target_at
     if (tk == MASKLOSS_TARGET_U8) return reinterpret_cast<const unsigned char *>(tgt)[i] ? (A)1 : (A)0;
     if (tk == MASKLOSS_TARGET_F32) return (A) reinterpret_cast<const float *>(tgt)[i];
     return (A)to_acc(reinterpret_cast<const T *>(tgt)[i]);
-}
-
-// butterfly over the 64 lanes: every lane ends with the same bits
-template <typename A> __device__ __forceinline__ A wave_sum(A v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
 }
 
 template <typename A> __device__ __forceinline__ void finish(A fsum, A a, A b, A c, int P, A *focal, A *dice, A *sums)
@@ -354,53 +326,33 @@ __global__ __launch_bounds__(kThreads) void backward_kernel(const T *__restrict_
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------
-int elem_size(int dtype)
-{
-    switch (dtype) {
-    case MASKLOSS_F32: return 4;
-    case MASKLOSS_F64: return 8;
-    case MASKLOSS_BF16: case MASKLOSS_F16: return 2;
-    default: return 0;
-    }
-}
-
-int acc_size(int dtype) { return dtype == MASKLOSS_F64 ? 8 : 4; }
-long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
-
 int check_shape(const maskloss_shape *s)
 {
-    if (!s) return fail("null pointer: shape");
+    if (!s) return err.fail("null pointer: shape");
     if (s->N < 0 || s->h <= 0 || s->w <= 0 || s->H <= 0 || s->W <= 0)
-        return fail("sizes must be positive (N may be 0)");
-    if ((long long)s->h * s->w > 0x7fffffffLL) return fail("h * w = %lld does not fit 31 bits", (long long)s->h * s->w);
-    if ((long long)s->H * s->W > 0x7fffffffLL) return fail("H * W = %lld does not fit 31 bits", (long long)s->H * s->W);
+        return err.fail("sizes must be positive (N may be 0)");
+    if ((long long)s->h * s->w > 0x7fffffffLL) return err.fail("h * w = %lld does not fit 31 bits", (long long)s->h * s->w);
+    if ((long long)s->H * s->W > 0x7fffffffLL) return err.fail("H * W = %lld does not fit 31 bits", (long long)s->H * s->W);
     return MASKLOSS_OK;
 }
 
 int check_types(int dtype, int target_kind)
 {
-    if (!elem_size(dtype)) return fail("bad dtype code %lld", dtype);
+    if (!elem_size(dtype)) return err.fail("bad dtype code %lld", dtype);
     if (target_kind != MASKLOSS_TARGET_U8 && target_kind != MASKLOSS_TARGET_SAME && target_kind != MASKLOSS_TARGET_F32)
-        return fail("bad target kind %lld", target_kind);
+        return err.fail("bad target kind %lld", target_kind);
     return MASKLOSS_OK;
 }
 
 // how gamma is applied; negative on a gamma the operator refuses
 int gamma_mode(double gamma)
 {
-    if (!(gamma >= 0.0) || gamma > 1.0e30) return fail("gamma must be 0, 1 or larger than 1 (and finite)");
+    if (!(gamma >= 0.0) || gamma > 1.0e30) return err.fail("gamma must be 0, 1 or larger than 1 (and finite)");
     if (gamma == 0.0) return kGammaZero;
     if (gamma == 1.0) return kGammaOne;
     if (gamma == 2.0) return kGammaTwo;
-    if (gamma < 1.0) return fail("gamma in (0, 1) is not supported: the derivative is unbounded at p_t = 1");
+    if (gamma < 1.0) return err.fail("gamma in (0, 1) is not supported: the derivative is unbounded at p_t = 1");
     return kGammaPow;
-}
-
-int grid_of(long long blocks, unsigned *out)
-{
-    if (blocks > 0x7fffffffLL) return fail("too many workgroups for one launch (%lld)", blocks);
-    *out = (unsigned)blocks;
-    return MASKLOSS_OK;
 }
 
 int fwd_tiles(const maskloss_shape &s) { return (int)cdiv((long long)s.H * s.W, kFwdTile); }
@@ -412,13 +364,13 @@ int launch_forward(int tk, const void *src, const void *tgt, const maskloss_shap
     typedef typename Acc<T>::type A;
     const int tiles = fwd_tiles(s);
     unsigned g1, g2;
-    if (grid_of((long long)s.N * tiles, &g1) || grid_of(cdiv(s.N, kWaves), &g2)) return MASKLOSS_ERR_ARGUMENT;
+    if (err.grid_of((long long)s.N * tiles, &g1) || err.grid_of(cdiv(s.N, kWaves), &g2)) return MASKLOSS_ERR_ARGUMENT;
     hipLaunchKernelGGL((forward_kernel<T>), dim3(g1), dim3(kThreads), 0, st, (const T *)src, tgt, tk, (A *)ws, (A *)focal,
                        (A *)dice, (A *)sums, s, tiles, (A)alpha, (A)gamma, gm);
     if (tiles > 1)
         hipLaunchKernelGGL((combine_kernel<A>), dim3(g2), dim3(kThreads), 0, st, (const A *)ws, (A *)focal, (A *)dice,
                            (A *)sums, s.N, tiles, s.H * s.W);
-    return check_launch("maskloss_forward");
+    return err.check_launch("maskloss_forward");
 }
 
 template <typename T>
@@ -428,10 +380,10 @@ int launch_backward(int tk, const void *src, const void *tgt, const void *sums, 
     typedef typename Acc<T>::type A;
     const int tx = (int)cdiv(s.w, kBX), ty = (int)cdiv(s.h, kBY);
     unsigned g1;
-    if (grid_of((long long)s.N * tx * ty, &g1)) return MASKLOSS_ERR_ARGUMENT;
+    if (err.grid_of((long long)s.N * tx * ty, &g1)) return MASKLOSS_ERR_ARGUMENT;
     hipLaunchKernelGGL((backward_kernel<T>), dim3(g1), dim3(kThreads), 0, st, (const T *)src, tgt, tk, (const A *)sums,
                        (const A *)gf, (const A *)gd, (T *)gsrc, s, tx, ty, (A)alpha, (A)gamma, gm);
-    return check_launch("maskloss_backward");
+    return err.check_launch("maskloss_backward");
 }
 
 }  // namespace maskloss
@@ -442,7 +394,7 @@ extern "C" {
 
 int maskloss_version(void) { return MASKLOSS_ABI_VERSION; }
 
-const char *maskloss_last_error(void) { return g_err; }
+const char *maskloss_last_error(void) { return err.msg; }
 
 int maskloss_tile(int which)
 {
@@ -458,8 +410,8 @@ int maskloss_tile(int which)
 
 long long maskloss_workspace_bytes(int dtype, const maskloss_shape *shape)
 {
-    g_err[0] = 0;
-    if (!elem_size(dtype)) return fail("bad dtype code %lld", dtype);
+    err.clear();
+    if (!elem_size(dtype)) return err.fail("bad dtype code %lld", dtype);
     if (check_shape(shape) != MASKLOSS_OK) return MASKLOSS_ERR_ARGUMENT;
     const int tiles = fwd_tiles(*shape);
     const long long bytes = tiles > 1 ? (long long)shape->N * tiles * 4 * acc_size(dtype) : 0;
@@ -469,48 +421,39 @@ long long maskloss_workspace_bytes(int dtype, const maskloss_shape *shape)
 int maskloss_forward(int dtype, int target_kind, const void *src, const void *target, const maskloss_shape *shape,
                      double alpha, double gamma, void *workspace, void *focal, void *dice, void *sums, void *stream)
 {
-    g_err[0] = 0;
+    err.clear();
     if (check_types(dtype, target_kind) != MASKLOSS_OK || check_shape(shape) != MASKLOSS_OK) return MASKLOSS_ERR_ARGUMENT;
     const int gm = gamma_mode(gamma);
     if (gm < 0) return MASKLOSS_ERR_ARGUMENT;
-    if (!(alpha == alpha)) return fail("alpha must be a number");
+    if (!(alpha == alpha)) return err.fail("alpha must be a number");
     const maskloss_shape &s = *shape;
     if (s.N == 0) return MASKLOSS_OK;
-    if (!src || !target || !focal || !dice || !sums) return fail("null pointer: src, target, focal, dice and sums are required");
-    if (!workspace && fwd_tiles(s) > 1) return fail("null pointer: workspace is required when an instance is more than one tile");
+    if (!src || !target || !focal || !dice || !sums) return err.fail("null pointer: src, target, focal, dice and sums are required");
+    if (!workspace && fwd_tiles(s) > 1) return err.fail("null pointer: workspace is required when an instance is more than one tile");
     hipStream_t st = (hipStream_t)stream;
-#define MASKLOSS_FWD(T) launch_forward<T>(target_kind, src, target, s, alpha, gamma, gm, workspace, focal, dice, sums, st)
-    switch (dtype) {
-    case MASKLOSS_F32: return MASKLOSS_FWD(float);
-    case MASKLOSS_F64: return MASKLOSS_FWD(double);
-    case MASKLOSS_BF16: return MASKLOSS_FWD(__hip_bfloat16);
-    default: return MASKLOSS_FWD(__half);
-    }
-#undef MASKLOSS_FWD
+    return dispatch(dtype, [&](auto t) {
+        return launch_forward<type_of<decltype(t)>>(target_kind, src, target, s, alpha, gamma, gm, workspace, focal, dice, sums, st);
+    });
 }
 
 int maskloss_backward(int dtype, int target_kind, const void *src, const void *target, const void *sums,
                       const void *grad_focal, const void *grad_dice, const maskloss_shape *shape, double alpha,
                       double gamma, void *grad_src, void *stream)
 {
-    g_err[0] = 0;
+    err.clear();
     if (check_types(dtype, target_kind) != MASKLOSS_OK || check_shape(shape) != MASKLOSS_OK) return MASKLOSS_ERR_ARGUMENT;
     const int gm = gamma_mode(gamma);
     if (gm < 0) return MASKLOSS_ERR_ARGUMENT;
-    if (!(alpha == alpha)) return fail("alpha must be a number");
+    if (!(alpha == alpha)) return err.fail("alpha must be a number");
     const maskloss_shape &s = *shape;
     if (s.N == 0) return MASKLOSS_OK;
     if (!src || !target || !sums || !grad_focal || !grad_dice || !grad_src)
-        return fail("null pointer: src, target, sums, grad_focal, grad_dice and grad_src are required");
+        return err.fail("null pointer: src, target, sums, grad_focal, grad_dice and grad_src are required");
     hipStream_t st = (hipStream_t)stream;
-#define MASKLOSS_BWD(T) launch_backward<T>(target_kind, src, target, sums, grad_focal, grad_dice, s, alpha, gamma, gm, grad_src, st)
-    switch (dtype) {
-    case MASKLOSS_F32: return MASKLOSS_BWD(float);
-    case MASKLOSS_F64: return MASKLOSS_BWD(double);
-    case MASKLOSS_BF16: return MASKLOSS_BWD(__hip_bfloat16);
-    default: return MASKLOSS_BWD(__half);
-    }
-#undef MASKLOSS_BWD
+    return dispatch(dtype, [&](auto t) {
+        return launch_backward<type_of<decltype(t)>>(target_kind, src, target, sums, grad_focal, grad_dice, s, alpha, gamma, gm,
+                                                     grad_src, st);
+    });
 }
 
 }  // extern "C"

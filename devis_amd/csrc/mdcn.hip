@@ -7,21 +7,7 @@
 
 namespace mdcn {
 
-thread_local char g_err[512] = "";
-
-int fail(const char *fmt, long long a, long long b)
-{
-    snprintf(g_err, sizeof(g_err), fmt, a, b);
-    return MDCN_ERR_ARGUMENT;
-}
-
-int fail_hip(const char *what, hipError_t e)
-{
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return MDCN_ERR_HIP;
-}
-
-void clear_error() { g_err[0] = 0; }
+thread_local Status err;
 
 // V channels of one pixel as one naturally aligned load / store (16 bytes at V = 16 / sizeof(T))
 template <typename T, int V> struct alignas(sizeof(T) * V) Pack { T v[V]; };
@@ -122,33 +108,17 @@ __global__ __launch_bounds__(kThreads) void mdcn_backward_kernel(const T *__rest
 // ---- host ----------------------------------------------------------------------------------------------------
 int check_shape(const mdcn_shape *s)
 {
-    if (!s) return fail("null pointer: shape");
+    if (!s) return err.fail("null pointer: shape");
     if (s->N < 0 || s->C <= 0 || s->H <= 0 || s->W <= 0 || s->Ho <= 0 || s->Wo <= 0 || s->Kh <= 0 || s->Kw <= 0 ||
         s->stride_h <= 0 || s->stride_w <= 0 || s->dil_h <= 0 || s->dil_w <= 0 || s->G <= 0)
-        return fail("sizes must be positive (N may be 0), padding not negative");
-    if (s->pad_h < 0 || s->pad_w < 0) return fail("sizes must be positive (N may be 0), padding not negative");
-    if (s->C % s->G) return fail("C = %lld is not a multiple of the offset groups G = %lld", s->C, s->G);
+        return err.fail("sizes must be positive (N may be 0), padding not negative");
+    if (s->pad_h < 0 || s->pad_w < 0) return err.fail("sizes must be positive (N may be 0), padding not negative");
+    if (s->C % s->G) return err.fail("C = %lld is not a multiple of the offset groups G = %lld", s->C, s->G);
     const long long eh = (long long)s->H + 2LL * s->pad_h - (long long)s->dil_h * (s->Kh - 1) - 1;
     const long long ew = (long long)s->W + 2LL * s->pad_w - (long long)s->dil_w * (s->Kw - 1) - 1;
     if (eh < 0 || ew < 0 || eh / s->stride_h + 1 != s->Ho || ew / s->stride_w + 1 != s->Wo)
-        return fail("Ho x Wo = %lld x %lld is not the output size of this convolution", s->Ho, s->Wo);
+        return err.fail("Ho x Wo = %lld x %lld is not the output size of this convolution", s->Ho, s->Wo);
     return MDCN_OK;
-}
-
-int elem_size(int dtype)
-{
-    switch (dtype) {
-    case MDCN_F32: return 4;
-    case MDCN_F64: return 8;
-    case MDCN_BF16: case MDCN_F16: case MDCN_BF16_OFF32: case MDCN_F16_OFF32: return 2;
-    default: return 0;
-    }
-}
-
-int check_launch(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MDCN_OK : fail_hip(what, e);
 }
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -166,15 +136,15 @@ int launch_im2col(const void *x, const void *off, const void *msk, const mdcn_sh
     constexpr int full = 16 / (int)sizeof(T);
     const int V = vector_width<T>(s, x, col);
     const long long total = (long long)s.N * s.Ho * s.Wo * s.Kh * s.Kw * (s.C / V);
-    const long long blocks = (total + kThreads - 1) / kThreads;
-    if (blocks > 0x7fffffffLL) return fail("too many workgroups for one launch (%lld): call with fewer images", blocks);
+    unsigned blocks;
+    if (err.grid_of(cdiv(total, kThreads), &blocks, kFewerImages)) return MDCN_ERR_ARGUMENT;
     if (V == full)
-        hipLaunchKernelGGL((mdcn_im2col_kernel<T, TO, full>), dim3((unsigned)blocks), dim3(kThreads), 0, st,
+        hipLaunchKernelGGL((mdcn_im2col_kernel<T, TO, full>), dim3(blocks), dim3(kThreads), 0, st,
                            (const T *)x, (const TO *)off, (const TO *)msk, (T *)col, s, total);
     else
-        hipLaunchKernelGGL((mdcn_im2col_kernel<T, TO, 1>), dim3((unsigned)blocks), dim3(kThreads), 0, st,
+        hipLaunchKernelGGL((mdcn_im2col_kernel<T, TO, 1>), dim3(blocks), dim3(kThreads), 0, st,
                            (const T *)x, (const TO *)off, (const TO *)msk, (T *)col, s, total);
-    return check_launch("mdcn_im2col_kernel");
+    return err.check_launch("mdcn_im2col_kernel");
 }
 
 // Lanes per (pixel, tap, group): among 32 and 64 the one that pads the group's channels least (ties: the wider, one
@@ -197,13 +167,12 @@ int launch_backward(int grads, const void *x, const void *off, const void *msk, 
     typedef typename Acc<T>::type A;
     const int team = team_size(s.C / s.G);
     const long long items = (long long)s.N * s.Ho * s.Wo * s.Kh * s.Kw * s.G;
-    const int per_block = kThreads / team;
-    const long long blocks = (items + per_block - 1) / per_block;
-    if (blocks > 0x7fffffffLL) return fail("too many workgroups for one launch (%lld): call with fewer images", blocks);
-    hipLaunchKernelGGL((mdcn_backward_kernel<T, TO>), dim3((unsigned)blocks), dim3(kThreads), 0, st, (const T *)x,
+    unsigned blocks;
+    if (err.grid_of(cdiv(items, kThreads / team), &blocks, kFewerImages)) return MDCN_ERR_ARGUMENT;
+    hipLaunchKernelGGL((mdcn_backward_kernel<T, TO>), dim3(blocks), dim3(kThreads), 0, st, (const T *)x,
                        (const TO *)off, (const TO *)msk, (const T *)gcol, (A *)gin, (TO *)goff, (TO *)gmsk, s, items, team,
                        grads);
-    return check_launch("mdcn_backward_kernel");
+    return err.check_launch("mdcn_backward_kernel");
 }
 
 }  // namespace mdcn
@@ -214,68 +183,53 @@ extern "C" {
 
 int mdcn_version(void) { return MDCN_ABI_VERSION; }
 
-const char *mdcn_last_error(void) { return g_err; }
+const char *mdcn_last_error(void) { return err.msg; }
 
 long long mdcn_workspace_bytes(int dtype, const mdcn_shape *shape, int batch)
 {
-    g_err[0] = 0;
-    if (!elem_size(dtype)) return fail("bad dtype code %lld", dtype);
-    if (!shape) return fail("null pointer: shape");
+    err.clear();
+    if (check_dtype(dtype) != MDCN_OK) return MDCN_ERR_ARGUMENT;
+    if (!shape) return err.fail("null pointer: shape");
     mdcn_shape s = *shape;
     s.N = 0;
     if (check_shape(&s) != MDCN_OK) return MDCN_ERR_ARGUMENT;
-    if (batch < 0) return fail("sizes must be positive (N may be 0), padding not negative");
-    return (long long)batch * s.Ho * s.Wo * s.Kh * s.Kw * s.C * elem_size(dtype);
+    if (batch < 0) return err.fail("sizes must be positive (N may be 0), padding not negative");
+    return (long long)batch * s.Ho * s.Wo * s.Kh * s.Kw * s.C * elem_size(input_code(dtype));
 }
 
 int mdcn_im2col(int dtype, const void *input, const void *offset, const void *mask, const mdcn_shape *shape,
                 void *columns, void *stream)
 {
-    g_err[0] = 0;
-    if (!elem_size(dtype)) return fail("bad dtype code %lld", dtype);
+    err.clear();
+    if (check_dtype(dtype) != MDCN_OK) return MDCN_ERR_ARGUMENT;
     if (check_shape(shape) != MDCN_OK) return MDCN_ERR_ARGUMENT;
-    if (!input || !offset || !columns) return fail("null pointer: input, offset and columns are required");
+    if (!input || !offset || !columns) return err.fail("null pointer: input, offset and columns are required");
     if (shape->N == 0) return MDCN_OK;
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-    case MDCN_F32: return launch_im2col<float, float>(input, offset, mask, *shape, columns, st);
-    case MDCN_F64: return launch_im2col<double, double>(input, offset, mask, *shape, columns, st);
-    case MDCN_BF16: return launch_im2col<__hip_bfloat16, __hip_bfloat16>(input, offset, mask, *shape, columns, st);
-    case MDCN_F16: return launch_im2col<__half, __half>(input, offset, mask, *shape, columns, st);
-    case MDCN_BF16_OFF32: return launch_im2col<__hip_bfloat16, float>(input, offset, mask, *shape, columns, st);
-    default: return launch_im2col<__half, float>(input, offset, mask, *shape, columns, st);
-    }
+    return dispatch_types(dtype, [&](auto t, auto to) {
+        return launch_im2col<type_of<decltype(t)>, type_of<decltype(to)>>(input, offset, mask, *shape, columns, st);
+    });
 }
 
 int mdcn_backward(int grads, int dtype, const void *input, const void *offset, const void *mask,
                   const void *grad_columns, const mdcn_shape *shape, void *grad_input_acc, void *grad_offset,
                   void *grad_mask, void *stream)
 {
-    g_err[0] = 0;
-    if (!elem_size(dtype)) return fail("bad dtype code %lld", dtype);
+    err.clear();
+    if (check_dtype(dtype) != MDCN_OK) return MDCN_ERR_ARGUMENT;
     if (grads < 0 || grads > (MDCN_GRAD_INPUT | MDCN_GRAD_SAMPLING))
-        return fail("grads = %lld is not a mask of MDCN_GRAD_INPUT and MDCN_GRAD_SAMPLING", grads);
+        return err.fail("grads = %lld is not a mask of MDCN_GRAD_INPUT and MDCN_GRAD_SAMPLING", grads);
     if (check_shape(shape) != MDCN_OK) return MDCN_ERR_ARGUMENT;
-    if (!input || !offset || !grad_columns) return fail("null pointer: input, offset and grad_columns are required");
-    if ((grads & MDCN_GRAD_INPUT) && !grad_input_acc) return fail("null pointer: grad_input_acc with MDCN_GRAD_INPUT");
+    if (!input || !offset || !grad_columns) return err.fail("null pointer: input, offset and grad_columns are required");
+    if ((grads & MDCN_GRAD_INPUT) && !grad_input_acc) return err.fail("null pointer: grad_input_acc with MDCN_GRAD_INPUT");
     if ((grads & MDCN_GRAD_SAMPLING) && (!grad_offset || !grad_mask != !mask))
-        return fail("null pointer: MDCN_GRAD_SAMPLING needs grad_offset, and grad_mask exactly when there is a mask");
+        return err.fail("null pointer: MDCN_GRAD_SAMPLING needs grad_offset, and grad_mask exactly when there is a mask");
     if (shape->N == 0 || grads == 0) return MDCN_OK;
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-    case MDCN_F32:
-        return launch_backward<float, float>(grads, input, offset, mask, grad_columns, *shape, grad_input_acc, grad_offset, grad_mask, st);
-    case MDCN_F64:
-        return launch_backward<double, double>(grads, input, offset, mask, grad_columns, *shape, grad_input_acc, grad_offset, grad_mask, st);
-    case MDCN_BF16:
-        return launch_backward<__hip_bfloat16, __hip_bfloat16>(grads, input, offset, mask, grad_columns, *shape, grad_input_acc, grad_offset, grad_mask, st);
-    case MDCN_F16:
-        return launch_backward<__half, __half>(grads, input, offset, mask, grad_columns, *shape, grad_input_acc, grad_offset, grad_mask, st);
-    case MDCN_BF16_OFF32:
-        return launch_backward<__hip_bfloat16, float>(grads, input, offset, mask, grad_columns, *shape, grad_input_acc, grad_offset, grad_mask, st);
-    default:
-        return launch_backward<__half, float>(grads, input, offset, mask, grad_columns, *shape, grad_input_acc, grad_offset, grad_mask, st);
-    }
+    return dispatch_types(dtype, [&](auto t, auto to) {
+        return launch_backward<type_of<decltype(t)>, type_of<decltype(to)>>(
+            grads, input, offset, mask, grad_columns, *shape, grad_input_acc, grad_offset, grad_mask, st);
+    });
 }
 
 }  // extern "C"

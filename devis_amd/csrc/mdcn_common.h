@@ -1,35 +1,20 @@
 // mdcn_common.h -- what the translation units of the modulated deformable convolution share (mdcn.hip: im2col and the
-// default backward; mdcn_det.hip: the fixed-point grad_input): the storage types, where a tap samples and its bilinear
-// weights, and the host helpers of the entry points.  Both backward kernels take a tap's corners and weights from locate(),
-// so they scatter the same products to the same elements.
+// default backward; mdcn_det.hip: the fixed-point grad_input): where a tap samples and its bilinear weights, and the host
+// helpers of the entry points.  Both backward kernels take a tap's corners and weights from locate(), so they scatter the
+// same products to the same elements.  The storage types and what every operator's host side needs are op_common.h.
 #ifndef MDCN_COMMON_H_
 #define MDCN_COMMON_H_
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-#include <stdint.h>
-#include <stdio.h>
-
+#include "op_common.h"
 #include "mdcn.h"
-
-#pragma clang fp contract(off)
 
 namespace mdcn {
 
+using namespace devis;
+
+static_assert(MDCN_OK == kOk && MDCN_ERR_ARGUMENT == kErrArgument && MDCN_ERR_HIP == kErrHip, "status codes");
+static_assert(MDCN_F32 == kF32 && MDCN_F64 == kF64 && MDCN_BF16 == kBF16 && MDCN_F16 == kF16, "dtype codes");
+
 constexpr int kThreads = 256;       // 4 waves per workgroup
-
-// ---- storage types: arithmetic in float, in double for double ------------------------------------------------
-template <typename T> struct Acc { typedef float type; };
-template <> struct Acc<double> { typedef double type; };
-
-__device__ __forceinline__ float to_acc(float v) { return v; }
-__device__ __forceinline__ double to_acc(double v) { return v; }
-__device__ __forceinline__ float to_acc(__hip_bfloat16 v) { return __bfloat162float(v); }
-__device__ __forceinline__ float to_acc(__half v) { return __half2float(v); }
-__device__ __forceinline__ void from_acc(float &d, float v) { d = v; }
-__device__ __forceinline__ void from_acc(double &d, double v) { d = v; }
-__device__ __forceinline__ void from_acc(__hip_bfloat16 &d, float v) { d = __float2bfloat16(v); }
-__device__ __forceinline__ void from_acc(__half &d, float v) { d = __float2half(v); }
 
 // ---- one tap of one output pixel -----------------------------------------------------------------------------
 // Where tap k of output pixel `pix` (of this call's N*Ho*Wo) samples for offset group g, the four bilinear weights
@@ -79,13 +64,20 @@ __device__ __forceinline__ Tap<A> locate(const mdcn_shape &s, const TO *__restri
 }
 
 // ---- host (mdcn.hip) -----------------------------------------------------------------------------------------
-int fail(const char *fmt, long long a = 0, long long b = 0);    // sets mdcn_last_error(); returns MDCN_ERR_ARGUMENT
-int fail_hip(const char *what, hipError_t e);                   // "<what>: <HIP's message>"; returns MDCN_ERR_HIP
-void clear_error();
+extern thread_local Status err;     // mdcn_last_error(), of both translation units
 int check_shape(const mdcn_shape *s);
-int elem_size(int dtype);                                       // 0 for a bad dtype code
-int check_launch(const char *what);
 int team_size(int Cg);      // lanes per (pixel, tap, group) of the backward kernels
+
+// a dtype code as (code of input / columns, whether offset / mask are float32 beside them)
+inline bool off32(int dtype) { return dtype == MDCN_BF16_OFF32 || dtype == MDCN_F16_OFF32; }
+inline int input_code(int dtype) { return off32(dtype) ? dtype - MDCN_BF16_OFF32 + MDCN_BF16 : dtype; }
+inline int check_dtype(int dtype) { return elem_size(input_code(dtype)) ? MDCN_OK : err.fail("bad dtype code %lld", dtype); }
+
+// f(Tag<T>, Tag<TO>): T the type of input / columns, TO that of offset / mask
+template <typename F> int dispatch_types(int dtype, F &&f) { return dispatch(input_code(dtype), off32(dtype), f); }
+
+// the message of a grid that Status::grid_of refuses ends in this
+constexpr const char *kFewerImages = ": call with fewer images";
 
 }  // namespace mdcn
 #endif  // MDCN_COMMON_H_

@@ -48,16 +48,6 @@ __device__ __forceinline__ long long terms_bound(const mdcn_shape &s)
     return (long long)s.Ho * s.Wo * s.Kh * s.Kw;
 }
 
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_xor(v, d, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 // grid (N, parts): workgroup `blockIdx.y` of image `blockIdx.x` strides over the image's mask and grad_columns rows.
 // maxima[2n] = bits of the largest finite |mask| (of 1 without a mask), maxima[2n + 1] = of the largest finite |grad_columns|;
 // unsigned order is magnitude order for non-negative floats, and a max does not depend on the order it is taken in.
@@ -170,11 +160,10 @@ int launch_fixed(const void *off, const void *msk, const void *gcol, const mdcn_
     unsigned long long *maxima = reinterpret_cast<unsigned long long *>(ws + l.maxima);
     const int team = team_size(s.C / s.G);
     const long long items = (long long)s.N * s.Ho * s.Wo * s.Kh * s.Kw * s.G;
-    const int per_block = kThreads / team;
-    const long long blocks = (items + per_block - 1) / per_block;
-    if (blocks > 0x7fffffffLL) return fail("too many workgroups for one launch (%lld): call with fewer images", blocks);
+    unsigned blocks;
+    if (err.grid_of(cdiv(items, kThreads / team), &blocks, kFewerImages)) return MDCN_ERR_ARGUMENT;
     const hipError_t zeroed = hipMemsetAsync(ws, 0, (size_t)l.total, st);
-    if (zeroed != hipSuccess) return fail_hip("mdcn_backward_input_fixed: hipMemsetAsync(workspace)", zeroed);
+    if (zeroed != hipSuccess) return err.fail_hip("mdcn_backward_input_fixed: hipMemsetAsync(workspace)", zeroed);
 
     // (image, part) workgroups: parts so that a batch covers the chip about twice; an image's maxima do not depend on the split
     const long long per_image = (long long)s.Ho * s.Wo * s.Kh * s.Kw * s.C;
@@ -184,17 +173,17 @@ int launch_fixed(const void *off, const void *msk, const void *gcol, const mdcn_
     parts = parts < 1 ? 1 : (parts > 65535 ? 65535 : parts);
     hipLaunchKernelGGL((mdcn_fixed_maxima_kernel<T, TO>), dim3((unsigned)s.N, (unsigned)parts), dim3(kThreads), 0, st,
                        (const TO *)msk, (const T *)gcol, maxima, s);
-    int rc = check_launch("mdcn_fixed_maxima_kernel");
+    int rc = err.check_launch("mdcn_fixed_maxima_kernel");
     if (rc != MDCN_OK) return rc;
-    hipLaunchKernelGGL((mdcn_fixed_scatter_kernel<T, TO>), dim3((unsigned)blocks), dim3(kThreads), 0, st, (const TO *)off,
+    hipLaunchKernelGGL((mdcn_fixed_scatter_kernel<T, TO>), dim3(blocks), dim3(kThreads), 0, st, (const TO *)off,
                        (const TO *)msk, (const T *)gcol, maxima, acc, cls, s, items, team);
-    rc = check_launch("mdcn_fixed_scatter_kernel");
+    rc = err.check_launch("mdcn_fixed_scatter_kernel");
     if (rc != MDCN_OK) return rc;
     const long long total = (long long)s.N * s.H * s.W * s.C;
     const long long want = (total + kThreads - 1) / kThreads;
     hipLaunchKernelGGL((mdcn_fixed_convert_kernel<A>), dim3((unsigned)(want < 65536 * 16 ? want : 65536 * 16)), dim3(kThreads),
                        0, st, maxima, acc, cls, (A *)gin, s, total);
-    return check_launch("mdcn_fixed_convert_kernel");
+    return err.check_launch("mdcn_fixed_convert_kernel");
 }
 
 }  // namespace
@@ -206,35 +195,31 @@ extern "C" {
 
 long long mdcn_fixed_workspace_bytes(int dtype, const mdcn_shape *shape, int batch)
 {
-    clear_error();
-    if (!elem_size(dtype)) return fail("bad dtype code %lld", dtype);
-    if (!shape) return fail("null pointer: shape");
+    err.clear();
+    if (check_dtype(dtype) != MDCN_OK) return MDCN_ERR_ARGUMENT;
+    if (!shape) return err.fail("null pointer: shape");
     mdcn_shape s = *shape;
     s.N = 0;
     if (check_shape(&s) != MDCN_OK) return MDCN_ERR_ARGUMENT;
-    if (batch < 0) return fail("sizes must be positive (N may be 0), padding not negative");
+    if (batch < 0) return err.fail("sizes must be positive (N may be 0), padding not negative");
     return fixed_layout(s, batch).total;
 }
 
 int mdcn_backward_input_fixed(int dtype, const void *offset, const void *mask, const void *grad_columns,
                               const mdcn_shape *shape, void *workspace, void *grad_input, void *stream)
 {
-    clear_error();
-    if (!elem_size(dtype)) return fail("bad dtype code %lld", dtype);
+    err.clear();
+    if (check_dtype(dtype) != MDCN_OK) return MDCN_ERR_ARGUMENT;
     if (check_shape(shape) != MDCN_OK) return MDCN_ERR_ARGUMENT;
     if (!offset || !grad_columns || !workspace || !grad_input)
-        return fail("null pointer: offset, grad_columns, workspace and grad_input are required");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return fail("workspace must be 256-byte aligned");
+        return err.fail("null pointer: offset, grad_columns, workspace and grad_input are required");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return err.fail("workspace must be 256-byte aligned");
     if (shape->N == 0) return MDCN_OK;
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-    case MDCN_F32: return launch_fixed<float, float>(offset, mask, grad_columns, *shape, workspace, grad_input, st);
-    case MDCN_F64: return launch_fixed<double, double>(offset, mask, grad_columns, *shape, workspace, grad_input, st);
-    case MDCN_BF16: return launch_fixed<__hip_bfloat16, __hip_bfloat16>(offset, mask, grad_columns, *shape, workspace, grad_input, st);
-    case MDCN_F16: return launch_fixed<__half, __half>(offset, mask, grad_columns, *shape, workspace, grad_input, st);
-    case MDCN_BF16_OFF32: return launch_fixed<__hip_bfloat16, float>(offset, mask, grad_columns, *shape, workspace, grad_input, st);
-    default: return launch_fixed<__half, float>(offset, mask, grad_columns, *shape, workspace, grad_input, st);
-    }
+    return dispatch_types(dtype, [&](auto t, auto to) {
+        return launch_fixed<type_of<decltype(t)>, type_of<decltype(to)>>(offset, mask, grad_columns, *shape, workspace,
+                                                                                     grad_input, st);
+    });
 }
 
 }  // extern "C"

@@ -4,14 +4,15 @@
 //
 // The kernels are templates of the storage type of x alone.  Whether weight / bias, extra and out are float32 beside a
 // 16-bit x is a kernel argument: a wave-uniform branch around a load or a store, not a compile-time variant.
-#include "mdcn_common.h"    // the storage types (Acc, to_acc, from_acc)
+#include "op_common.h"
 #include "mhstage.h"
 
 namespace mhstage {
 
-using mdcn::Acc;
-using mdcn::from_acc;
-using mdcn::to_acc;
+using namespace devis;
+
+static_assert(MHSTAGE_OK == kOk && MHSTAGE_ERR_ARGUMENT == kErrArgument && MHSTAGE_ERR_HIP == kErrHip, "status codes");
+static_assert(MHSTAGE_F32 == kF32 && MHSTAGE_F64 == kF64 && MHSTAGE_BF16 == kBF16 && MHSTAGE_F16 == kF16, "dtype codes");
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -24,26 +25,7 @@ constexpr int kBwdPixels = 64 * kBP;
 constexpr int kBC = 16;                         // backward pass 1: channels per workgroup
 constexpr int kGxPer = 4;                       // backward pass 2: elements per lane
 
-thread_local char g_err[512] = "";
-
-int fail(const char *fmt, long long a = 0, long long b = 0)
-{
-    snprintf(g_err, sizeof(g_err), fmt, a, b);
-    return MHSTAGE_ERR_ARGUMENT;
-}
-
-int check_launch(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return MHSTAGE_OK;
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return MHSTAGE_ERR_HIP;
-}
-
-__device__ __forceinline__ float mad(float a, float b, float c) { return fmaf(a, b, c); }
-__device__ __forceinline__ double mad(double a, double b, double c) { return fma(a, b, c); }
-__device__ __forceinline__ float rsq(float v) { return 1.0f / sqrtf(v); }
-__device__ __forceinline__ double rsq(double v) { return 1.0 / sqrt(v); }
+thread_local Status err;     // mhstage_last_error()
 
 // PyTorch's mode="nearest" source index (include/mhstage.h), in float32 for every dtype
 __device__ __forceinline__ int src_index(int d, int in, int out)
@@ -83,28 +65,7 @@ __device__ __forceinline__ long long index_at(const void *idx, int is64, long lo
 
 // the forward's expressions, shared with the backward so that its gate is the forward's
 template <typename A> __device__ __forceinline__ A xhat_of(A x, A mean, A rstd) { return (x - mean) * rstd; }
-template <typename A> __device__ __forceinline__ A z_of(A xhat, A w, A b) { return mad(xhat, w, b); }
-
-// butterfly over the 64 lanes: every lane ends with the same bits
-template <typename A> __device__ __forceinline__ A wave_sum(A v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// the workgroup's sum in every thread: butterflies, then the waves in ascending order.  `red` is reusable after return.
-template <typename A> __device__ __forceinline__ A block_sum(A v, A *red)
-{
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    A r = red[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) r += red[w];
-    __syncthreads();
-    return r;
-}
+template <typename A> __device__ __forceinline__ A z_of(A xhat, A w, A b) { return fma_of(xhat, w, b); }
 
 // ---- statistics --------------------------------------------------------------------------------------------------------
 // A workgroup owns one tile of kStatTile elements of one (image, group) block, which is contiguous in NCHW: the tile's
@@ -131,18 +92,18 @@ __global__ __launch_bounds__(kThreads) void stat_kernel(const T *__restrict__ x,
         v[j] = i < cnt ? (A)to_acc(p[i]) : (A)0;
         sum += v[j];
     }
-    const A m = block_sum(sum, red) / (A)cnt;
+    const A m = block_sum<kWaves>(sum, red) / (A)cnt;
     A dev = (A)0;
 #pragma unroll
     for (int j = 0; j < kStatPer; ++j) {
         const A d = v[j] - m;
-        if (j * kThreads + tid < cnt) dev = mad(d, d, dev);
+        if (j * kThreads + tid < cnt) dev = fma_of(d, d, dev);
     }
-    const A m2 = block_sum(dev, red);
+    const A m2 = block_sum<kWaves>(dev, red);
     if (tid == 0) {
         if (tiles == 1) {
             mean[blk] = m;
-            rstd[blk] = rsq(m2 / (A)L + eps);
+            rstd[blk] = rsqrt_of(m2 / (A)L + eps);
         } else {
             ws[(blk * tiles + tile) * 2] = m;
             ws[(blk * tiles + tile) * 2 + 1] = m2;
@@ -163,17 +124,17 @@ __global__ __launch_bounds__(kThreads) void stat_combine_kernel(const A *__restr
     const A *wp = ws + blk * tiles * 2;
     const int last = (int)(L - (long long)(tiles - 1) * kStatTile);
     A s = (A)0;
-    for (int i = lane; i < tiles; i += 64) s = mad((A)(i == tiles - 1 ? last : kStatTile), wp[2 * i], s);
+    for (int i = lane; i < tiles; i += 64) s = fma_of((A)(i == tiles - 1 ? last : kStatTile), wp[2 * i], s);
     const A m = wave_sum(s) / (A)L;
     A q = (A)0;
     for (int i = lane; i < tiles; i += 64) {
         const A d = wp[2 * i] - m;
-        q += mad((A)(i == tiles - 1 ? last : kStatTile) * d, d, wp[2 * i + 1]);
+        q += fma_of((A)(i == tiles - 1 ? last : kStatTile) * d, d, wp[2 * i + 1]);
     }
     q = wave_sum(q);
     if (lane == 0) {
         mean[blk] = m;
-        rstd[blk] = rsq(q / (A)L + eps);
+        rstd[blk] = rsqrt_of(q / (A)L + eps);
     }
 }
 
@@ -287,7 +248,7 @@ __global__ __launch_bounds__(kThreads) void bwd_gate_kernel(const T *__restrict_
             const A dv = z_of(xh, wv, bv) > (A)0 ? gsum : (A)0;
             dy[row + at[j]] = dv;
             a1 += dv;
-            a2 = mad(dv, xh, a2);
+            a2 = fma_of(dv, xh, a2);
         }
         a1 = wave_sum(a1);
         a2 = wave_sum(a2);
@@ -330,8 +291,8 @@ __global__ __launch_bounds__(kThreads) void bwd_combine_kernel(const typename Ac
             nc[(n * C + c) * 2 + 1] = a2;
         }
         const A wv = ld<T>(weight, c, pwide);
-        s1 = mad(wv, a1, s1);
-        s2 = mad(wv, a2, s2);
+        s1 = fma_of(wv, a1, s1);
+        s2 = fma_of(wv, a2, s2);
     }
     if (lane == 0) {
         gs[blk * 2] = s1;
@@ -410,47 +371,27 @@ __global__ __launch_bounds__(kThreads) void bwd_skip_kernel(const void *__restri
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------
-int elem_size(int dtype)
-{
-    switch (dtype) {
-    case MHSTAGE_F32: return 4;
-    case MHSTAGE_F64: return 8;
-    case MHSTAGE_BF16: case MHSTAGE_F16: return 2;
-    default: return 0;
-    }
-}
-
-int acc_size(int dtype) { return dtype == MHSTAGE_F64 ? 8 : 4; }
-long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
-
 int check_shape(const mhstage_shape *s, bool with_skip)
 {
-    if (!s) return fail("null pointer: shape");
+    if (!s) return err.fail("null pointer: shape");
     if (s->N < 0 || s->E < 0 || s->C <= 0 || s->G <= 0 || s->h <= 0 || s->w <= 0 || s->H <= 0 || s->W <= 0)
-        return fail("sizes must be positive (N and E may be 0)");
-    if (with_skip && s->F <= 0) return fail("sizes must be positive: F = %lld beside a skip", s->F);
-    if (s->C % s->G != 0) return fail("C = %lld channels are not a multiple of the G = %lld groups", s->C, s->G);
-    if ((long long)s->h * s->w > 0x7fffffffLL) return fail("h * w = %lld does not fit 31 bits", (long long)s->h * s->w);
-    if ((long long)s->H * s->W > 0x7fffffffLL) return fail("H * W = %lld does not fit 31 bits", (long long)s->H * s->W);
-    if ((long long)s->C + s->E > 0x7fffffffLL) return fail("C + E = %lld does not fit 31 bits", (long long)s->C + s->E);
+        return err.fail("sizes must be positive (N and E may be 0)");
+    if (with_skip && s->F <= 0) return err.fail("sizes must be positive: F = %lld beside a skip", s->F);
+    if (s->C % s->G != 0) return err.fail("C = %lld channels are not a multiple of the G = %lld groups", s->C, s->G);
+    if ((long long)s->h * s->w > 0x7fffffffLL) return err.fail("h * w = %lld does not fit 31 bits", (long long)s->h * s->w);
+    if ((long long)s->H * s->W > 0x7fffffffLL) return err.fail("H * W = %lld does not fit 31 bits", (long long)s->H * s->W);
+    if ((long long)s->C + s->E > 0x7fffffffLL) return err.fail("C + E = %lld does not fit 31 bits", (long long)s->C + s->E);
     if ((long long)(s->C / s->G) * s->h * s->w > 0x7fffffffLL)
-        return fail("a group block of %lld elements does not fit 31 bits", (long long)(s->C / s->G) * s->h * s->w);
+        return err.fail("a group block of %lld elements does not fit 31 bits", (long long)(s->C / s->G) * s->h * s->w);
     return MHSTAGE_OK;
 }
 
 int check_types(int dtype, int param_wide, int extra_wide, int out_wide)
 {
-    if (!elem_size(dtype)) return fail("bad dtype code %lld", dtype);
-    if (((param_wide | extra_wide | out_wide) & ~1) != 0) return fail("a wide flag must be 0 or 1");
+    if (!elem_size(dtype)) return err.fail("bad dtype code %lld", dtype);
+    if (((param_wide | extra_wide | out_wide) & ~1) != 0) return err.fail("a wide flag must be 0 or 1");
     if ((param_wide || extra_wide || out_wide) && elem_size(dtype) != 2)
-        return fail("a wide (float32) tensor goes beside a 16-bit dtype only, not beside dtype code %lld", dtype);
-    return MHSTAGE_OK;
-}
-
-int grid_of(long long blocks, unsigned *out)
-{
-    if (blocks > 0x7fffffffLL) return fail("too many workgroups for one launch (%lld)", blocks);
-    *out = (unsigned)blocks;
+        return err.fail("a wide (float32) tensor goes beside a 16-bit dtype only, not beside dtype code %lld", dtype);
     return MHSTAGE_OK;
 }
 
@@ -467,7 +408,7 @@ int launch_forward(int pwide, int ewide, int owide, const void *x, const void *w
     const int tiles = stat_tiles(s);
     const int ptiles = (int)cdiv((long long)s.H * s.W, kTP), ctiles = (int)cdiv((long long)s.C + s.E, kTC);
     unsigned g1, g2, g3;
-    if (grid_of(blocks * tiles, &g1) || grid_of(cdiv(blocks, kWaves), &g2) || grid_of((long long)s.N * ctiles * ptiles, &g3))
+    if (err.grid_of(blocks * tiles, &g1) || err.grid_of(cdiv(blocks, kWaves), &g2) || err.grid_of((long long)s.N * ctiles * ptiles, &g3))
         return MHSTAGE_ERR_ARGUMENT;
     hipLaunchKernelGGL((stat_kernel<T>), dim3(g1), dim3(kThreads), 0, st, (const T *)x, (A *)ws, (A *)mean, (A *)rstd, L, tiles,
                        (A)eps);
@@ -476,7 +417,7 @@ int launch_forward(int pwide, int ewide, int owide, const void *x, const void *w
                            blocks, L, tiles, (A)eps);
     hipLaunchKernelGGL((apply_kernel<T>), dim3(g3), dim3(kThreads), 0, st, (const T *)x, weight, bias, (const A *)mean,
                        (const A *)rstd, (const T *)skip, sidx, is64, extra, out, s, pwide, ewide, owide, ptiles, ctiles);
-    return check_launch("mhstage_forward");
+    return err.check_launch("mhstage_forward");
 }
 
 template <typename T>
@@ -491,8 +432,8 @@ int launch_backward(int grads, int pwide, int owide, const void *x, const void *
         const int stiles = bwd_tiles(s), ctiles = (int)cdiv(s.C, kBC), ptiles = (int)cdiv(p, kThreads * kGxPer);
         A *part = (A *)ws, *nc = part + (long long)s.N * s.C * stiles * 2, *gsum = nc + (long long)s.N * s.C * 2;
         unsigned g1, g2, g3, g4;
-        if (grid_of((long long)s.N * ctiles * stiles, &g1) || grid_of(cdiv((long long)s.N * s.G, kWaves), &g2) ||
-            grid_of((long long)s.N * s.C * ptiles, &g3) || grid_of(cdiv(s.C, kWaves), &g4))
+        if (err.grid_of((long long)s.N * ctiles * stiles, &g1) || err.grid_of(cdiv((long long)s.N * s.G, kWaves), &g2) ||
+            err.grid_of((long long)s.N * s.C * ptiles, &g3) || err.grid_of(cdiv(s.C, kWaves), &g4))
             return MHSTAGE_ERR_ARGUMENT;
         hipLaunchKernelGGL((bwd_gate_kernel<T>), dim3(g1), dim3(kThreads), 0, st, (const T *)x, weight, bias, (const A *)mean,
                            (const A *)rstd, gout, gs_n, gs_c, gs_y, gs_x, (A *)dy, part, s, pwide, owide, stiles, ctiles);
@@ -509,11 +450,11 @@ int launch_backward(int grads, int pwide, int owide, const void *x, const void *
     if (grads & MHSTAGE_GRAD_SKIP) {
         const int ptiles = (int)cdiv(P, kThreads);
         unsigned g5;
-        if (grid_of((long long)s.F * s.C * ptiles, &g5)) return MHSTAGE_ERR_ARGUMENT;
+        if (err.grid_of((long long)s.F * s.C * ptiles, &g5)) return MHSTAGE_ERR_ARGUMENT;
         hipLaunchKernelGGL((bwd_skip_kernel<T>), dim3(g5), dim3(kThreads), 0, st, gout, gs_n, gs_c, gs_x, sidx, is64,
                            (T *)gskip, s.N, s.C, (int)P, ptiles, owide);
     }
-    return check_launch("mhstage_backward");
+    return err.check_launch("mhstage_backward");
 }
 
 }  // namespace mhstage
@@ -524,7 +465,7 @@ extern "C" {
 
 int mhstage_version(void) { return MHSTAGE_ABI_VERSION; }
 
-const char *mhstage_last_error(void) { return g_err; }
+const char *mhstage_last_error(void) { return err.msg; }
 
 int mhstage_tile(int which)
 {
@@ -539,8 +480,8 @@ int mhstage_tile(int which)
 
 long long mhstage_workspace_bytes(int dtype, const mhstage_shape *shape)
 {
-    g_err[0] = 0;
-    if (!elem_size(dtype)) return fail("bad dtype code %lld", dtype);
+    err.clear();
+    if (!elem_size(dtype)) return err.fail("bad dtype code %lld", dtype);
     if (check_shape(shape, false) != MHSTAGE_OK) return MHSTAGE_ERR_ARGUMENT;
     const mhstage_shape &s = *shape;
     const long long fwd = (long long)s.N * s.G * stat_tiles(s) * 2;
@@ -554,29 +495,23 @@ int mhstage_forward(int dtype, int param_wide, int extra_wide, int out_wide, con
                     const void *extra, const mhstage_shape *shape, void *workspace, void *mean, void *rstd, void *out,
                     void *stream)
 {
-    g_err[0] = 0;
+    err.clear();
     if (check_types(dtype, param_wide, extra_wide, out_wide) != MHSTAGE_OK || check_shape(shape, skip != nullptr) != MHSTAGE_OK)
         return MHSTAGE_ERR_ARGUMENT;
     const mhstage_shape &s = *shape;
     if (!skip && !extra && (s.H != s.h || s.W != s.w))
-        return fail("without skip and extra the output map is the input's: H, W must be h, w");
-    if (!skip && skip_index) return fail("skip_index without skip");
-    if (skip && !skip_index && s.F != s.N) return fail("without skip_index F = %lld must equal N = %lld", s.F, s.N);
-    if ((s.E > 0) != (extra != nullptr)) return fail("null pointer: extra must be given exactly when E = %lld > 0", s.E);
+        return err.fail("without skip and extra the output map is the input's: H, W must be h, w");
+    if (!skip && skip_index) return err.fail("skip_index without skip");
+    if (skip && !skip_index && s.F != s.N) return err.fail("without skip_index F = %lld must equal N = %lld", s.F, s.N);
+    if ((s.E > 0) != (extra != nullptr)) return err.fail("null pointer: extra must be given exactly when E = %lld > 0", s.E);
     if (s.N == 0) return MHSTAGE_OK;
     if (!x || !weight || !bias || !workspace || !mean || !rstd || !out)
-        return fail("null pointer: x, weight, bias, workspace, mean, rstd and out are required");
+        return err.fail("null pointer: x, weight, bias, workspace, mean, rstd and out are required");
     hipStream_t st = (hipStream_t)stream;
-#define MHSTAGE_FWD(T)                                                                                                   \
-    launch_forward<T>(param_wide, extra_wide, out_wide, x, weight, bias, eps, skip, skip_index, index_is64, extra, s,    \
-                      workspace, mean, rstd, out, st)
-    switch (dtype) {
-    case MHSTAGE_F32: return MHSTAGE_FWD(float);
-    case MHSTAGE_F64: return MHSTAGE_FWD(double);
-    case MHSTAGE_BF16: return MHSTAGE_FWD(__hip_bfloat16);
-    default: return MHSTAGE_FWD(__half);
-    }
-#undef MHSTAGE_FWD
+    return dispatch(dtype, [&](auto t) {
+        return launch_forward<type_of<decltype(t)>>(param_wide, extra_wide, out_wide, x, weight, bias, eps, skip, skip_index,
+                                                    index_is64, extra, s, workspace, mean, rstd, out, st);
+    });
 }
 
 int mhstage_backward(int grads, int dtype, int param_wide, int out_wide, const void *x, const void *weight,
@@ -584,38 +519,33 @@ int mhstage_backward(int grads, int dtype, int param_wide, int out_wide, const v
                      const void *grad_out, int grad_out_layout, const mhstage_shape *shape, void *workspace, void *dy,
                      void *grad_x, void *grad_weight, void *grad_bias, void *grad_skip, void *stream)
 {
-    g_err[0] = 0;
+    err.clear();
     const int all = MHSTAGE_GRAD_X | MHSTAGE_GRAD_WEIGHT | MHSTAGE_GRAD_BIAS | MHSTAGE_GRAD_SKIP;
     if (check_types(dtype, param_wide, 0, out_wide) != MHSTAGE_OK) return MHSTAGE_ERR_ARGUMENT;
-    if (grads < 0 || grads > all) return fail("grads = %lld is not a mask of the MHSTAGE_GRAD_* bits", grads);
-    if (grad_out_layout != 0 && grad_out_layout != 1) return fail("grad_out_layout = %lld must be 0 (NCHW) or 1 (channels-last)", grad_out_layout);
+    if (grads < 0 || grads > all) return err.fail("grads = %lld is not a mask of the MHSTAGE_GRAD_* bits", grads);
+    if (grad_out_layout != 0 && grad_out_layout != 1) return err.fail("grad_out_layout = %lld must be 0 (NCHW) or 1 (channels-last)", grad_out_layout);
     if (check_shape(shape, (grads & MHSTAGE_GRAD_SKIP) != 0) != MHSTAGE_OK) return MHSTAGE_ERR_ARGUMENT;
     const mhstage_shape &s = *shape;
     if ((grads & MHSTAGE_GRAD_SKIP) && !skip_index && s.F != s.N)
-        return fail("without skip_index F = %lld must equal N = %lld", s.F, s.N);
+        return err.fail("without skip_index F = %lld must equal N = %lld", s.F, s.N);
     if (grads == 0 || (s.N == 0 && !(grads & MHSTAGE_GRAD_SKIP))) return MHSTAGE_OK;
-    if (!grad_out && s.N > 0) return fail("null pointer: grad_out is required");
+    if (!grad_out && s.N > 0) return err.fail("null pointer: grad_out is required");
     if (grads & (all & ~MHSTAGE_GRAD_SKIP)) {
         if (!x || !weight || !bias || !mean || !rstd || !workspace || !dy)
-            return fail("null pointer: x, weight, bias, mean, rstd, workspace and dy are required");
+            return err.fail("null pointer: x, weight, bias, mean, rstd, workspace and dy are required");
         if (((grads & MHSTAGE_GRAD_X) && !grad_x) || ((grads & MHSTAGE_GRAD_WEIGHT) && !grad_weight) ||
             ((grads & MHSTAGE_GRAD_BIAS) && !grad_bias))
-            return fail("null pointer: a gradient named in grads = %lld has no buffer", grads);
-        if (grad_x && dy == grad_x && elem_size(dtype) == 2) return fail("grad_x may alias dy for MHSTAGE_F32 and MHSTAGE_F64 only");
+            return err.fail("null pointer: a gradient named in grads = %lld has no buffer", grads);
+        if (grad_x && dy == grad_x && elem_size(dtype) == 2) return err.fail("grad_x may alias dy for MHSTAGE_F32 and MHSTAGE_F64 only");
     }
-    if ((grads & MHSTAGE_GRAD_SKIP) && !grad_skip) return fail("null pointer: a gradient named in grads = %lld has no buffer", grads);
+    if ((grads & MHSTAGE_GRAD_SKIP) && !grad_skip) return err.fail("null pointer: a gradient named in grads = %lld has no buffer", grads);
     if (s.N == 0) grads &= MHSTAGE_GRAD_SKIP;      // no image: grad_skip is all zeros, the parameters' sums too (the caller's)
     hipStream_t st = (hipStream_t)stream;
-#define MHSTAGE_BWD(T)                                                                                                   \
-    launch_backward<T>(grads, param_wide, out_wide, x, weight, bias, mean, rstd, skip_index, index_is64, grad_out,       \
-                       grad_out_layout, s, workspace, dy, grad_x, grad_weight, grad_bias, grad_skip, st)
-    switch (dtype) {
-    case MHSTAGE_F32: return MHSTAGE_BWD(float);
-    case MHSTAGE_F64: return MHSTAGE_BWD(double);
-    case MHSTAGE_BF16: return MHSTAGE_BWD(__hip_bfloat16);
-    default: return MHSTAGE_BWD(__half);
-    }
-#undef MHSTAGE_BWD
+    return dispatch(dtype, [&](auto t) {
+        return launch_backward<type_of<decltype(t)>>(grads, param_wide, out_wide, x, weight, bias, mean, rstd, skip_index,
+                                                     index_is64, grad_out, grad_out_layout, s, workspace, dy, grad_x, grad_weight,
+                                                     grad_bias, grad_skip, st);
+    });
 }
 
 }  // extern "C"

@@ -10,14 +10,10 @@ There is no CPU path and no eager fallback: CPU tensors raise, a failing kernel 
 import torch
 
 from .. import _attmap, _native
+from ._common import _check_device, _require, _workspace
 
 NEED_Q, NEED_K = _attmap.GRAD_Q, _attmap.GRAD_K
 NEED_ALL = NEED_Q | NEED_K
-
-
-def _require(cond, msg):
-    if not cond:
-        raise RuntimeError(msg)
 
 
 def grads_mask(need_q, need_k):
@@ -49,22 +45,9 @@ def check_shapes(q, k, mask, num_heads, out_dtype=None):
     return B, Q, num_heads, D // num_heads, H, W, _attmap.out_dtype(q.dtype, out_dtype)
 
 
-def _check_device(named):
-    for name, t in named:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("Not implemented on the CPU (%s is not a GPU tensor)" % name)
-    dev = named[0][1].device
-    for name, t in named:
-        _require(t is None or t.device == dev, "attention_maps: %s is on another device than q" % name)
-
-
-def _workspace(code, shape, device):
-    return torch.empty(_attmap.workspace_bytes(code, shape), dtype=torch.uint8, device=device)
-
-
 def _forward(q, k, mask, num_heads, scale, out_dtype=None):
     """out [B, Q, n, H, W]: two kernel passes, no logits tensor."""
-    _check_device([("q", q), ("k", k), ("mask", mask)])
+    _check_device("attention_maps", [("q", q), ("k", k), ("mask", mask)])
     B, Q, n, c, H, W, odt = check_shapes(q, k, mask, num_heads, out_dtype)
     out = torch.empty((B, Q, n, H, W), dtype=odt, device=q.device)
     if B == 0 or Q == 0:
@@ -74,7 +57,7 @@ def _forward(q, k, mask, num_heads, scale, out_dtype=None):
     if mask is not None:
         mask = mask.contiguous()
         mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
-    _attmap.forward(code, out_code, q.contiguous(), k.contiguous(), mask, shape, scale, _workspace(code, shape, q.device), out)
+    _attmap.forward(code, out_code, q.contiguous(), k.contiguous(), mask, shape, scale, _workspace(_attmap, code, shape, q.device), out)
     return out
 
 
@@ -82,7 +65,7 @@ def _backward(grad_out, q, k, out, num_heads, scale, grads=NEED_ALL):
     """(grad_q, grad_k) for the gradients in ``grads``; the other is neither allocated nor computed and comes back None.
     Both are contractions of the same ``dl``, so each alone has the bits it has in a full backward."""
     _require(0 <= grads <= NEED_ALL, "attention_maps: grads must be a mask of NEED_Q and NEED_K")
-    _check_device([("q", q), ("k", k), ("out", out), ("grad_out", grad_out)])
+    _check_device("attention_maps", [("q", q), ("k", k), ("out", out), ("grad_out", grad_out)])
     B, Q, n, c, H, W, _ = check_shapes(q, k, None, num_heads)
     odt = _attmap.out_dtype(q.dtype, out.dtype)
     _require(tuple(out.shape) == (B, Q, n, H, W), "attention_maps: out must be [B, Q, n, H, W]")
@@ -99,7 +82,7 @@ def _backward(grad_out, q, k, out, num_heads, scale, grads=NEED_ALL):
     code, out_code = _native.dtype_code(q.dtype), _native.dtype_code(odt)
     dl = torch.empty((B, n, Q, P), dtype=q.dtype, device=q.device)
     _attmap.backward(grads, code, out_code, out.contiguous(), grad_out.contiguous(), shape, scale,
-                     _workspace(code, shape, q.device), dl)
+                     _workspace(_attmap, code, shape, q.device), dl)
     if grads & NEED_Q:      # [B, n, Q, P] x [B, n, P, c] -> [B, n, Q, c]
         gq = torch.matmul(dl, k.contiguous().view(B, n, c, P).transpose(2, 3))
         grad_q = gq.permute(0, 2, 1, 3).reshape(B, Q, n * c)

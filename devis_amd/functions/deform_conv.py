@@ -15,6 +15,7 @@ import warnings
 import torch
 
 from .. import _mdcn
+from ._common import _check_device, _require
 
 # Bound on ONE column buffer ([chunk * Ho * Wo, Kh * Kw * C] in the input's dtype).  A call is cut into chunks of whole images
 # so that the buffer stays under it (one image is the smallest chunk, whatever its size); the forward holds one such
@@ -79,11 +80,6 @@ def input_mode(grads):
     return need, fixed
 
 
-def _require(cond, msg):
-    if not cond:
-        raise RuntimeError(msg)
-
-
 def _pair(v, name):
     if isinstance(v, (tuple, list)):
         _require(len(v) == 2, "%s must be an int or a pair" % name)
@@ -139,15 +135,6 @@ def check_shapes(input, offset, weight, bias, stride, padding, dilation, mask):
     return Ho, Wo, G
 
 
-def _check_device(named):
-    for name, t in named:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("Not implemented on the CPU (%s is not a GPU tensor)" % name)
-    dev = named[0][1].device
-    for name, t in named:
-        _require(t is None or t.device == dev, "deform_conv2d: %s is on another device than input" % name)
-
-
 def alert_nondeterministic(grads):
     """grad_input is a sum of float atomics, so it depends on the order the adds arrive in: under
     ``torch.use_deterministic_algorithms(True)`` asking for it raises (warns with ``warn_only=True``), as PyTorch's own
@@ -172,7 +159,7 @@ def chunk_images(code, shape, N, workspace_bytes=None):
 
 
 def _prepare(input, offset, weight, bias, stride, padding, dilation, mask):
-    _check_device([("input", input), ("offset", offset), ("weight", weight), ("bias", bias), ("mask", mask)])
+    _check_device("deform_conv2d", [("input", input), ("offset", offset), ("weight", weight), ("bias", bias), ("mask", mask)])
     Ho, Wo, G = check_shapes(input, offset, weight, bias, stride, padding, dilation, mask)
     N, C, H, W = input.shape
     Co, _, Kh, Kw = weight.shape
@@ -216,7 +203,7 @@ def _backward(grad_out, input, offset, weight, mask, stride, padding, dilation, 
     grads, fixed = input_mode(grads)
     if not fixed:
         alert_nondeterministic(grads)
-    _check_device([("input", input), ("grad_out", grad_out)])
+    _check_device("deform_conv2d", [("input", input), ("grad_out", grad_out)])
     shape, code, x, offset, mask, w2 = _prepare(input, offset, weight, None, stride, padding, dilation, mask)
     N, C, H, W = input.shape
     Co, _, Kh, Kw = weight.shape

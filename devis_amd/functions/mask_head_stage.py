@@ -11,15 +11,11 @@ There is no CPU path and no eager fallback: CPU tensors raise, a failing kernel 
 import torch
 
 from .. import _mhstage, _native
+from ._common import _check_device, _require, _workspace
 
 NEED_X, NEED_WEIGHT, NEED_BIAS, NEED_SKIP = _mhstage.GRAD_X, _mhstage.GRAD_WEIGHT, _mhstage.GRAD_BIAS, _mhstage.GRAD_SKIP
 NEED_EXTRA = 16         # host only: a slice of grad_out
 NEED_ALL = NEED_X | NEED_WEIGHT | NEED_BIAS | NEED_SKIP | NEED_EXTRA
-
-
-def _require(cond, msg):
-    if not cond:
-        raise RuntimeError(msg)
 
 
 def grads_mask(need_x, need_weight, need_bias, need_skip, need_extra):
@@ -69,26 +65,13 @@ def check_shapes(x, num_groups, weight, bias, skip=None, skip_index=None, extra=
     return N, F, C, num_groups, E, h, w, H, W, _mhstage.wide_dtype(x.dtype, out_dtype, "out")
 
 
-def _check_device(named):
-    for name, t in named:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("Not implemented on the CPU (%s is not a GPU tensor)" % name)
-    dev = named[0][1].device
-    for name, t in named:
-        _require(t is None or t.device == dev, "mask_head_stage: %s is on another device than x" % name)
-
-
-def _workspace(code, shape, device):
-    return torch.empty(_mhstage.workspace_bytes(code, shape), dtype=torch.uint8, device=device)
-
-
 def _dense(t):
     return None if t is None else t.contiguous()
 
 
 def _forward(x, num_groups, weight, bias, eps, skip=None, skip_index=None, extra=None, out_dtype=None):
     """(out, mean, rstd): out [N, C+E, H, W] in channels-last memory, mean and rstd [N, G] in the arithmetic type."""
-    _check_device([("x", x), ("weight", weight), ("bias", bias), ("skip", skip), ("skip_index", skip_index), ("extra", extra)])
+    _check_device("mask_head_stage", [("x", x), ("weight", weight), ("bias", bias), ("skip", skip), ("skip_index", skip_index), ("extra", extra)])
     N, F, C, G, E, h, w, H, W, odt = check_shapes(x, num_groups, weight, bias, skip, skip_index, extra, out_dtype)
     acc = _native.acc_dtype(x.dtype)
     out = torch.empty((N, C + E, H, W), dtype=odt, device=x.device, memory_format=torch.channels_last)
@@ -99,7 +82,7 @@ def _forward(x, num_groups, weight, bias, eps, skip=None, skip_index=None, extra
     code = _native.dtype_code(x.dtype)
     _mhstage.forward(code, weight.dtype != x.dtype, extra is not None and extra.dtype != x.dtype, odt != x.dtype,
                      x.contiguous(), weight.contiguous(), bias.contiguous(), eps, _dense(skip), _dense(skip_index),
-                     _dense(extra), shape, _workspace(code, shape, x.device), mean, rstd, out)
+                     _dense(extra), shape, _workspace(_mhstage, code, shape, x.device), mean, rstd, out)
     return out, mean, rstd
 
 
@@ -108,7 +91,7 @@ def _backward(grad_out, x, weight, bias, mean, rstd, skip_index, num_groups, num
     computed and come back None.  ``num_skip`` is F (0 without a skip).  grad_extra is the slice ``grad_out[:, C:]`` and is
     taken by the caller.  Each gradient alone has the bits it has in a full backward."""
     _require(0 <= grads <= NEED_ALL, "mask_head_stage: grads must be a mask of the NEED_* bits")
-    _check_device([("x", x), ("weight", weight), ("bias", bias), ("mean", mean), ("rstd", rstd), ("skip_index", skip_index),
+    _check_device("mask_head_stage", [("x", x), ("weight", weight), ("bias", bias), ("mean", mean), ("rstd", rstd), ("skip_index", skip_index),
                    ("grad_out", grad_out)])
     _require(x.dim() == 4 and grad_out.dim() == 4 and grad_out.shape[0] == x.shape[0] and grad_out.shape[1] >= x.shape[1],
              "mask_head_stage: grad_out must be [N, C+E, H, W]")
@@ -146,7 +129,7 @@ def _backward(grad_out, x, weight, bias, mean, rstd, skip_index, num_groups, num
     code = _native.dtype_code(x.dtype)
     _mhstage.backward(grads, code, weight.dtype != x.dtype, odt != x.dtype, x.contiguous(), weight.contiguous(),
                       bias.contiguous(), mean, rstd, _dense(skip_index), grad_out, channels_last, shape,
-                      _workspace(code, shape, dev), dy, grad_x, grad_w, grad_b, grad_skip)
+                      _workspace(_mhstage, code, shape, dev), dy, grad_x, grad_w, grad_b, grad_skip)
     return grad_x, grad_w, grad_b, grad_skip
 
 

@@ -13,11 +13,7 @@ import math
 import torch
 
 from .. import _maskloss, _native
-
-
-def _require(cond, msg):
-    if not cond:
-        raise RuntimeError(msg)
+from ._common import _check_device, _require
 
 
 def check_gamma(gamma):
@@ -43,20 +39,11 @@ def check_shapes(src, target):
     return N, h, w, H, W, kind
 
 
-def _check_device(named):
-    for name, t in named:
-        if not t.is_cuda:
-            raise RuntimeError("Not implemented on the CPU (%s is not a GPU tensor)" % name)
-    dev = named[0][1].device
-    for name, t in named:
-        _require(t.device == dev, "mask_loss_terms: %s is on another device than src_masks" % name)
-
-
 def _forward(src, target, alpha, gamma):
     """(focal [N], dice [N], sums [N, 3]) in the arithmetic type: float32, float64 for float64 logits."""
     N, h, w, H, W, kind = check_shapes(src, target)
     gamma = check_gamma(gamma)
-    _check_device([("src_masks", src), ("target_masks", target)])
+    _check_device("mask_loss_terms", [("src_masks", src), ("target_masks", target)])
     acc = _native.acc_dtype(src.dtype)
     focal, dice = torch.empty((N,), dtype=acc, device=src.device), torch.empty((N,), dtype=acc, device=src.device)
     sums = torch.empty((N, 3), dtype=acc, device=src.device)
@@ -74,7 +61,7 @@ def _backward(grad_focal, grad_dice, src, target, sums, alpha, gamma):
     """grad_src [N, h, w] in src's dtype."""
     N, h, w, H, W, kind = check_shapes(src, target)
     gamma = check_gamma(gamma)
-    _check_device([("src_masks", src), ("target_masks", target), ("sums", sums), ("grad_focal", grad_focal),
+    _check_device("mask_loss_terms", [("src_masks", src), ("target_masks", target), ("sums", sums), ("grad_focal", grad_focal),
                    ("grad_dice", grad_dice)])
     acc = _native.acc_dtype(src.dtype)
     _require(tuple(sums.shape) == (N, 3) and sums.dtype == acc, "mask_loss_terms: sums must be [N, 3] in the arithmetic type")

@@ -11,11 +11,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _native
-
-
-def _require(cond, msg):
-    if not cond:
-        raise RuntimeError(msg)
+from ._common import _require
 
 
 def _check_inputs(named):

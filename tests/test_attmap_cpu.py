@@ -127,6 +127,49 @@ def test_attmap_argument_errors_without_gpu():
         _attmap.workspace_bytes(0, _shape(W=0))
 
 
+def test_each_operator_keeps_an_error_message_of_its_own():
+    """The four mask-path operators share the code of their error state, not the state: a failure of one leaves the
+    others' <operator>_last_error() alone.  Run in a fresh thread, whose messages all start empty."""
+    import threading
+    from devis_amd import _attmap, _maskloss, _mdcn, _mhstage
+    lib = _attmap.load()
+    for binding in (_mdcn, _mhstage, _maskloss):
+        assert binding.load() is lib
+    last = {name: getattr(lib, name + "_last_error") for name in ("mdcn", "attmap", "mhstage", "maskloss")}
+    seen = []
+
+    def messages():
+        return {name: f().decode() for name, f in last.items()}
+
+    def run():
+        seen.append(messages())
+        try:
+            _attmap.workspace_bytes(0, _shape(W=0))
+        except RuntimeError as e:
+            seen.append((str(e), messages()))
+        assert lib.attmap_workspace_bytes(0, ctypes.byref(_shape())) > 0       # a good call clears the operator's message
+        seen.append(messages())
+        bad = _mdcn.Shape(N=1, C=8, H=6, W=7, Ho=6, Wo=7, Kh=3, Kw=3, stride_h=1, stride_w=1, pad_h=1, pad_w=1, dil_h=1,
+                          dil_w=1, G=3)
+        try:
+            _mdcn.workspace_bytes(0, bad, 1)
+        except RuntimeError as e:
+            seen.append((str(e), messages()))
+
+    t = threading.Thread(target=run)
+    t.start()
+    t.join()
+    assert len(seen) == 4, seen
+    empty = dict.fromkeys(last, "")
+    assert seen[0] == empty and seen[2] == empty
+    text, after = seen[1]
+    assert "positive" in after["attmap"] and text.endswith(after["attmap"]) and "attmap_workspace_bytes failed" in text
+    assert after == dict(empty, attmap=after["attmap"])
+    text, after = seen[3]
+    assert "offset groups" in after["mdcn"] and text.endswith(after["mdcn"]) and "mdcn_workspace_bytes failed" in text
+    assert after == dict(empty, mdcn=after["mdcn"])
+
+
 # ---- host ------------------------------------------------------------------------------------------------------------
 
 def test_operator_raises_on_cpu_tensors_and_on_bad_shapes_before_any_launch():
