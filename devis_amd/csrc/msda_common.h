@@ -1,5 +1,5 @@
 // msda_common.h -- shared by the translation units of libmsda_hip.so (devis_amd/csrc/*.hip, one per kernel family):
-// storage-type helpers, the kernel parameter block, tap arithmetic, launch geometry constants, and the host-side
+// storage-type helpers, tap arithmetic, and the host-side
 // services (error / route strings, test knobs, per-device caches) and per-family launchers the dispatcher in
 // msda_api.hip calls.  gfx950 only; no CUDA compatibility layer.
 //
@@ -22,6 +22,9 @@
 
 #include "msda.h"
 
+#define MSDA_HD __host__ __device__
+#include "msda_params.h"
+
 // No implicit FMA contraction anywhere in the library: HIP's __fmul_rn / __fsub_rn are plain `*` / `-` unless
 // OCML_BASIC_ROUNDED_OPERATIONS is defined, and hipcc contracts by default, so `x * W - 0.5` could become one
 // FMA in some inlining contexts and not in others -- forward, gather pass and scatter would then disagree with
@@ -31,9 +34,6 @@
 
 namespace msda {
 
-
-constexpr int kWave = 64;   // gfx950 wavefront
-constexpr int kPch = 16;    // sampling points per LDS chunk (= L*P of the DeVIS configs)
 
 // ------------------------------------------------------------------------------------------------
 // storage-type helpers: everything is computed in fp32 (fp64 for double)
@@ -193,7 +193,6 @@ __device__ __forceinline__ void gather_load(const T *base, int elem_off, unsigne
 // read as zeros without touching memory -- not as pixel 0 times weight 0, which would turn a non-finite value at
 // an unrelated pixel into NaN (the reference does not read such corners at all, cuh:56-80).  The backward kernels
 // mask the dots of such corners by their validity bits instead and keep the plain loads.
-constexpr unsigned kOobBytes = 0xF0000000u;
 template <typename T> constexpr int oob_elems() { return (int)(kOobBytes / sizeof(T)); }
 template <typename S, typename T, int N>
 __device__ __forceinline__ void gather_load_z(__amdgpu_buffer_rsrc_t rsrc, int elem_off, unsigned lane_bytes, float (&v)[N])
@@ -220,45 +219,6 @@ __device__ __forceinline__ unsigned lds_addr(const void *q)
 __device__ __forceinline__ void atomic_accumulate(float *p, float v) { unsafeAtomicAdd(p, v); }
 __device__ __forceinline__ void atomic_accumulate(double *p, double v) { unsafeAtomicAdd(p, v); }
 
-// ------------------------------------------------------------------------------------------------
-// kernel parameters: one struct serves the plain op (frames = 1, window = 0, LB = 0) and the fused
-// temporal op (array A = current-frame points, array B = temporal points)
-// ------------------------------------------------------------------------------------------------
-struct Params {
-    const void *value;          // [groups, S, M, D]; groups = clips * frames
-    const int64_t *shapes;      // [L, 2] (H, W)
-    const int64_t *lsi;         // [L]
-    const int32_t *ftab;        // [frames, window] or null
-    const void *locA, *awA;     // [groups, Lq, M, LA, PA, 2], [groups, Lq, M, LA, PA]
-    const void *locB, *awB;     // [groups, Lq, M, LB, PB, 2], ...      (LB = window * L)
-    void *out;                  // fwd: [groups, Lq, M*D]
-    const void *grad_out;       // bwd
-    void *grad_value;           // bwd: acc type, pre-zeroed
-    void *glocA, *gawA, *glocB, *gawB;
-    unsigned *workspace;        // bwd: 8 work-ticket counters of the scatter pass (zeroed by the caller) or null
-    int *bbox;                  // bwd: [groups, M, LA+LB, Lq, 2] (min, max) top tap row per (row, virtual level) -- or, with
-                                // cull_points, the top tap row of each of its <= 4 points as int16 (same 8 bytes) --
-                                // written by the gather pass, read by the scatter pass to cull rows; or null
-    int groups, frames, window;
-    int S, M, D, L, Lq;
-    int LA, PA, LB, PB;
-    int64_t v_clip, v_head;     // element strides of `value`: between clips (= frames * S pixels), between heads
-    int v_pix;                  // ... and between consecutive pixels (standard [S, M, D]: frames*S*M*D, D, M*D)
-    int *bsum;                  // bwd: [groups, M, LA+LB, ceil(Lq/64), 2] (min, max) top tap row over blocks of 64 queries
-                                // (built from the per-point records; lets long candidate ranges skip dead blocks) or null
-    const int64_t *shapes_host; // HOST copy of `shapes` or null: kernel selection only (never dereferenced on the device)
-    int cull_points;            // bbox entries are 4 x int16 top tap rows, one per POINT (PA, PB <= 4), not (min, max)
-    int wide_stores;            // bwd: the four gradient arrays are 16-byte aligned (resident-slab gather pass: whole-row stores)
-    int wide_loads;             // loc / attn arrays are 16-byte aligned (resident-slab kernels: whole-row loads)
-    int dbg;                    // measurement hooks (MSDA_DBG env), 0 in production
-    int gv_storage;             // bwd: grad_value is in the STORAGE type (16-bit), not the arithmetic type (owner-computes scatter only)
-    int own_levels;             // bwd: the owner-computes scatter handles levels [0, own_levels); the trailing (coarse) levels are
-                                // the matrix-pipe scatter's (msda_mfma.hip).  = L when that kernel does not run
-    unsigned rec_mask;          // bwd: bit l = the gather pass leaves culling records for level l and the owner-computes scatter reads
-                                // them; clear for the matrix-pipe levels and for levels that are ONE band (every group a candidate)
-};
-
-struct Level { int H, W, start, pad; };   // start = first pixel of the level inside the CLIP slab
 
 // virtual level j of the wave's (clip, frame t):  j < LA -> level j of frame t (plain op: of the only
 // map); j >= LA -> temporal slot w = (j-LA)/L, level (j-LA)%L of frame ftab[t, w].
@@ -325,16 +285,6 @@ __device__ __forceinline__ Taps make_taps(float x, float y, const Level lv, int 
 // small shared helpers
 // ------------------------------------------------------------------------------------------------
 typedef unsigned long long u64;
-constexpr int kNoRow16 = -32768;            // culling record of a point that touches no row (see the gather passes)
-constexpr int kSlabMaxLevels = 32;          // levels the resident-slab kernels keep tables for
-constexpr int kScatterMaxLevels = 32;
-constexpr int kOwnMaxSorted = 256;            // (level, band) pairs the owner-computes scatter sorts by position (more: level order)
-constexpr int kScatterMaxSources = 64;      // 1 + frames * window must fit
-constexpr int kCullBlock = 64;              // queries per block summary of the culling records
-constexpr int kLiveWords = 64;              // up to 2048 cull batches per item take the block-summary pre-pass
-// gradient groups of a backward call (include/msda.h, msda_backward_grads)
-constexpr int kGradValue = MSDA_GRAD_VALUE, kGradSampling = MSDA_GRAD_SAMPLING, kGradAll = kGradValue | kGradSampling;
-constexpr int kGradDet = MSDA_GRAD_DETERMINISTIC;
 
 // levels [result, L) form the slab: the last levels whose pixels are one contiguous tail of the map and
 // whose [pixels, D] slab fits `cap` elements
@@ -379,73 +329,6 @@ __device__ __forceinline__ void load_xy(const f16_t *loc2, float &x, float &y)
     x = v.x; y = v.y;
 }
 
-// ------------------------------------------------------------------------------------------------
-// launch geometry shared by kernels and dispatcher
-// ------------------------------------------------------------------------------------------------
-constexpr int kRowSlots = kPch + 1;         // tile kernels: 16-byte record slots per row (odd: LDS banks)
-constexpr int kTileMaxWaves = 8;            // forward tile kernel: waves of one workgroup that share a tile (small calls)
-// owner-computes scatter
-constexpr int kOwnThreads = 1024;                   // (512: two workgroups per CU out of phase with each other)
-constexpr int kOwnQuads = kOwnThreads / 4;
-constexpr int kOwnSlots = 4;                        // pixels per owner quad
-constexpr int kOwnPix = kOwnQuads * kOwnSlots;      // pixels per band
-// resident-slab kernels
-constexpr int kRsThreads = 1024, kRsWaves = kRsThreads / kWave;     // (512: 8 waves with a 256-VGPR budget each -- measured slower)
-constexpr int kRsRows = kWave / 4;       // rows per wave tile: one quad per row
-constexpr int kRsSlack = 1024;          // bytes: the last LDS-DMA piece may overrun the slab's pixels
-constexpr int kRsLdsBytes = 160 * 1024;
-constexpr int kRsMaxFrames = 32;        // frames x frames slot masks live in LDS
-constexpr int kRsRowB = 128;            // bytes of one pixel of one head in a 4-byte type (D = 32); 64 in a 2-byte type
-constexpr int kRsTailBytes = kRsRowB + kRsMaxFrames * kRsMaxFrames * 4 + 4 * kSlabMaxLevels * 4 + 16;   // after the slab
-constexpr int kRsSlabBytes = ((kRsLdsBytes - 256 - kRsTailBytes) / 128) * 128;
-
-// ---- resident-window kernels (msda_win.hip): encoder-shaped calls, where query i IS pixel i of the pyramid and samples round
-// its own position.  A workgroup owns the queries of one spatial TILE (By x Bx level-0 pixels and the pixels of the other
-// levels whose centres fall into it) and stages, per source frame, a WINDOW of every level -- the tile's footprint on that
-// level plus `halo` pixels on every side -- in LDS; taps outside the window are read from memory (any input is computed
-// exactly; only speed depends on locality).  When all windows do not fit at a useful halo the levels are staged in two
-// phases per source frame: levels < split, then levels >= split (split = 0: one phase).
-constexpr int kWinMaxLevels = 8;
-struct WinPlan {
-    int By, Bx, tiles_y, tiles_x;       // tile size in level-0 pixels; tiles of one map
-    int split;                          // first level of the second staging phase (0 = one phase)
-    int halo[2];                        // pixels round the footprint, per phase
-    int wbase[kWinMaxLevels];           // first LDS pixel of level l's window (inside its phase's layout)
-    int tpg;                            // wave tiles (16 rows) per query frame: ceil(most queries of a tile / 16)
-    int nt;                             // wave tiles per wave: ceil(frames * tpg / 16 waves) <= 3
-};
-
-// One axis of a tile's geometry on a level with n_l pixels (n_0 on level 0): the level's own pixels the tile OWNS
-// [q0, q1) -- pixel y belongs to the tile its centre falls into, i.e. floor((2y + 1) n_0 / (2 n_l) / B) -- and the window
-// [w0, w1) that holds every tap of a point within `halo` pixels of the tile's extent (floor(y n_l - 0.5) and the row below).
-// Host (planning: maxima over the tiles) and device (the tile's own tables) evaluate the same integers.
-__host__ __device__ inline int win_fdiv(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-__host__ __device__ inline void win_axis(int n_l, int n_0, int t, int B, int halo, int &q0, int &q1, int &w0, int &w1)
-{
-    const int a = 2 * n_l * t * B - n_0, b = 2 * n_l * (t + 1) * B - n_0, d = 2 * n_0;
-    auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-    q0 = clampi(-win_fdiv(-a, d), 0, n_l);          // ceil
-    q1 = clampi(-win_fdiv(-b, d), 0, n_l);
-    w0 = clampi(win_fdiv(a, d) - halo, 0, n_l);
-    w1 = clampi(win_fdiv(b, d) + 2 + halo, 0, n_l);
-}
-
-constexpr int kWinTailBytes = 128 + kRsMaxFrames * kRsMaxFrames * 4 + 14 * kWinMaxLevels * 4 + 64;    // zero row, slot masks, level tables
-constexpr int kWinSlabBytes = ((160 * 1024 - 256 - kWinTailBytes) / 128) * 128;
-
-struct PrepParams {
-    const void *off_c, *off_t;        // [rows, M, L, Pc, 2], [rows, M, W*L, Pt, 2]   raw sampling offsets
-    const void *logit_c, *logit_t;    // [rows, M, L*Pc], [rows, M, W*L*Pt]           raw attention logits
-    const void *ref_c, *ref_t;        // [rows, L, d], [rows, W*L, d]                 reference points (d = 2 | 4)
-    const int64_t *shapes;            // [L, 2] (H, W)
-    void *loc_c, *loc_t, *aw_c, *aw_t;            // forward outputs (backward: aw_* are inputs)
-    const void *gloc_c, *gloc_t, *gaw_c, *gaw_t;  // backward inputs
-    void *goff_c, *goff_t, *glogit_c, *glogit_t;  // backward outputs
-    int64_t rows;
-    int64_t ld;                       // row stride of the Linear-side tensors (offsets / logits forward, their grads
-                                      // backward) when they are column slices of one fused matrix; 0 = each dense
-    int M, L, W, Pc, Pt, d;
-};
 
 // ------------------------------------------------------------------------------------------------
 // host side (defined in msda_api.hip)
@@ -453,7 +336,6 @@ struct PrepParams {
 int fail(int code, const char *fmt, const char *detail = "");
 int check_launch(const char *what);                 // appends `what` to the route string, reports launch errors
 int device_cus();
-constexpr int kMaxDevices = 64;
 // Dynamic LDS above 64 KiB must be opted into per kernel function AND per device; `granted` is the caller's
 // per-instantiation table of what each device has been given so far.
 struct LdsGrant { size_t bytes[kMaxDevices]; };
@@ -499,7 +381,6 @@ int launch_scatter_lds(int dtype, int G, const Params &p, unsigned grid, int cap
 int launch_scatter_grp(int dtype, bool storage_typed_grad_value, const Params &p, unsigned grid, int dbg, bool image_order,
                        hipStream_t stream);
 // msda_mfma.hip: grad_value of the trailing levels [l0, L) (at most 2, `tiles` = mfma_scatter_tiles(their pixels)) on the matrix pipe
-int mfma_scatter_tiles(long long pixels);
 int launch_scatter_mfma(int dtype, bool storage_typed_grad_value, const Params &p, int l0, int tiles, hipStream_t stream);
 // msda_generic.hip: any-shape kernels, the modules' fused pre-op pass, the padding-mask pass
 int launch_generic(int dtype, const Params &p, bool bwd, hipStream_t stream, int grads = kGradAll);
@@ -509,8 +390,6 @@ int launch_mask_rows(int bytes_per_thread, char *rows, const uint8_t *mask, long
 // msda_det.hip: grad_value in int64 fixed point (MSDA_GRAD_DETERMINISTIC); `workspace` of det_workspace_bytes(), 256-B aligned.
 // prepare (zero-fill, maxima) -> one scatter route -> convert.
 struct DetArgs;
-long long det_maxima_bytes(long long clips, int num_heads);
-long long det_workspace_bytes(long long clips, int frames, int spatial_size, int num_heads, int channels);
 int launch_det_prepare(int dtype, const Params &p, void *workspace, DetArgs &d, hipStream_t stream);
 int launch_det_scatter_any(int dtype, const Params &p, const DetArgs &d, hipStream_t stream);
 int launch_det_convert(int dtype, const Params &p, const DetArgs &d, hipStream_t stream);

@@ -23,6 +23,7 @@
 // accumulators, then [ceil(elems / 8)] u32 class words (4 bits per element); zeroed on the stream first.
 #include "msda_common.h"
 #include "msda_det.h"
+#include "msda_plan.h"
 #include <algorithm>
 
 namespace msda {
@@ -170,10 +171,10 @@ int det_prepare(const Params &p, char *ws, DetArgs &d, hipStream_t stream)
     const int64_t elems = (int64_t)p.groups * p.S * p.M * p.D;
     unsigned long long *maxima = reinterpret_cast<unsigned long long *>(ws);
     d.maxima = maxima;
-    d.acc = reinterpret_cast<long long *>(ws + det_maxima_bytes(clips, p.M));
+    d.acc = reinterpret_cast<long long *>(ws + plan::det_maxima_bytes(clips, p.M));
     d.cls = reinterpret_cast<unsigned *>(d.acc + elems);
     if (items > 0x7fffffffLL) return fail(MSDA_ERR_ARG, "msda: problem too large for one launch%s");
-    if (hipMemsetAsync(ws, 0, (size_t)det_workspace_bytes(clips, p.frames, p.S, p.M, p.D), stream) != hipSuccess)
+    if (hipMemsetAsync(ws, 0, (size_t)plan::det_workspace_bytes(clips, p.frames, p.S, p.M, p.D), stream) != hipSuccess)
         return fail(MSDA_ERR_HIP, "msda backward: hipMemsetAsync(deterministic workspace) failed%s");
     // (clip, head) workgroups, split so that a batch covers the chip about twice; a clip's maxima do not depend on the split
     const int64_t per_item = (int64_t)p.frames * p.Lq * std::max<int64_t>((int64_t)p.LA * p.PA + (int64_t)p.LB * p.PB, p.D);
@@ -206,17 +207,6 @@ int det_convert(const Params &p, const DetArgs &d, hipStream_t stream)
 }
 
 }  // namespace
-
-long long det_maxima_bytes(long long clips, int num_heads)
-{
-    return (clips * num_heads * 16 + 255) / 256 * 256;
-}
-
-long long det_workspace_bytes(long long clips, int frames, int spatial_size, int num_heads, int channels)
-{
-    const long long elems = clips * frames * spatial_size * (long long)num_heads * channels;
-    return det_maxima_bytes(clips, num_heads) + elems * 8 + (elems + 7) / 8 * 4;
-}
 
 int launch_det_prepare(int dtype, const Params &p, void *workspace, DetArgs &d, hipStream_t stream)
 {

@@ -63,7 +63,6 @@ __device__ __forceinline__ float g_value(const float *p) { return *p; }
 __device__ __forceinline__ unsigned short g_bits(const bf16_t *p) { return *reinterpret_cast<const unsigned short *>(p); }
 __device__ __forceinline__ unsigned short g_bits(const f16_t *p) { return *reinterpret_cast<const unsigned short *>(p); }
 
-constexpr int mfma_rows(int MT) { return MT * 32 - 16; }                 // pixel rows per k-chunk of a tile: pixels + 1 trash row <= this
 constexpr int mfma_tile_bytes(int MT) { return 2 * mfma_rows(MT) * 16; }  // one A tile (hi or lo)
 constexpr int mfma_phase_tiles(int MT) { return MT < 4 ? MT : 4; }      // tiles per reduction phase: NW x tiles x 4 KiB of LDS
 constexpr int mfma_lds_bytes(int MT, int NW)
@@ -407,14 +406,6 @@ int scatter_mfma_sizes(const Params &p, int l0, int tiles, unsigned grid, hipStr
 }
 
 }  // namespace
-
-// Pixel tiles (of 32) the matrix-pipe scatter needs for `pixels` coarse pixels, or 0 when they do not fit its largest kernel.
-int mfma_scatter_tiles(long long pixels)
-{
-    for (int mt : {2, 4, 6, 8, 10})
-        if (pixels + 1 <= mfma_rows(mt)) return mt;
-    return 0;
-}
 
 int launch_scatter_mfma(int dtype, bool storage_typed, const Params &p, int l0, int tiles, hipStream_t stream)
 {

@@ -1274,7 +1274,7 @@ int launch_scatter_lds_det(int dtype, int G, const Params &p, unsigned grid, int
     });
 }
 
-// `image_order`: the items in image order (the dispatcher's rule, msda_api.hip owner_image_order), else heaviest first
+// `image_order`: the items in image order (the dispatcher's rule, msda_plan.hip owner_image_order), else heaviest first
 int launch_scatter_grp(int dtype, bool storage_typed, const Params &p, unsigned grid, int dbg, bool image_order, hipStream_t stream)
 {
     return dispatch_types(dtype, [&](auto t, auto tl) {

@@ -141,7 +141,7 @@ __device__ __forceinline__ void build_chunk(const Params &p, const ChunkRef<TL> 
 // single-wave workgroups on 1024 SIMDs, each walking its rows' 96 points as ~24 dependent batches of gathers: latency-bound.  With
 // MW a workgroup is blockDim.x / 64 waves on the SAME tile: wave w takes the chunks w, w + nw, ... (its own record slots in LDS,
 // no workgroup barrier inside the loop) and the partial rows are added up through LDS in wave order at the end -- the same sums
-// on every run.  The host uses it (3 waves) while the workgroups are fewer than the SIMDs (msda_api.hip): 60 queries 0.020 ->
+// on every run.  The host uses it (3 waves) while the workgroups are fewer than the SIMDs (msda_plan.hip): 60 queries 0.020 ->
 // 0.013 ms (fp16 0.034 -> 0.015); at 300 queries in fp32 (1824 workgroups) it changes nothing.
 template <typename T, typename TL, int G, int NB, bool MW>       // T: value / out, TL: sampling_loc / attn_weight
 __global__ void __launch_bounds__(MW ? kWave * kTileMaxWaves : kWave, 4)

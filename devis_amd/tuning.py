@@ -1,7 +1,7 @@
 """Measured kernel routes: time the alternatives the library has for a call shape on THIS GPU and pin the winner
 (include/msda.h, ``msda_pin_route``; round 5).
 
-The library's route rules (``csrc/msda_api.hip``, the ``plan_*`` functions) were calibrated on three pyramids and a few batch sizes.  They
+The library's route rules (``csrc/msda_plan.hip``, the ``plan_*`` functions) were calibrated on three pyramids and a few batch sizes.  They
 stay as the fallback; ``tune`` replaces guessing by measurement for the shapes a user actually runs::
 
     import devis_amd

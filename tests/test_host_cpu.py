@@ -491,7 +491,7 @@ def test_split_k_weight_gradient_on_16_bit_inputs_is_as_accurate_as_one_gemm():
 
 def test_grad_value_dtype_of_operands_that_are_not_16_byte_aligned_is_answered_on_the_host(monkeypatch):
     """A 16-bit `value` or `grad_out` view at an odd storage offset takes grad_value in the arithmetic type (the library would
-    refuse the storage type there: csrc/msda_api.hip fast_path_takes), and float64 never has another: all three answers come
+    refuse the storage type there: csrc/msda_plan.hip fast_path_takes), and float64 never has another: all three answers come
     from the pointers and dtypes alone, without the library."""
     from devis_amd import _native
 

@@ -124,7 +124,7 @@ def test_matrix_pipe_scatter_is_automatic_on_the_bench_batch_and_off_for_one_cli
 
 def test_gather_pass_leaves_records_only_for_the_owner_kernels_levels(monkeypatch):
     """Round 6: with the coarse levels on the matrix pipe the gather pass writes culling records for levels [0, l0) only
-    (msda_api.hip: the plan is made before the gather pass).  The same results with every record written
+    (msda_plan.hip: the plan is made before the gather pass).  The same results with every record written
     (MSDA_BWD_ALL_RECORDS=1, a measurement hook), on a decoder batch that takes the route by itself."""
     from devis_amd import _native
     monkeypatch.delenv("MSDA_SCATTER_MFMA", raising=False)

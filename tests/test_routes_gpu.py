@@ -8,13 +8,14 @@ import pytest
 import torch
 
 from helpers import PYR_A, make_temporal_inputs
+from route_cases import PYR, SINGLE_FRAME_FORWARD_ROUTES, TEMPORAL_CALL_ROUTES
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(autouse=True)
 def rules_only(request):
-    """The route expectations below are those of the RULES (csrc/msda_api.hip): the shipped table of measured routes
+    """The route expectations below are those of the RULES (csrc/msda_plan.hip): the shipped table of measured routes
     (devis_amd/routes.json) is taken out for them and put back afterwards; the tests of the table itself keep it."""
     from devis_amd import _native
     _native.load()
@@ -28,7 +29,6 @@ def rules_only(request):
         _native.clear_routes()
         _native._load_shipped_routes()
 
-PYR = {"A": [(45, 80), (23, 40), (12, 20), (6, 10)], "S": [(60, 96), (30, 48), (15, 24), (8, 12)], "B": [(100, 167), (50, 84), (25, 42), (13, 21)]}
 DEV = "cuda:0"
 
 
@@ -55,29 +55,8 @@ def _temporal(pyr, clips, Lq, dtype, T=6):
     return fwd, _native.last_route()
 
 
-@pytest.mark.parametrize("pyr,clips,Lq,dtype,fwd_has,bwd_has", [
-    # the call DeVIS issues: tile forward, gather pass on the slab kernel with the frames as a workgroup index
-    ("A", 1, 300, torch.float32, "(tile kernel)", "one source frame per workgroup"),
-    ("B", 1, 300, torch.bfloat16, "tile kernel", "one source frame per workgroup"),
-    # ... at the query counts of DeVIS's shipped configs (60 per frame on YouTube-VIS, 180 on OVIS): 2.5-3x faster than the tile kernels
-    ("A", 1, 60, torch.float32, "tile kernel, several waves per tile", "one source frame per workgroup"),
-    ("S", 1, 180, torch.float16, "tile kernel, several waves per tile", "one source frame per workgroup"),
-    # the bench batch
-    ("A", 16, 300, torch.float32, "resident-slab kernel, 1 tiles per wave", "one source frame per workgroup"),
-    ("A", 16, 300, torch.bfloat16, "resident-slab kernel, 4 tiles per wave", "one source frame per workgroup"),
-    # large maps outside the slab: no frame split (12-20 % slower there)
-    ("B", 16, 300, torch.float32, "resident-slab kernel, 1 tiles per wave", "resident-slab kernel, grad_loc/grad_attn)"),
-    ("S", 16, 300, torch.float32, "resident-slab kernel, 1 tiles per wave", "resident-slab kernel, grad_loc/grad_attn)"),
-    ("S", 16, 300, torch.bfloat16, "resident-slab kernel", "one source frame per workgroup"),
-    # encoder-shaped calls: slab kernels while three levels fit, window kernels when a 4-byte slab holds two or fewer
-    ("A", 1, None, torch.float32, "resident-slab kernel, 2 tiles per wave", "resident-slab kernel, grad_loc/grad_attn)"),
-    ("A", 1, None, torch.bfloat16, "resident-slab kernel, 4 tiles per wave", "resident-slab kernel, grad_loc/grad_attn)"),
-    ("S", 1, None, torch.float32, "resident-window kernel", "resident-window kernel"),
-    ("S", 1, None, torch.bfloat16, "resident-slab kernel, 2 tiles per wave", "resident-slab kernel, grad_loc/grad_attn)"),
-    # four clips in fp32: one round of (clip, head, part) workgroups -> the frame-split grid; not in 2-byte types
-    ("A", 4, 300, torch.float32, "resident-slab kernel, 1 tiles per wave", "one source frame per workgroup"),
-    ("A", 4, 300, torch.bfloat16, "resident-slab kernel, 1 tiles per wave", "resident-slab kernel, grad_loc/grad_attn)"),
-], ids=lambda v: str(v).replace("torch.", "") if not isinstance(v, str) or len(v) < 3 else None)
+@pytest.mark.parametrize("pyr,clips,Lq,dtype,fwd_has,bwd_has", TEMPORAL_CALL_ROUTES,
+                         ids=lambda v: str(v).replace("torch.", "") if not isinstance(v, str) or len(v) < 3 else None)
 def test_temporal_call_routes(pyr, clips, Lq, dtype, fwd_has, bwd_has):
     fwd, bwd = _temporal(pyr, clips, Lq, dtype)
     assert fwd_has in fwd, fwd
@@ -91,17 +70,18 @@ def test_single_frame_decoder_like_call_on_a_sparse_fp32_slab_takes_the_tile_for
     """36 images x 300 queries on the SwinL pyramid in fp32: the slab would start at level 2 and 19 tiles would sit on 2 x 16
     waves -- the tile forward is 30 % faster there (the gather pass stays on the slab kernel)."""
     from devis_amd import _native
-    shapes = torch.tensor(PYR["S"], dtype=torch.int64, device=DEV)
+    (pyr_s, N, Lq, _, _), (pyr_a, _, _, _, _) = SINGLE_FRAME_FORWARD_ROUTES
+    shapes = torch.tensor(PYR[pyr_s], dtype=torch.int64, device=DEV)
     lsi = torch.cat((shapes.new_zeros(1), shapes.prod(1).cumsum(0)[:-1]))
-    S, N, Lq = int(shapes.prod(1).sum()), 36, 300
+    S = int(shapes.prod(1).sum())
     value = torch.zeros(N, S, 8, 32, device=DEV)
     loc = torch.full((N, Lq, 8, 4, 4, 2), 0.5, device=DEV)
     aw = torch.zeros(N, Lq, 8, 4, 4, device=DEV)
     out = torch.empty(N, Lq, 256, device=DEV)
     _native.forward(value, shapes, lsi, loc, aw, out)
     assert "tile kernel" in _native.last_route(), _native.last_route()
-    value_a = torch.zeros(N, 4820, 8, 32, device=DEV)
-    shapes_a = torch.tensor(PYR["A"], dtype=torch.int64, device=DEV)
+    shapes_a = torch.tensor(PYR[pyr_a], dtype=torch.int64, device=DEV)
+    value_a = torch.zeros(N, int(shapes_a.prod(1).sum()), 8, 32, device=DEV)
     lsi_a = torch.cat((shapes_a.new_zeros(1), shapes_a.prod(1).cumsum(0)[:-1]))
     _native.forward(value_a, shapes_a, lsi_a, loc, aw, out)
     assert "resident-slab kernel" in _native.last_route(), _native.last_route()

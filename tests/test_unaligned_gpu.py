@@ -1,6 +1,6 @@
 """GPU: every kernel route on contiguous operands that are not 16-byte aligned -- views at an odd offset of a flat buffer, as
 `x[1:]`, a piece of torch.split with an odd row size or a parameter inside a flattened bucket are.  The dispatcher decides
-from the pointers at every call whether a kernel may use 16-byte accesses (csrc/msda_api.hip: fast_path_takes for value, out,
+from the pointers at every call whether a kernel may use 16-byte accesses (csrc/msda_plan.hip: fast_path_takes for value, out,
 grad_out and grad_value; wide_loads / wide_stores for the sampling arrays and their gradients), and tensors fresh from the
 caching allocator only ever select the wide side of those decisions.
 
