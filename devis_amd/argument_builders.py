@@ -284,3 +284,32 @@ def patch_mask_losses(criterion_module):
 def unpatch_mask_losses(criterion_module, previous):
     """Undo :func:`patch_mask_losses` (tests)."""
     criterion_module.SetCriterion.loss_masks = previous
+
+
+def patch_tracker(tracker_module, matcher_module):
+    """Opt-in: make the reference's clip stitching (``src.models.tracker``, ``src.models.matcher``) run on
+    :func:`devis_amd.binarize_masks` and :func:`devis_amd.mask_soft_iou` (:mod:`devis_amd.tracking`):
+    ``Tracker.process_masks`` keeps the stitching frames as small :class:`devis_amd.LogitMask` s and encodes the others
+    through one binarise call; the module's ``encode_mask`` accepts a ``LogitMask``; and
+    ``HungarianInferenceMatcher.compute_volumetric_iou_cost`` / ``compute_frame_average_iou_cost`` compute the soft IoU
+    matrix in one operator call (with ``use_binary_mask_iou`` they run as before).  Takes effect at once, also for trackers
+    and matchers that already exist.  Returns what was replaced (to undo the patch; :func:`unpatch_tracker`).  The other
+    patches are separate choices."""
+    from . import tracking
+    matcher = matcher_module.HungarianInferenceMatcher
+    previous = {"process_masks": tracker_module.Tracker.process_masks, "encode_mask": tracker_module.encode_mask,
+                "compute_volumetric_iou_cost": matcher.compute_volumetric_iou_cost,
+                "compute_frame_average_iou_cost": matcher.compute_frame_average_iou_cost}
+    tracker_module.Tracker.process_masks = tracking.make_process_masks(tracker_module)
+    tracker_module.encode_mask = tracking.make_encode_mask(tracker_module, previous["encode_mask"])
+    matcher.compute_volumetric_iou_cost = tracking.make_iou_cost(previous["compute_volumetric_iou_cost"], "volume")
+    matcher.compute_frame_average_iou_cost = tracking.make_iou_cost(previous["compute_frame_average_iou_cost"], "frame")
+    return previous
+
+
+def unpatch_tracker(tracker_module, matcher_module, previous):
+    """Undo :func:`patch_tracker` (tests)."""
+    tracker_module.Tracker.process_masks = previous["process_masks"]
+    tracker_module.encode_mask = previous["encode_mask"]
+    matcher_module.HungarianInferenceMatcher.compute_volumetric_iou_cost = previous["compute_volumetric_iou_cost"]
+    matcher_module.HungarianInferenceMatcher.compute_frame_average_iou_cost = previous["compute_frame_average_iou_cost"]

@@ -26,6 +26,9 @@ through the C ABI, the same numbers -- and whose fake implementation gives shape
                                ``mask_head_stage_backward`` computes the gradients its ``grads`` mask names
 ``mask_loss_terms``            the mask loss (:func:`mask_loss_terms`; include/maskloss.h) -> (focal [N], dice [N], the
                                [N, 3] sums the backward needs); ``mask_loss_terms_backward`` computes grad_src
+``mask_soft_iou``              the clip-stitching cost (:func:`mask_soft_iou`; include/maskiou.h) -> (iou [Na, Nb], inter
+                               [F, Na, Nb], sum_a [F, Na], sum_b [F, Nb]); an inference operator: no autograd formula
+``binarize_masks``             the binarised full-resolution masks (:func:`binarize_masks`) -> bool [N, H, W]
 =============================  ==========================================================================================
 
 Everything that reads the host or keeps Python state -- the ``spatial_shapes`` host hint, the frame-table cache, the
@@ -48,6 +51,7 @@ from . import _native
 from .functions import attention_maps as _A
 from .functions import deform_conv as _D
 from .functions import mask_head_stage as _S
+from .functions import mask_iou as _I
 from .functions import mask_losses as _L
 from .functions import ms_deform_attn_func as _F
 
@@ -743,3 +747,88 @@ def mask_losses(src_masks, target_masks, num_boxes, alpha=0.25, gamma=2.0):
     tensor, as in the reference; the two tiny reductions stay in torch."""
     focal, dice = mask_loss_terms(src_masks, target_masks, alpha, gamma)
     return {"loss_mask": focal.sum() / num_boxes, "loss_dice": dice.sum() / num_boxes}
+
+
+# ---- clip stitching (include/maskiou.h) --------------------------------------------------------------------------------
+
+@_op("mask_soft_iou")
+def mask_soft_iou_op(a: Tensor, b: Tensor, size: List[int], reduce: str, eps: float) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``mask_soft_iou`` on [N, F, h, w] logits with every argument given: (iou, inter, sum_a, sum_b)."""
+    return _I._pairwise(a, b, size, reduce, eps)
+
+
+@mask_soft_iou_op.register_fake
+def _(a, b, size, reduce, eps):
+    Na, Nb, F = _I.check_pair(a, b, size)[:3]
+    _I.check_reduce(reduce)
+    _I.check_eps(eps)
+    acc = _native.acc_dtype(a.dtype)
+    return _empty(a, (Na, Nb), acc), _empty(a, (F, Na, Nb), acc), _empty(a, (F, Na), acc), _empty(a, (F, Nb), acc)
+
+
+@_op("binarize_masks")
+def binarize_masks_op(src: Tensor, size: List[int], order: str) -> Tensor:
+    """``binarize_masks`` with every argument given: bool [N, H, W] (for "F" the transposed view of a dense [N, W, H])."""
+    return _I._binarize(src, size, order)
+
+
+@binarize_masks_op.register_fake
+def _(src, size, order):
+    N, _h, _w, H, W = _I.check_src(src, size)
+    _I.check_order(order)
+    if order == "F":
+        return _empty(src, (N, W, H), torch.bool).transpose(1, 2)
+    return _empty(src, (N, H, W), torch.bool)
+
+
+def _stitch_args(a, b):
+    _I._require(a.dim() == b.dim() and a.dim() in (3, 4), "mask_soft_iou: a and b must be [N, F, h, w] (or [N, h, w])")
+    _I.check_no_grad("mask_soft_iou", [("a", a), ("b", b)])
+    return (a[:, None], b[:, None]) if a.dim() == 3 else (a, b)
+
+
+def _soft_iou(a, b, size, reduce, eps):
+    a, b = _stitch_args(a, b)
+    size = [size[0], size[1]] if len(size) == 2 else list(size)
+    if torch.compiler.is_compiling():
+        return mask_soft_iou_op(a, b, size, reduce, eps)
+    with torch.no_grad():
+        return _I._pairwise(a, b, size, reduce, eps)
+
+
+def mask_soft_iou(a, b, size, *, reduce="volume", eps=1e-6):
+    """The soft mask IoU between every map of ``a`` and every map of ``b`` -- DeVIS's clip-stitching cost
+    (``HungarianInferenceMatcher.soft_iou`` over all pairs) -- on the fused HIP kernels of include/maskiou.h::
+
+        pa = F.interpolate(a, size=size, mode="bilinear", align_corners=False).sigmoid().flatten(2)      # [Na, F, H*W]
+        pb = likewise                                                                                     # [Nb, F, H*W]
+        inter = einsum("ifk,jfk->fij", pa, pb);  sa = pa.sum(2).T;  sb = pb.sum(2).T
+        "volume":  I, Sa, Sb = the sums over f;  I / (Sa[:, None] + Sb[None] - I).clamp(min=eps)
+        "frame":   (inter / (sa[:, :, None] + sb[:, None] - inter).clamp(min=eps)).mean(0)
+
+    ``a`` [Na, F, h, w] and ``b`` [Nb, F, h, w] logits (or [N, h, w]: one frame) of one dtype (f32 / f64 / bf16 / f16);
+    ``size`` the (H, W) both are resampled to.  Returns [Na, Nb] in float32 (float64 for float64 logits).  The probability
+    maps never exist in memory.  An inference operator: no gradient, and an input that requires one while gradients are
+    recorded raises.  GPU tensors only.  Bitwise reproducible; an entry has the same bits alone and in any larger call."""
+    return _soft_iou(a, b, size, _I.check_reduce(reduce), _I.check_eps(eps))[0]
+
+
+def mask_soft_iou_terms(a, b, size):
+    """``(inter [F, Na, Nb], sum_a [F, Na], sum_b [F, Nb])`` of :func:`mask_soft_iou`: per frame the sum over the pixels of
+    the product of the two probability maps, and of each map's probabilities."""
+    return tuple(_soft_iou(a, b, size, "volume", 1e-6)[1:])
+
+
+def binarize_masks(src, size, *, order="C"):
+    """``F.interpolate(src[:, None], size=size, mode="bilinear", align_corners=False)[:, 0] > 0`` as bool [N, H, W] on the
+    HIP kernel of include/maskiou.h: the reference's ``sigmoid() > 0.5`` without the float map (the two differ only for
+    logits between 0 and about 6e-8).  ``src`` [N, h, w] logits (f32 / f64 / bf16 / f16).  ``order="F"`` returns the
+    transposed view of a dense [N, W, H] buffer: every mask in Fortran order, as a run-length encoder reads it.  NaN gives
+    False.  An inference operator: no gradient.  GPU tensors only."""
+    order = _I.check_order(order)
+    _I.check_no_grad("binarize_masks", [("src", src)])
+    size = [size[0], size[1]] if len(size) == 2 else list(size)
+    if torch.compiler.is_compiling():
+        return binarize_masks_op(src, size, order)
+    with torch.no_grad():
+        return _I._binarize(src, size, order)

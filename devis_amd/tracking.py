@@ -1,0 +1,124 @@
+"""Drop-ins for the clip stitching of the reference's tracker (``src/models/tracker.py``, ``src/models/matcher.py``) on the
+operators of include/maskiou.h (wired by :func:`devis_amd.patch_tracker`).
+
+The reference resamples every trajectory's logit map to the video's resolution, one map at a time, keeps the float
+probability maps of the stitching frames on the GPU, copies float maps to the host to threshold them there, and computes the
+stitching cost pair by pair with a host synchronisation each.  Here a track keeps the small logit map (:class:`LogitMask`),
+the maps to encode are binarised by one kernel call into bytes in the encoder's own memory order, and the cost matrix is one
+operator call and one host copy.
+"""
+import numpy as np
+import torch
+
+
+class LogitMask:
+    """A mask a track keeps for clip stitching: the mask head's ``[h, w]`` logit map and the size it stands for, in place of
+    the full-resolution probability map.  Neither a ``dict`` (an encoded mask) nor ``None`` (no detection), so the
+    reference's checks of ``Track.masks`` treat it as they treat a tensor."""
+
+    __slots__ = ("logits", "size")
+
+    def __init__(self, logits, size):
+        if logits.dim() != 2:
+            raise ValueError("LogitMask: logits must be [h, w], got %s" % (tuple(logits.shape),))
+        self.logits = logits.detach()
+        self.size = (int(size[0]), int(size[1]))
+
+    def probabilities(self):
+        """The map the reference keeps: ``[H, W]`` probabilities, by torch."""
+        x = torch.nn.functional.interpolate(self.logits[None, None], self.size, mode="bilinear", align_corners=False)
+        return x.sigmoid()[0, 0]
+
+    def __repr__(self):
+        return "LogitMask(%s -> %s, %s)" % (tuple(self.logits.shape), self.size, self.logits.dtype)
+
+
+def encode_logits(logits, size, mask_util):
+    """The run-length encodings of ``logits`` [N, h, w] at ``size``, as the reference's ``encode_mask`` returns them: one
+    :func:`devis_amd.binarize_masks` call in Fortran order, one host copy of bytes, then ``mask_util.encode`` per mask."""
+    from .ops import binarize_masks
+    with torch.no_grad():
+        bits = binarize_masks(logits, size, order="F")
+    host = bits.transpose(1, 2).cpu().numpy()           # the dense [N, W, H] buffer
+    out = []
+    for n in range(host.shape[0]):
+        rle = mask_util.encode(host[n].T)               # [H, W], Fortran-contiguous, no copy
+        rle["counts"] = rle["counts"].decode("utf-8")
+        out.append(rle)
+    return out
+
+
+def frames_to_encode(use_binary_mask_iou, overlap_window, start_idx, idx, num_masks):
+    """Which of a clip's ``num_masks`` frames the reference's ``process_masks`` encodes at once (the others are kept for
+    stitching): all of them for binary mask IoU; else, for the first clip, those before the last ``overlap_window`` frames,
+    and for a later clip those between the two overlaps and those before ``start_idx``."""
+    if use_binary_mask_iou:
+        return [True] * num_masks
+    if idx == 0:
+        return [t < num_masks - overlap_window for t in range(num_masks)]
+    return [overlap_window + start_idx <= t < num_masks - overlap_window or t < start_idx for t in range(num_masks)]
+
+
+def make_process_masks(tracker_module):
+    def process_masks(self, start_idx, idx, tgt_size, masks):
+        """Drop-in for ``Tracker.process_masks``: the reference's choice of frames; the frames to encode through one
+        binarise call, the kept ones as :class:`LogitMask`."""
+        num_masks = masks.shape[0]
+        encode = frames_to_encode(self.hungarian_matcher.use_binary_mask_iou, self.overlap_window, start_idx, idx, num_masks)
+        which = [t for t in range(num_masks) if encode[t]]
+        processed = [None if encode[t] else LogitMask(masks[t], tgt_size) for t in range(num_masks)]
+        if which:
+            picked = masks.detach() if len(which) == num_masks else masks.detach()[which]
+            for t, rle in zip(which, encode_logits(picked, tgt_size, tracker_module.mask_util)):
+                processed[t] = rle
+        return processed
+
+    return process_masks
+
+
+def make_encode_mask(tracker_module, previous):
+    def encode_mask(mask):
+        """Drop-in for the tracker module's ``encode_mask``: a :class:`LogitMask` is binarised on the GPU; anything else
+        goes to the replaced function."""
+        if isinstance(mask, LogitMask):
+            return encode_logits(mask.logits[None], mask.size, tracker_module.mask_util)[0]
+        return previous(mask)
+
+    return encode_mask
+
+
+def _stack(masks_per_track):
+    """[N, F, h, w] logits and the common target size of the tracks' LogitMasks."""
+    size, rows = None, []
+    for masks in masks_per_track:
+        for m in masks:
+            if not isinstance(m, LogitMask):
+                raise TypeError("expected a LogitMask among the stitching frames' masks, got %s" % type(m).__name__)
+            if size is None:
+                size = m.size
+            elif m.size != size:
+                raise RuntimeError("the stitching frames' masks stand for different sizes: %s and %s" % (size, m.size))
+        rows.append(torch.stack([m.logits for m in masks]))
+    return torch.stack(rows), size
+
+
+def make_iou_cost(previous, reduce):
+    def iou_cost(self, track1, track2):
+        """Drop-in for ``HungarianInferenceMatcher.compute_volumetric_iou_cost`` / ``compute_frame_average_iou_cost`` for
+        soft IoU: the tracks' logit maps stacked, one :func:`devis_amd.mask_soft_iou` call, one host copy; float64
+        ``[len(track1), len(track2)]`` as the reference returns.  (Every pair is computed: the reference's reuse of a value
+        for equal mask ids gives the same numbers.)  With ``use_binary_mask_iou`` the replaced method runs."""
+        if self.use_binary_mask_iou:
+            return previous(self, track1, track2)
+        if not len(track1) or not len(track2):
+            return np.zeros([len(track1), len(track2)])
+        from .ops import mask_soft_iou
+        a, size = _stack([track.get_last_results(self.overlap_w, "masks") for track in track1])
+        b, size_b = _stack([track.get_first_results(self.overlap_w, "masks") for track in track2])
+        if size_b != size:
+            raise RuntimeError("the stitching frames' masks stand for different sizes: %s and %s" % (size, size_b))
+        with torch.no_grad():
+            iou = mask_soft_iou(a, b, size, reduce=reduce)
+        return iou.cpu().numpy().astype(np.float64)
+
+    return iou_cost
