@@ -286,7 +286,7 @@ def unpatch_mask_losses(criterion_module, previous):
     criterion_module.SetCriterion.loss_masks = previous
 
 
-def patch_tracker(tracker_module, matcher_module):
+def patch_tracker(tracker_module, matcher_module, *, gpu_rle=False):
     """Opt-in: make the reference's clip stitching (``src.models.tracker``, ``src.models.matcher``) run on
     :func:`devis_amd.binarize_masks` and :func:`devis_amd.mask_soft_iou` (:mod:`devis_amd.tracking`):
     ``Tracker.process_masks`` keeps the stitching frames as small :class:`devis_amd.LogitMask` s and encodes the others
@@ -294,14 +294,22 @@ def patch_tracker(tracker_module, matcher_module):
     ``HungarianInferenceMatcher.compute_volumetric_iou_cost`` / ``compute_frame_average_iou_cost`` compute the soft IoU
     matrix in one operator call (with ``use_binary_mask_iou`` they run as before).  Takes effect at once, also for trackers
     and matchers that already exist.  Returns what was replaced (to undo the patch; :func:`unpatch_tracker`).  The other
-    patches are separate choices."""
+    patches are separate choices.
+
+    ``gpu_rle=True`` (an opt-in of its own): the frames to encode go through :func:`devis_amd.mask_run_lengths` and the
+    module's ``mask_util.frPyObjects`` instead of the byte map and ``mask_util.encode``
+    (:func:`devis_amd.tracking.encode_logits_rle`); a mask with more runs than the operator's cap still takes the byte path.
+    Raises AttributeError, before anything is replaced, when the module's ``mask_util`` has no ``frPyObjects``."""
     from . import tracking
     matcher = matcher_module.HungarianInferenceMatcher
+    if gpu_rle and not hasattr(tracker_module.mask_util, "frPyObjects"):
+        raise AttributeError("patch_tracker(gpu_rle=True): the tracker module's mask_util has no frPyObjects to pack the "
+                             "run lengths with")
     previous = {"process_masks": tracker_module.Tracker.process_masks, "encode_mask": tracker_module.encode_mask,
                 "compute_volumetric_iou_cost": matcher.compute_volumetric_iou_cost,
                 "compute_frame_average_iou_cost": matcher.compute_frame_average_iou_cost}
-    tracker_module.Tracker.process_masks = tracking.make_process_masks(tracker_module)
-    tracker_module.encode_mask = tracking.make_encode_mask(tracker_module, previous["encode_mask"])
+    tracker_module.Tracker.process_masks = tracking.make_process_masks(tracker_module, gpu_rle)
+    tracker_module.encode_mask = tracking.make_encode_mask(tracker_module, previous["encode_mask"], gpu_rle)
     matcher.compute_volumetric_iou_cost = tracking.make_iou_cost(previous["compute_volumetric_iou_cost"], "volume")
     matcher.compute_frame_average_iou_cost = tracking.make_iou_cost(previous["compute_frame_average_iou_cost"], "frame")
     return previous

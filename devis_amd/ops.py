@@ -29,6 +29,8 @@ through the C ABI, the same numbers -- and whose fake implementation gives shape
 ``mask_soft_iou``              the clip-stitching cost (:func:`mask_soft_iou`; include/maskiou.h) -> (iou [Na, Nb], inter
                                [F, Na, Nb], sum_a [F, Na], sum_b [F, Nb]); an inference operator: no autograd formula
 ``binarize_masks``             the binarised full-resolution masks (:func:`binarize_masks`) -> bool [N, H, W]
+``mask_run_lengths``           the COCO run lengths of those masks without the masks (:func:`mask_run_lengths`;
+                               include/maskrle.h) -> int32 [N, 1 + max_runs]; an inference operator
 =============================  ==========================================================================================
 
 Everything that reads the host or keeps Python state -- the ``spatial_shapes`` host hint, the frame-table cache, the
@@ -53,6 +55,7 @@ from .functions import deform_conv as _D
 from .functions import mask_head_stage as _S
 from .functions import mask_iou as _I
 from .functions import mask_losses as _L
+from .functions import mask_rle as _R
 from .functions import ms_deform_attn_func as _F
 
 
@@ -832,3 +835,40 @@ def binarize_masks(src, size, *, order="C"):
         return binarize_masks_op(src, size, order)
     with torch.no_grad():
         return _I._binarize(src, size, order)
+
+
+# ---- the run-length encoder (include/maskrle.h) --------------------------------------------------------------------------
+
+@_op("mask_run_lengths")
+def mask_run_lengths_op(src: Tensor, size: List[int], max_runs: int) -> Tensor:
+    """``mask_run_lengths`` with every argument given: int32 [N, 1 + max_runs]."""
+    return _R._run_lengths(src, size, max_runs)
+
+
+@mask_run_lengths_op.register_fake
+def _(src, size, max_runs):
+    N = _R.check_src(src, size, max_runs)[0]
+    return _empty(src, (N, 1 + max_runs), torch.int32)
+
+
+def mask_run_lengths(src, size, *, max_runs=None):
+    """The COCO run lengths of ``binarize_masks(src, size)`` on the HIP kernels of include/maskrle.h, without the byte map:
+    int32 ``runs`` [N, 1 + max_runs] from ``src`` [N, h, w] logits (f32 / f64 / bf16 / f16).  Every mask is walked in
+    column-major order; its counts are the lengths of the alternating runs of equal bits, the first a run of zeros (0 when
+    pixel (0, 0) is set): what ``{"size": [H, W], "counts": [...]}`` holds in an uncompressed COCO encoding.
+    ``runs[n, 0]`` is the mask's number of runs R_n -- the true one, also when it exceeds ``max_runs`` --
+    ``runs[n, 1:1 + min(R_n, max_runs)]`` the counts or their prefix, and the rest of the row 0.  A row with
+    ``R_n > max_runs`` is truncated and must not be decoded.  ``max_runs`` defaults to ``min(H*W + 1, 8*W + 1)``; a compact
+    region has at most ``2*W + 1`` runs.  The bits are those of :func:`binarize_masks` at every pixel (NaN gives 0).  An
+    inference operator: no gradient.  GPU tensors only.  A mask has the same row alone and in any batch."""
+    size = [size[0], size[1]] if len(size) == 2 else list(size)
+    if max_runs is None:            # (the other checks of size are the operator's: nothing here formats a symbolic size)
+        _R._require(len(size) == 2, "mask_run_lengths: size must be (H, W)")
+        max_runs = _R.default_max_runs(size[0], size[1])
+    else:
+        _R.check_max_runs(max_runs)
+    _I.check_no_grad("mask_run_lengths", [("src", src)])
+    if torch.compiler.is_compiling():
+        return mask_run_lengths_op(src, size, max_runs)
+    with torch.no_grad():
+        return _R._run_lengths(src, size, max_runs)

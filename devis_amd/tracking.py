@@ -5,7 +5,8 @@ The reference resamples every trajectory's logit map to the video's resolution, 
 probability maps of the stitching frames on the GPU, copies float maps to the host to threshold them there, and computes the
 stitching cost pair by pair with a host synchronisation each.  Here a track keeps the small logit map (:class:`LogitMask`),
 the maps to encode are binarised by one kernel call into bytes in the encoder's own memory order, and the cost matrix is one
-operator call and one host copy.
+operator call and one host copy.  With ``patch_tracker(..., gpu_rle=True)`` the maps to encode never become bytes: the device
+counts their run lengths (include/maskrle.h) and the host packs the counts (:func:`encode_logits_rle`).
 """
 import numpy as np
 import torch
@@ -48,6 +49,33 @@ def encode_logits(logits, size, mask_util):
     return out
 
 
+def encode_logits_rle(logits, size, mask_util, max_runs=None):
+    """:func:`encode_logits` without the byte map: one :func:`devis_amd.mask_run_lengths` call, one host copy of the rows (a
+    few KB per mask), then ``mask_util.frPyObjects`` on each mask's counts -- the encoder's string packer on an uncompressed
+    encoding.  A mask with more runs than the cap (``max_runs``; the operator's default when None) is never encoded from its
+    truncated row: those masks go through :func:`encode_logits` together, and the results come back in the order of
+    ``logits``."""
+    from .ops import mask_run_lengths
+    H, W = int(size[0]), int(size[1])
+    with torch.no_grad():
+        runs = mask_run_lengths(logits, (H, W), max_runs=max_runs)
+    host = runs.cpu().numpy()
+    cap = host.shape[1] - 1
+    out, over = [None] * host.shape[0], []
+    for n in range(host.shape[0]):
+        count = int(host[n, 0])
+        if count > cap:
+            over.append(n)
+            continue
+        rle = mask_util.frPyObjects({"size": [H, W], "counts": host[n, 1:1 + count].tolist()}, H, W)
+        rle["counts"] = rle["counts"].decode("utf-8")
+        out[n] = rle
+    if over:
+        for n, rle in zip(over, encode_logits(logits[over], (H, W), mask_util)):
+            out[n] = rle
+    return out
+
+
 def frames_to_encode(use_binary_mask_iou, overlap_window, start_idx, idx, num_masks):
     """Which of a clip's ``num_masks`` frames the reference's ``process_masks`` encodes at once (the others are kept for
     stitching): all of them for binary mask IoU; else, for the first clip, those before the last ``overlap_window`` frames,
@@ -59,29 +87,37 @@ def frames_to_encode(use_binary_mask_iou, overlap_window, start_idx, idx, num_ma
     return [overlap_window + start_idx <= t < num_masks - overlap_window or t < start_idx for t in range(num_masks)]
 
 
-def make_process_masks(tracker_module):
+def _encoder(gpu_rle):
+    return encode_logits_rle if gpu_rle else encode_logits
+
+
+def make_process_masks(tracker_module, gpu_rle=False):
+    encode_frames = _encoder(gpu_rle)
+
     def process_masks(self, start_idx, idx, tgt_size, masks):
         """Drop-in for ``Tracker.process_masks``: the reference's choice of frames; the frames to encode through one
-        binarise call, the kept ones as :class:`LogitMask`."""
+        binarise call (one run-length call with ``gpu_rle``), the kept ones as :class:`LogitMask`."""
         num_masks = masks.shape[0]
         encode = frames_to_encode(self.hungarian_matcher.use_binary_mask_iou, self.overlap_window, start_idx, idx, num_masks)
         which = [t for t in range(num_masks) if encode[t]]
         processed = [None if encode[t] else LogitMask(masks[t], tgt_size) for t in range(num_masks)]
         if which:
             picked = masks.detach() if len(which) == num_masks else masks.detach()[which]
-            for t, rle in zip(which, encode_logits(picked, tgt_size, tracker_module.mask_util)):
+            for t, rle in zip(which, encode_frames(picked, tgt_size, tracker_module.mask_util)):
                 processed[t] = rle
         return processed
 
     return process_masks
 
 
-def make_encode_mask(tracker_module, previous):
+def make_encode_mask(tracker_module, previous, gpu_rle=False):
+    encode_frames = _encoder(gpu_rle)
+
     def encode_mask(mask):
         """Drop-in for the tracker module's ``encode_mask``: a :class:`LogitMask` is binarised on the GPU; anything else
         goes to the replaced function."""
         if isinstance(mask, LogitMask):
-            return encode_logits(mask.logits[None], mask.size, tracker_module.mask_util)[0]
+            return encode_frames(mask.logits[None], mask.size, tracker_module.mask_util)[0]
         return previous(mask)
 
     return encode_mask
