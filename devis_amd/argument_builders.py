@@ -286,32 +286,46 @@ def unpatch_mask_losses(criterion_module, previous):
     criterion_module.SetCriterion.loss_masks = previous
 
 
-def patch_tracker(tracker_module, matcher_module, *, gpu_rle=False):
+def patch_tracker(tracker_module, matcher_module, *, gpu_rle=False, gpu_binary_iou=False):
     """Opt-in: make the reference's clip stitching (``src.models.tracker``, ``src.models.matcher``) run on
     :func:`devis_amd.binarize_masks` and :func:`devis_amd.mask_soft_iou` (:mod:`devis_amd.tracking`):
     ``Tracker.process_masks`` keeps the stitching frames as small :class:`devis_amd.LogitMask` s and encodes the others
     through one binarise call; the module's ``encode_mask`` accepts a ``LogitMask``; and
     ``HungarianInferenceMatcher.compute_volumetric_iou_cost`` / ``compute_frame_average_iou_cost`` compute the soft IoU
-    matrix in one operator call (with ``use_binary_mask_iou`` they run as before).  Takes effect at once, also for trackers
+    matrix in one operator call (with ``use_binary_mask_iou`` they run as before, unless ``gpu_binary_iou`` is given).  Takes effect at once, also for trackers
     and matchers that already exist.  Returns what was replaced (to undo the patch; :func:`unpatch_tracker`).  The other
     patches are separate choices.
 
     ``gpu_rle=True`` (an opt-in of its own): the frames to encode go through :func:`devis_amd.mask_run_lengths` and the
     module's ``mask_util.frPyObjects`` instead of the byte map and ``mask_util.encode``
     (:func:`devis_amd.tracking.encode_logits_rle`); a mask with more runs than the operator's cap still takes the byte path.
-    Raises AttributeError, before anything is replaced, when the module's ``mask_util`` has no ``frPyObjects``."""
+    Raises AttributeError, before anything is replaced, when the module's ``mask_util`` has no ``frPyObjects``.
+
+    ``gpu_binary_iou=True`` (an opt-in of its own, which combines freely with ``gpu_rle``): a matcher whose
+    ``use_binary_mask_iou`` is true takes the same route as the soft cost -- ``process_masks`` keeps the stitching frames
+    as ``LogitMask`` s, which the track's own schedule encodes as they leave the window, and the two cost methods make one
+    :func:`devis_amd.mask_binary_iou` call on the stacked maps (a frame without a detection counts as an empty mask; a
+    window of encodings and None only goes to the replaced method).  The reference skips its final ``encode_all_masks()``
+    in binary mode, so ``Track.get_formatted_result`` is wrapped to call it first; what it replaced is returned under a
+    fifth key.  Raises AttributeError, before anything is replaced, when the tracker module has no ``Track``."""
     from . import tracking
     matcher = matcher_module.HungarianInferenceMatcher
+    if gpu_binary_iou and not hasattr(tracker_module, "Track"):
+        raise AttributeError("patch_tracker(gpu_binary_iou=True): the tracker module has no Track whose "
+                             "get_formatted_result could encode the last stitching window")
     if gpu_rle and not hasattr(tracker_module.mask_util, "frPyObjects"):
         raise AttributeError("patch_tracker(gpu_rle=True): the tracker module's mask_util has no frPyObjects to pack the "
                              "run lengths with")
     previous = {"process_masks": tracker_module.Tracker.process_masks, "encode_mask": tracker_module.encode_mask,
                 "compute_volumetric_iou_cost": matcher.compute_volumetric_iou_cost,
                 "compute_frame_average_iou_cost": matcher.compute_frame_average_iou_cost}
-    tracker_module.Tracker.process_masks = tracking.make_process_masks(tracker_module, gpu_rle)
+    if gpu_binary_iou:
+        previous["get_formatted_result"] = tracker_module.Track.get_formatted_result
+        tracker_module.Track.get_formatted_result = tracking.make_get_formatted_result(previous["get_formatted_result"])
+    tracker_module.Tracker.process_masks = tracking.make_process_masks(tracker_module, gpu_rle, gpu_binary_iou)
     tracker_module.encode_mask = tracking.make_encode_mask(tracker_module, previous["encode_mask"], gpu_rle)
-    matcher.compute_volumetric_iou_cost = tracking.make_iou_cost(previous["compute_volumetric_iou_cost"], "volume")
-    matcher.compute_frame_average_iou_cost = tracking.make_iou_cost(previous["compute_frame_average_iou_cost"], "frame")
+    matcher.compute_volumetric_iou_cost = tracking.make_iou_cost(previous["compute_volumetric_iou_cost"], "volume", gpu_binary_iou)
+    matcher.compute_frame_average_iou_cost = tracking.make_iou_cost(previous["compute_frame_average_iou_cost"], "frame", gpu_binary_iou)
     return previous
 
 
@@ -321,3 +335,5 @@ def unpatch_tracker(tracker_module, matcher_module, previous):
     tracker_module.encode_mask = previous["encode_mask"]
     matcher_module.HungarianInferenceMatcher.compute_volumetric_iou_cost = previous["compute_volumetric_iou_cost"]
     matcher_module.HungarianInferenceMatcher.compute_frame_average_iou_cost = previous["compute_frame_average_iou_cost"]
+    if "get_formatted_result" in previous:          # (patched with gpu_binary_iou=True)
+        tracker_module.Track.get_formatted_result = previous["get_formatted_result"]

@@ -31,6 +31,10 @@ through the C ABI, the same numbers -- and whose fake implementation gives shape
 ``binarize_masks``             the binarised full-resolution masks (:func:`binarize_masks`) -> bool [N, H, W]
 ``mask_run_lengths``           the COCO run lengths of those masks without the masks (:func:`mask_run_lengths`;
                                include/maskrle.h) -> int32 [N, 1 + max_runs]; an inference operator
+``mask_binary_iou_terms``      the pixel counts of the binary clip-stitching cost (:func:`mask_binary_iou_terms`;
+                               include/maskbiou.h) -> int32 (inter [Na, Nb, F], area_a [Na, F], area_b [Nb, F])
+``mask_binary_iou``            the binary mask IoU matrix made of them (:func:`mask_binary_iou`) -> float64 [Na, Nb]; both
+                               are inference operators
 =============================  ==========================================================================================
 
 Everything that reads the host or keeps Python state -- the ``spatial_shapes`` host hint, the frame-table cache, the
@@ -52,6 +56,7 @@ from torch import Tensor
 from . import _native
 from .functions import attention_maps as _A
 from .functions import deform_conv as _D
+from .functions import mask_binary_iou as _B
 from .functions import mask_head_stage as _S
 from .functions import mask_iou as _I
 from .functions import mask_losses as _L
@@ -872,3 +877,68 @@ def mask_run_lengths(src, size, *, max_runs=None):
         return mask_run_lengths_op(src, size, max_runs)
     with torch.no_grad():
         return _R._run_lengths(src, size, max_runs)
+
+
+# ---- the binary mask IoU (include/maskbiou.h) ----------------------------------------------------------------------------
+
+@_op("mask_binary_iou_terms")
+def mask_binary_iou_terms_op(a: Tensor, b: Tensor, size: List[int]) -> tuple[Tensor, Tensor, Tensor]:
+    """``mask_binary_iou_terms`` on [N, F, h, w] logits: int32 (inter [Na, Nb, F], area_a [Na, F], area_b [Nb, F])."""
+    return _B._terms(a, b, size)
+
+
+@mask_binary_iou_terms_op.register_fake
+def _(a, b, size):
+    Na, Nb, F = _B.check_pair(a, b, size)[:3]
+    return _empty(a, (Na, Nb, F), torch.int32), _empty(a, (Na, F), torch.int32), _empty(a, (Nb, F), torch.int32)
+
+
+@_op("mask_binary_iou")
+def mask_binary_iou_op(a: Tensor, b: Tensor, size: List[int], reduce: str) -> Tensor:
+    """``mask_binary_iou`` with every argument given: float64 [Na, Nb]."""
+    return _B._binary_iou(a, b, size, reduce)
+
+
+@mask_binary_iou_op.register_fake
+def _(a, b, size, reduce):
+    Na, Nb = _B.check_pair(a, b, size)[:2]
+    _B.check_reduce(reduce)
+    return _empty(a, (Na, Nb), torch.float64)
+
+
+def mask_binary_iou_terms(a, b, size):
+    """The pixel counts a binary mask IoU is made of, between every map of ``a`` and every map of ``b``, on the HIP kernels of
+    include/maskbiou.h: int32 ``(inter [Na, Nb, F], area_a [Na, F], area_b [Nb, F])`` from ``a`` [Na, F, h, w] and ``b``
+    [Nb, F, h, w] logits of one dtype (f32 / f64 / bf16 / f16)::
+
+        A = binarize_masks(a.flatten(0, 1), size).view(Na, F, H*W);  B likewise
+        inter[i, j, f] = (A[i, f] & B[j, f]).sum();  area_a[i, f] = A[i, f].sum();  area_b[j, f] = B[j, f].sum()
+
+    The bits are those of :func:`binarize_masks` at every pixel (NaN gives 0); the byte maps never exist in memory -- a mask
+    is one bit per pixel in the workspace, and an intersection a population count.  The counts are exact integers.  An
+    inference operator: no gradient.  GPU tensors only.  A pair has the same counts alone and in any larger call."""
+    _I.check_no_grad("mask_binary_iou", [("a", a), ("b", b)])
+    size = [size[0], size[1]] if len(size) == 2 else list(size)
+    if torch.compiler.is_compiling():
+        return mask_binary_iou_terms_op(a, b, size)
+    with torch.no_grad():
+        return _B._terms(a, b, size)
+
+
+def mask_binary_iou(a, b, size, *, reduce="volume"):
+    """The IoU of the binarised full-resolution masks between every map of ``a`` and every map of ``b`` -- DeVIS's
+    clip-stitching cost with ``use_binary_mask_iou`` (``HungarianInferenceMatcher.iou`` over all pairs) -- as float64
+    [Na, Nb], formed on the device in int64 from :func:`mask_binary_iou_terms`::
+
+        "volume":  I = inter.sum(2);  U = area_a.sum(1)[:, None] + area_b.sum(1)[None] - I;  I / U, 0.0 where U == 0
+        "frame":   the mean over f of inter / (area_a[:, None] + area_b[None] - inter), each 0.0 where its union is 0
+
+    ``"frame"`` is ``compute_frame_average_iou_cost`` with ``compute_iou_matrix``.  The counts are exact, so a ratio is the
+    correctly rounded quotient of two integers.  An inference operator: no gradient.  GPU tensors only."""
+    reduce = _B.check_reduce(reduce)
+    _I.check_no_grad("mask_binary_iou", [("a", a), ("b", b)])
+    size = [size[0], size[1]] if len(size) == 2 else list(size)
+    if torch.compiler.is_compiling():
+        return mask_binary_iou_op(a, b, size, reduce)
+    with torch.no_grad():
+        return _B._binary_iou(a, b, size, reduce)

@@ -6,7 +6,11 @@ probability maps of the stitching frames on the GPU, copies float maps to the ho
 stitching cost pair by pair with a host synchronisation each.  Here a track keeps the small logit map (:class:`LogitMask`),
 the maps to encode are binarised by one kernel call into bytes in the encoder's own memory order, and the cost matrix is one
 operator call and one host copy.  With ``patch_tracker(..., gpu_rle=True)`` the maps to encode never become bytes: the device
-counts their run lengths (include/maskrle.h) and the host packs the counts (:func:`encode_logits_rle`).
+counts their run lengths (include/maskrle.h) and the host packs the counts (:func:`encode_logits_rle`).  With
+``patch_tracker(..., gpu_binary_iou=True)`` the reference's other cost, the IoU of the binarised masks
+(``use_binary_mask_iou``), takes the same route: the stitching frames stay logit maps and the cost matrix is one
+:func:`devis_amd.mask_binary_iou` call (include/maskbiou.h) in place of a host loop over pairs of
+encodings.
 """
 import numpy as np
 import torch
@@ -91,14 +95,17 @@ def _encoder(gpu_rle):
     return encode_logits_rle if gpu_rle else encode_logits
 
 
-def make_process_masks(tracker_module, gpu_rle=False):
+def make_process_masks(tracker_module, gpu_rle=False, gpu_binary_iou=False):
     encode_frames = _encoder(gpu_rle)
 
     def process_masks(self, start_idx, idx, tgt_size, masks):
         """Drop-in for ``Tracker.process_masks``: the reference's choice of frames; the frames to encode through one
-        binarise call (one run-length call with ``gpu_rle``), the kept ones as :class:`LogitMask`."""
+        binarise call (one run-length call with ``gpu_rle``), the kept ones as :class:`LogitMask`.  With ``gpu_binary_iou``
+        binary mask IoU keeps the stitching frames too, as the soft cost does; the track's own schedule encodes each as it
+        leaves the window."""
         num_masks = masks.shape[0]
-        encode = frames_to_encode(self.hungarian_matcher.use_binary_mask_iou, self.overlap_window, start_idx, idx, num_masks)
+        binary = self.hungarian_matcher.use_binary_mask_iou and not gpu_binary_iou
+        encode = frames_to_encode(binary, self.overlap_window, start_idx, idx, num_masks)
         which = [t for t in range(num_masks) if encode[t]]
         processed = [None if encode[t] else LogitMask(masks[t], tgt_size) for t in range(num_masks)]
         if which:
@@ -138,13 +145,69 @@ def _stack(masks_per_track):
     return torch.stack(rows), size
 
 
-def make_iou_cost(previous, reduce):
+def _stack_binary(masks_per_track):
+    """:func:`_stack` for the binary cost, where a frame without a detection (None) counts as an empty mask: None when the
+    windows hold no LogitMask at all (encodings and None only), else ([N, F, h, w] logits, the common target size) with a map
+    of zeros -- no pixel set -- for every None.  Encodings beside LogitMasks raise TypeError."""
+    first, encoded = None, False
+    for masks in masks_per_track:
+        for m in masks:
+            if isinstance(m, LogitMask):
+                first = first or m
+            elif m is not None:
+                if not isinstance(m, dict):
+                    raise TypeError("expected a LogitMask, an encoded mask or None among the stitching frames' masks, got %s"
+                                    % type(m).__name__)
+                encoded = True
+    if first is None:
+        return None
+    if encoded:
+        raise TypeError("the stitching frames hold encoded masks beside LogitMasks: the binary mask IoU takes a window of "
+                        "one kind")
+    empty = LogitMask(torch.zeros_like(first.logits), first.size)
+    return _stack([[empty if m is None else m for m in masks] for masks in masks_per_track])
+
+
+def _binary_iou_cost(matcher, previous, track1, track2, reduce):
+    """The binary cost of :func:`make_iou_cost`: the windows' maps stacked, one :func:`devis_amd.mask_binary_iou` call, one
+    host copy.  A window without a LogitMask goes to the replaced method."""
+    if not len(track1) or not len(track2):
+        return np.zeros([len(track1), len(track2)])
+    windows1 = [track.get_last_results(matcher.overlap_w, "masks") for track in track1]
+    windows2 = [track.get_first_results(matcher.overlap_w, "masks") for track in track2]
+    both = _stack_binary(windows1 + windows2)
+    if both is None:
+        return previous(matcher, track1, track2)
+    maps, size = both
+    from .ops import mask_binary_iou
+    with torch.no_grad():
+        iou = mask_binary_iou(maps[:len(track1)], maps[len(track1):], size, reduce=reduce)
+    return iou.cpu().numpy()
+
+
+def make_get_formatted_result(previous):
+    def get_formatted_result(self, *args, **kwargs):
+        """Drop-in for ``Track.get_formatted_result`` beside ``gpu_binary_iou``: the reference skips its final
+        ``encode_all_masks()`` in binary mode, where its masks are encodings from the start; here the last clip's trailing
+        window still holds :class:`LogitMask` s, which are encoded first."""
+        self.encode_all_masks()
+        return previous(self, *args, **kwargs)
+
+    return get_formatted_result
+
+
+def make_iou_cost(previous, reduce, gpu_binary_iou=False):
     def iou_cost(self, track1, track2):
         """Drop-in for ``HungarianInferenceMatcher.compute_volumetric_iou_cost`` / ``compute_frame_average_iou_cost`` for
         soft IoU: the tracks' logit maps stacked, one :func:`devis_amd.mask_soft_iou` call, one host copy; float64
         ``[len(track1), len(track2)]`` as the reference returns.  (Every pair is computed: the reference's reuse of a value
-        for equal mask ids gives the same numbers.)  With ``use_binary_mask_iou`` the replaced method runs."""
+        for equal mask ids gives the same numbers.)  With ``use_binary_mask_iou`` the replaced method runs, or -- with
+        ``gpu_binary_iou`` -- one :func:`devis_amd.mask_binary_iou` call on the same stacked maps, a frame without a
+        detection as an empty mask (the reference's ``iou`` adds the other mask's area to the union and nothing to the
+        intersection: what an empty mask gives)."""
         if self.use_binary_mask_iou:
+            if gpu_binary_iou:
+                return _binary_iou_cost(self, previous, track1, track2, reduce)
             return previous(self, track1, track2)
         if not len(track1) or not len(track2):
             return np.zeros([len(track1), len(track2)])
