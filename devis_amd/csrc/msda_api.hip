@@ -125,12 +125,13 @@ int launch_backward(int dtype, const Params &p, const Knobs &k, const Shape &s, 
     if (sc.route == ScatterPlan::kOwner) {
         // owner-computes scatter: no float atomics; pixels outside its bands are zero-filled first
         if (!sc.fused_zero) {
-            rc = launch_zero_unowned(p, kOwnPix * p.D, p.gv_storage ? 2 : 4, stream);
+            rc = launch_zero_unowned(p, kOwnRowPix * p.D, p.gv_storage ? 2 : 4, stream);      // (rows own_row_fits takes are the scatter's)
             if (rc) return rc;
         }
         Params pg = p;
         pg.own_levels = sc.l0;
         pg.rec_mask = sc.rec_mask;
+        pg.own_pix = sc.own_pix;
         if (sc.run_owner)
             rc = launch_scatter_grp(dtype, p.gv_storage != 0, pg, grid * (1024 / kOwnThreads), (k.scatter_dbg & (511 | 4096)) | (sc.fused_zero ? 512 : 0),
                                     sc.image_order, stream);
@@ -150,6 +151,7 @@ int run(int dtype, const Params &p_in, const Knobs &k, bool bwd, hipStream_t str
     Params p = p_in;
     p.own_levels = p.L;
     p.rec_mask = ~0u;
+    p.own_pix = kOwnPix;
     p.dbg = k.dbg;
     // culling records per point (4 x int16) when the owner-computes scatter will read them; (min, max) intervals for the
     // LDS-atomic scatter (MSDA_BWD_CULL=2 forces them)

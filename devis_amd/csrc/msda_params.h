@@ -53,6 +53,8 @@ struct Params {
     int gv_storage;             // bwd: grad_value is in the STORAGE type (16-bit), not the arithmetic type (owner-computes scatter only)
     int own_levels;             // bwd: the owner-computes scatter handles levels [0, own_levels); the trailing (coarse) levels are
                                 // the matrix-pipe scatter's (msda_mfma.hip).  = L when that kernel does not run
+    int own_pix;                // bwd: pixels per band of the owner-computes scatter for THIS call (ScatterPlan::own_pix: 1280 or 1024);
+                                // selects the kernel's slot count at the launch, the planner counted the bands with it
     unsigned rec_mask;          // bwd: bit l = the gather pass leaves culling records for level l and the owner-computes scatter reads
                                 // them; clear for the matrix-pipe levels and for levels that are ONE band (every group a candidate)
 };
@@ -79,8 +81,36 @@ constexpr int kTileMaxWaves = 8;            // forward tile kernel: waves of one
 // owner-computes scatter
 constexpr int kOwnThreads = 1024;                   // (512: two workgroups per CU out of phase with each other)
 constexpr int kOwnQuads = kOwnThreads / 4;
-constexpr int kOwnSlots = 4;                        // pixels per owner quad
+constexpr int kOwnSlots = 4;                        // pixels per owner quad (LDS scatter, per-point owner kernel; the least of own_slots)
 constexpr int kOwnPix = kOwnQuads * kOwnSlots;      // pixels per band
+// The group-granular owner kernel (msda_bwd_value_grp_kernel) keeps FIVE pixels per owner quad where its instantiation has the
+// registers for them at 4 workgroups' worth of waves per SIMD (no VGPR spill, no scratch: profiles/own5_resource_usage.txt):
+// fp32, and the 16-bit types when grad_value is written in the storage type.  A 16-bit type with FLOAT grad_value is at 123
+// VGPRs with four slots and stays there.  The 360x640 pyramid's 45 x 80 level is then 3 bands of 15 rows instead of 4.
+// own_slots is the MOST an instantiation takes: dtype = an msda_dtype code, gv_storage = Params::gv_storage.  Both slot counts are
+// compiled where five fit, and the planner picks one per call (msda_plan.hip, plan_scatter: few-item calls stay on four); the
+// choice travels as ScatterPlan::own_pix / Params::own_pix, so that the kernel launched and every band count agree.
+constexpr int own_slots(int dtype, bool gv_storage) { return (dtype == MSDA_F32 || gv_storage) ? 5 : kOwnSlots; }
+constexpr int own_band_pixels(int dtype, bool gv_storage) { return kOwnQuads * own_slots(dtype, gv_storage); }
+// Bands of a level of H x W pixels at `pix` pixels per band: nb = ceil(H / floor(pix / W)) bands of equal height to within one
+// row -- the first H % nb bands have H / nb + 1 rows, the others H / nb (45 rows in 4 bands: 12, 11, 11, 11) -- instead of runs
+// of floor(pix / W) rows and a short last band.  0 = a "direct" level (no rows, or a row wider than kOwnRowPix = 1024 pixels, own_row_fits: one
+// item, float atomics).  That limit is the same for every slot count, as it was: the fifth slot buys taller bands, not wider rows
+// (a row of 1025-1280 pixels would be a band of ONE row per item), so which levels are "direct", which calls may have a
+// storage-typed grad_value and which need a zero-fill launch of their own does not depend on the instantiation.  Host (planner: band counts, the one-band rule of rec_mask) and device (items, row ranges) evaluate the same integers.
+constexpr int kOwnRowPix = kOwnPix;                 // the widest row a band takes, whatever its slots (also the zero-fill's cap)
+template <typename I> MSDA_HD inline bool own_row_fits(I W) { return W <= (I)kOwnRowPix; }
+template <typename I> MSDA_HD inline I own_band_count(I H, I W, I pix)
+{
+    const I rows = pix / (W > 0 ? W : 1);           // whole rows a band holds
+    return (H <= 0 || rows <= 0 || !own_row_fits(W)) ? 0 : (rows >= H ? 1 : (H + rows - 1) / rows);
+}
+// first and last row of band b of a level cut into nb > 0 bands: q = H / nb, rem = H % nb (no division per band)
+template <typename I> MSDA_HD inline void own_band_rows(I q, I rem, I b, I &r0, I &r1)
+{
+    r0 = b * q + (b < rem ? b : rem);
+    r1 = r0 + q - (b < rem ? 0 : 1);
+}
 // resident-slab kernels
 constexpr int kRsThreads = 1024, kRsWaves = kRsThreads / kWave;     // (512: 8 waves with a 256-VGPR budget each -- measured slower)
 constexpr int kRsRows = kWave / 4;       // rows per wave tile: one quad per row

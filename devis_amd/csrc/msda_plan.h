@@ -50,6 +50,7 @@ struct ScatterPlan {
     int l0 = 0;                         // kOwner: the owner-computes kernel walks levels [0, l0), the matrix-pipe kernel [l0, L)
     int mfma_tiles = 0;                 // kOwner: tiles of the matrix-pipe kernel, 0 = it does not run
     bool run_owner = false, run_mfma = false;   // kOwner: which of the two kernels run (MSDA_SCATTER_PART)
+    int own_pix = kOwnPix;              // kOwner: pixels per band of the owner kernel for this call (Params::own_pix)
     bool fused_zero = false;            // kOwner: the zero-fill rides in the owner kernel's prologue (bit 512 of its dbg)
     bool image_order = false;           // kOwner: the owner kernel's items in image order
     unsigned rec_mask = ~0u;            // levels the gather pass leaves culling records for (Params::rec_mask)

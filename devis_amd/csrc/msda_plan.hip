@@ -237,7 +237,7 @@ bool storage_typed_grad_value_ok(int dtype, const Params &p, const Knobs &k)
     if (k.force_generic || k.bwd_cull == 2) return false;
     if (!owner_scatter_applicable(p, 2, k) || !p.shapes_host) return false;
     for (int l = 0; l < p.L; ++l)
-        if (p.shapes_host[2 * l + 1] > kOwnPix || p.shapes_host[2 * l + 1] <= 0) return false;
+        if (!own_row_fits(p.shapes_host[2 * l + 1]) || p.shapes_host[2 * l + 1] <= 0) return false;
     // the shape conditions of fast_path_takes (pointer alignment is checked at the call: a mismatch is an error there)
     if (p.D % 8 || (int64_t)p.frames * p.S * p.M * p.D >= 0x7fffffffLL) return false;
     if (tile_lds_bytes(kWave / (p.D / 8), p.LA + p.LB, true) > 60 * 1024) return false;
@@ -381,15 +381,15 @@ static void plan_matrix_pipe(int dtype, const Shape &s, const Params &p, const K
 // `clip` outermost the batch is 8 serial tails.
 // (round 4, after the per-item fixed costs shrank: at 360x640, Lq = 4820, image order is now the slower one, 0.555 / 0.529)
 // (a pinned route, msda_pin_route scatter_order: 1 = level order, 2 = image order wherever the bands can be sorted)
-static bool owner_image_order(const Params &p, const Knobs &k, int own_levels)
+static bool owner_image_order(const Params &p, const Knobs &k, int own_levels, long long pix)
 {
     if (!((p.Lq >= 8192 && p.frames > 1) || k.scatter_order == 2) || !p.shapes_host || k.scatter_order == 1) return false;
     int bands = 0;
     for (int l = 0; l < own_levels; ++l) {
         const long long H = p.shapes_host[2 * l], W = p.shapes_host[2 * l + 1];
         if (H <= 0 || W <= 0) return false;         // (degenerate level: the device counts its bands differently)
-        const long long R = std::min<long long>(H, kOwnPix / W);
-        bands += R > 0 ? (int)((H + R - 1) / R) : 1;
+        const long long nb = own_band_count(H, W, pix);       // (0: a "direct" level is one item)
+        bands += nb > 0 ? (int)nb : 1;
     }
     return bands <= kOwnMaxSorted;
 }
@@ -406,13 +406,34 @@ ScatterPlan plan_scatter(int dtype, const Shape &s, const Params &p, const Knobs
     sc.route = owner ? ScatterPlan::kOwner : ScatterPlan::kLds;
     sc.l0 = p.L;
     if (owner) plan_matrix_pipe(dtype, s, p, k, sc);
+    // pixels per band of the owner kernel's instantiation for this call (msda_params.h): the kernel and the rules below count
+    // bands with own_band_count at this size (a row wider than kOwnPix is "direct" at every size)
+    long long pix = own_band_pixels(dtype, p.gv_storage != 0);
+    // FEW-ITEM calls stay on four slots: with about one item per workgroup (at most two per workgroup of the persistent grid,
+    // counted at five slots) a launch lasts as long as its heaviest item, and a band of 15 rows is heavier than one of 12 -- one
+    // clip of the 360x640 decoder call replayed from a graph, 288 items for 256 workgroups: 0.124 -> 0.130 ms at five slots,
+    // with 60 queries 0.0573 -> 0.0606; the SwinL fp16 encoder call image by image + 1.2 % (profiles/own5_ab.log, section 4b).
+    // From 16 clips on (3072 items) five slots win; between 2 and 16 clips nothing was measured.  Without the host copy of the
+    // shapes the items cannot be counted and the call keeps the larger bands.  (MSDA_SCATTER_DBG bit 8192: never -- tests)
+    if (owner && pix > kOwnPix && p.shapes_host && (k.scatter_dbg & 8192) == 0) {
+        long long bands = 0;
+        for (int l = 0; l < sc.l0; ++l) {
+            const long long nb = own_band_count<long long>(p.shapes_host[2 * l], p.shapes_host[2 * l + 1], pix);
+            bands += nb > 0 ? nb : 1;
+        }
+        if ((long long)p.groups * p.M * bands <= 2LL * persistent_grid(s.cus)) pix = kOwnPix;
+    }
+    sc.own_pix = (int)pix;
     // Culling records: not for the matrix-pipe levels, and not for levels of ONE band (the host copy of the shapes says so: every
-    // group is a candidate of the only band, the owner kernel takes all its points) -- the 23x40 level of the 360x640 pyramid.
+    // group is a candidate of the only band, the owner kernel takes all its points) -- the 23x40 level of the 360x640 pyramid; at
+    // five pixels per owner quad the 25x42 level of the 800x1333 one as well.  The device counts the bands with the same function
+    // at the same size (Params::own_pix picks its instantiation): a level it cut in two where the host saw one would take every
+    // group as a candidate of both bands (correct, and slower); the other way round records would be written and never read.
     if (owner && !k.bwd_all_records) {
         for (int l = sc.l0; l < p.L && l < 32; ++l) sc.rec_mask &= ~(1u << l);
         for (int l = 0; p.shapes_host && l < sc.l0 && l < 32; ++l) {
             const long long H = p.shapes_host[2 * l], W = p.shapes_host[2 * l + 1];
-            if (H > 0 && W > 0 && W <= kOwnPix && H <= kOwnPix / W) sc.rec_mask &= ~(1u << l);
+            if (H > 0 && W > 0 && own_band_count(H, W, pix) == 1) sc.rec_mask &= ~(1u << l);
         }
     }
     if (!want_value) sc.rec_mask = 0;
@@ -426,8 +447,8 @@ ScatterPlan plan_scatter(int dtype, const Shape &s, const Params &p, const Knobs
     // zero-fill of the pixels outside the levels -- normally none -- rides in the scatter kernel's prologue (bit 512) instead of
     // a launch of its own in front of it: one dependent dispatch less per backward (one clip from a HIP graph 0.127 -> see r04 logs)
     sc.fused_zero = p.shapes_host != nullptr && (k.scatter_dbg & 1024) == 0;
-    for (int l = 0; sc.fused_zero && l < p.L; ++l) sc.fused_zero = p.shapes_host[2 * l + 1] > 0 && p.shapes_host[2 * l + 1] <= kOwnPix;
-    sc.image_order = owner_image_order(p, k, sc.l0);
+    for (int l = 0; sc.fused_zero && l < p.L; ++l) sc.fused_zero = p.shapes_host[2 * l + 1] > 0 && own_row_fits(p.shapes_host[2 * l + 1]);
+    sc.image_order = owner_image_order(p, k, sc.l0, pix);
     sc.run_owner = !(sc.mfma_tiles && k.scatter_part == 2);
     sc.run_mfma = sc.mfma_tiles && k.scatter_part != 1;
     return sc;

@@ -550,7 +550,8 @@ msda_cull_summary_kernel(const Params p)
 // (8 B entry + 2 x 16 B of the row per lane) and accumulate in fp32 registers: ~650 B of plain LDS traffic
 // per hit instead of 2 KiB of atomics.  Same items (clip, source frame, head, band of pixel rows of one
 // level), same per-point culling records from the gather pass, same survivor list as
-// msda_bwd_value_points_kernel; bands are sized by the owners' registers (kOwnPix pixels) instead of by LDS.
+// msda_bwd_value_points_kernel; bands are sized by the owners' registers (own_band_pixels: 1280 or 1024 pixels, cut into
+// bands of equal height by own_band_count / own_band_rows, msda_params.h; a row wider than kOwnPix is "direct") instead of by LDS.
 // The sum of a pixel's terms is an fp32 sum in list order (the reference's atomicAdd order is arbitrary too,
 // cuh:125-152); terms are the products (w_corner * attn) * grad_out[c].
 constexpr unsigned kOwnNil = 0xffffffffu;
@@ -566,10 +567,11 @@ constexpr unsigned kOwnNil = 0xffffffffu;
 constexpr int kGrpList = 3 * kOwnThreads;       // survivor list entries (groups)
 constexpr int kGrpChunk = 512;                  // groups per chunk
 // (rows are staged as fp32 for every storage type: 128 bytes per group)
-template <typename T> constexpr int grp_lds_bytes()
+template <int SLOTS> constexpr int grp_lds_bytes()
 {
-    return kGrpChunk * 128 + 128 + 16 * kGrpChunk * 8 + kOwnPix * 4 + kGrpList * 4;
+    return kGrpChunk * 128 + 128 + 16 * kGrpChunk * 8 + kOwnQuads * SLOTS * 4 + kGrpList * 4;
 }
+static_assert(grp_lds_bytes<5>() + 8 * 1024 <= 160 * 1024, "the owner kernel's LDS: dynamic part + its static tables");
 
 // T = storage type of loc / attn / grad_out; GV = type of grad_value as written (float, or T: include/msda.h grad_value_dtype).
 // The grad_out rows are staged in LDS as FP32 whatever T is: a 16-bit row would have to be unpacked once per list entry in
@@ -582,10 +584,12 @@ __device__ __forceinline__ int per_item(int x)
     return x;
 }
 
-template <typename T, typename TL, typename GV, bool SORTED>        // SORTED: items in image order (long candidate ranges); TL: storage type of sampling_loc / attn_weight (T, or float with a 16-bit T)
+// SLOTS: pixels per owner quad = accumulator sets per thread (own_slots, msda_params.h); a band is kOwnQuads * SLOTS pixels.
+template <typename T, typename TL, typename GV, bool SORTED, int SLOTS>        // SORTED: items in image order (long candidate ranges); TL: storage type of sampling_loc / attn_weight (T, or float with a 16-bit T)
 __global__ void __launch_bounds__(kOwnThreads, 4)
 msda_bwd_value_grp_kernel(const Params p, int dbg)
 {
+    constexpr int kBandPix = kOwnQuads * SLOTS;                 // pixels per band
     constexpr int D = 32, kRowB = D * 4;                        // bytes of one staged grad_out row (fp32)
     constexpr int kOwnChunk = kGrpChunk;
     constexpr int kPasses = (4 * kOwnChunk + kOwnThreads - 1) / kOwnThreads;
@@ -596,9 +600,10 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
     // entry's row from its address); a reference = the absolute LDS address of an entry
     uint2 *ents = reinterpret_cast<uint2 *>(lds_raw + kOwnChunk * kRowB +
                                             ((128u - (lds_addr(lds_raw) & 127u)) & 127u));
-    unsigned *head = reinterpret_cast<unsigned *>(ents + 16 * kOwnChunk);       // [kOwnPix]
-    unsigned *list = head + kOwnPix;                                            // [kGrpList] (k:6 | points:4 | q:22)
-    __shared__ int s_H[kScatterMaxLevels], s_W[kScatterMaxLevels], s_R[kScatterMaxLevels],
+    unsigned *head = reinterpret_cast<unsigned *>(ents + 16 * kOwnChunk);       // [kBandPix]
+    unsigned *list = head + kBandPix;                                           // [kGrpList] (k:6 | points:4 | q:22)
+    // bands of a level (own_band_count; 0 = "direct" level, a row wider than a band) and their rows (own_band_rows: s_bq = H / bands, s_brem = H % bands)
+    __shared__ int s_H[kScatterMaxLevels], s_W[kScatterMaxLevels], s_nb[kScatterMaxLevels], s_bq[kScatterMaxLevels], s_brem[kScatterMaxLevels],
         s_first[kScatterMaxLevels + 1], s_lsi[kScatterMaxLevels];
     __shared__ int s_cnt[3];             // survivor counters rotate: slot j is reset two barriers before it is used again
     // Item descriptors and source tables are double-buffered: wave 0 prepares item n + 1 (ticket, decode, tables) in the shadow
@@ -619,17 +624,18 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
         int first = 0;
         for (int l = 0; l < L; ++l) {
             const int H = (int)p.shapes[2 * l], W = (int)p.shapes[2 * l + 1];
-            const int R = min(H, kOwnPix / max(1, W));          // rows per band; 0 = "direct" level (row wider than a band)
-            s_H[l] = H; s_W[l] = W; s_R[l] = R; s_lsi[l] = (int)p.lsi[l];
+            const int nb = own_band_count(H, W, kBandPix);
+            s_H[l] = H; s_W[l] = W; s_nb[l] = nb; s_lsi[l] = (int)p.lsi[l];
+            s_bq[l] = nb > 0 ? H / nb : 0; s_brem[l] = nb > 0 ? H % nb : 0;
             s_first[l] = first;
-            first += l >= p.own_levels ? 0 : (R > 0) ? (H + R - 1) / R : 1;       // (levels from own_levels on: no items here, msda_mfma.hip)
+            first += l >= p.own_levels ? 0 : (nb > 0) ? nb : 1;       // (levels from own_levels on: no items here, msda_mfma.hip)
         }
         s_first[L] = first;
         s_cnt[0] = s_cnt[1] = s_cnt[2] = 0;
     }
     if (tid < kWave) s_ftab[tid] = tid < p.frames * p.window ? p.ftab[tid] : -1;
     int ci = 0;                             // counter of the current cull batch
-    for (int i = tid; i < kOwnPix; i += kOwnThreads) head[i] = kOwnNil;
+    for (int i = tid; i < kBandPix; i += kOwnThreads) head[i] = kOwnNil;
     __syncthreads();
     const int NB = s_first[L];
     if (dbg & 512) {
@@ -641,7 +647,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
             const int sp = (int)(idx % p.S);
             bool inside = false, wide = false;
             for (int l = 0; l < L; ++l)
-                if (sp >= s_lsi[l] && sp < s_lsi[l] + s_H[l] * s_W[l]) { inside = true; wide = s_R[l] == 0; }
+                if (sp >= s_lsi[l] && sp < s_lsi[l] + s_H[l] * s_W[l]) { inside = true; wide = s_nb[l] == 0; }
             if (inside && !wide) continue;
             // `wide`: the host's copy of the shapes (a selection HINT, include/msda.h) said every level fits a band, so nothing
             // zero-filled grad_value for the float-atomic branch -- but the DEVICE shapes have a level wider than a band: the hint
@@ -665,7 +671,9 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
             if (tid < NB) {
                 int l = 0;
                 while (l + 1 < L && s_first[l + 1] <= tid) ++l;
-                s_key[tid] = s_R[l] > 0 ? (float)((tid - s_first[l]) * s_R[l]) / (float)s_H[l] : 0.f;
+                int kr0 = 0, kr1 = 0;
+                if (s_nb[l] > 0) own_band_rows(s_bq[l], s_brem[l], tid - s_first[l], kr0, kr1);
+                s_key[tid] = s_nb[l] > 0 ? (float)kr0 / (float)s_H[l] : 0.f;
             }
             __syncthreads();
             if (tid < NB) {
@@ -683,10 +691,18 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
     // static stride only: does the walk of one workgroup -- (item / M) in steps of gridDim / M -- share a factor with the band count?
     // (then it meets the same few bands of every frame and prepare() rotates the bands by the (clip, frame) index)
     unsigned stride_gcd = 1u;
+    // ... and where the band count divides the step and the quotient too (step 32 with the 4 bands of the 360x640 pyramid's levels
+    // 0-1 at five pixels per owner quad: (item / M) + 32, (clip, frame) + 8), the rotation by the (clip, frame) index brings the
+    // workgroup back to the SAME band every time -- one workgroup in four had nothing but the one-band level: 64 clips 4.75 ->
+    // 5.20 ms (profiles/own5_ab.log) -- so there the rotation advances once per step: by (clip, frame) / (step / bands).  (At step 32
+    // that is 4 bands and 2: only the 4-band case was measured; with 2 bands the old rotation stood still for the same reason.)
+    unsigned rot_div = 1u;
     {
-        unsigned a = max(gridDim.x / (unsigned)max(p.M, 1), 1u), b = (unsigned)max(NB, 1);
+        const unsigned step = max(gridDim.x / (unsigned)max(p.M, 1), 1u), nb = (unsigned)max(NB, 1);
+        unsigned a = step, b = nb;
         while (b) { const unsigned t = a % b; a = b; b = t; }
         stride_gcd = a;
+        if (step % nb == 0u && (step / nb) % nb == 0u) rot_div = step / nb;
     }
     const bool rotate_bands = stride_gcd > 1u && (dbg & 4096) == 0;
     const bool clip_major = (long long)p.Lq * (1 + p.window) <= 4096;       // see prepare()
@@ -752,7 +768,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
                 m = (int)(item % M);
                 unsigned rest = item / M;
                 const unsigned fc = rest / (unsigned)NB;
-                part = (int)((rest + (rotate_bands ? fc : 0u)) % (unsigned)NB);
+                part = (int)((rest + (rotate_bands ? fc / rot_div : 0u)) % (unsigned)NB);
                 f = (int)(fc % F);
                 clip = (int)(fc / F);
                 while (l + 1 < L && s_first[l + 1] <= part) ++l;
@@ -801,10 +817,10 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
             __syncthreads();
             continue;
         }
-        const int H = s_H[l], W = s_W[l], R = s_R[l];
-        const bool direct = (R == 0);
-        const int r0 = direct ? 0 : (part - s_first[l]) * R;
-        const int r1 = direct ? H - 1 : min(H, r0 + R) - 1;
+        const int H = s_H[l], W = s_W[l];
+        const bool direct = (s_nb[l] == 0);
+        int r0 = 0, r1 = H - 1;
+        if (!direct) own_band_rows(s_bq[l], s_brem[l], part - s_first[l], r0, r1);
         const int npix = direct ? 0 : (r1 - r0 + 1) * W;
         // Small bands (the last pyramid levels: 60 pixels at 360x640) would keep only npix of the 256 owner quads busy
         // while every pixel's list is long; their hits are dealt round-robin to SF sub-lists per pixel ("virtual
@@ -817,9 +833,9 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
                    (((int64_t)clip * p.frames + f) * p.S + s_lsi[l]) * MD + m * D;        // pixel (0, 0) of the level, head m
         const int ng = s_nsrc * p.Lq;              // candidate groups: (source, query) pairs, <= 4 points each
 
-        float acc[kOwnSlots][8];
+        float acc[SLOTS][8];
 #pragma unroll
-        for (int s = 0; s < kOwnSlots; ++s)
+        for (int s = 0; s < SLOTS; ++s)
 #pragma unroll
             for (int c = 0; c < 8; ++c) acc[s][c] = 0.f;
 
@@ -938,7 +954,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
             // this lane's two 16-byte pieces of a row, relative to the 128-byte group of the entry's own address
             const unsigned row_k1 = lds_addr(rows) - ents_lds + (unsigned)off1, row_k2 = lds_addr(rows) - ents_lds + (unsigned)(off1 ^ 64);
 #pragma unroll
-            for (int s = 0; s < kOwnSlots; ++s) {
+            for (int s = 0; s < SLOTS; ++s) {
                 const int pix = s * kOwnQuads + Q;
                 unsigned e = kOwnNil;
                 if (pix < nvpix) { e = head[pix]; if (e != kOwnNil) head[pix] = kOwnNil; }
@@ -1103,7 +1119,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
             GV *gband = gmap + (int64_t)r0 * W * MD;
             GV *gquad = gband + (int64_t)per_item(Q) * MD;          // pixel Q of the band; slot s is kOwnQuads pixels further
 #pragma unroll
-            for (int s = 0; s < kOwnSlots; ++s) {
+            for (int s = 0; s < SLOTS; ++s) {
                 const int pix = s * kOwnQuads + Q;
                 if constexpr (std::is_same<GV, float>::value) {
                     if (pix < npix) {
@@ -1213,14 +1229,14 @@ int scatter_lds_g(int G, const Params &p, unsigned grid, int cap_bytes, int dbg,
     }
 }
 
-template <typename T, typename TL, typename GV, bool SORTED>
+template <typename T, typename TL, typename GV, bool SORTED, int SLOTS>
 int scatter_grp(const Params &p, unsigned grid, int dbg, hipStream_t stream)
 {
     static LdsGrant granted;
-    const auto kern = &msda_bwd_value_grp_kernel<T, TL, GV, SORTED>;
-    if (const int rc = grant_lds(reinterpret_cast<const void *>(kern), (size_t)grp_lds_bytes<T>(), granted,
+    const auto kern = &msda_bwd_value_grp_kernel<T, TL, GV, SORTED, SLOTS>;
+    if (const int rc = grant_lds(reinterpret_cast<const void *>(kern), (size_t)grp_lds_bytes<SLOTS>(), granted,
                                  "the group-granular owner-computes scatter kernel")) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kOwnThreads), (size_t)grp_lds_bytes<T>(), stream, p, dbg);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kOwnThreads), (size_t)grp_lds_bytes<SLOTS>(), stream, p, dbg);
     if (SORTED)
         return check_launch(std::is_same<GV, float>::value ? "msda backward (owner-computes scatter kernel, group-granular, items in image order)"
                                                            : "msda backward (owner-computes scatter kernel, group-granular, items in image order, grad_value in the storage type)");
@@ -1280,10 +1296,28 @@ int launch_scatter_grp(int dtype, bool storage_typed, const Params &p, unsigned 
     return dispatch_types(dtype, [&](auto t, auto tl) {
         using T = typename decltype(t)::type;
         using TL = typename decltype(tl)::type;
+        // slots per owner quad: Params::own_pix, the planner's choice for this call (msda_plan.hip) -- at most own_slots(dtype,
+        // gv_storage), by the types the code stands for; a size the instantiation has no registers for is an error, not a fall-back
+        const int slots = p.own_pix / kOwnQuads;
+        auto go = [&](auto gv, auto sl) {
+            using GV = typename decltype(gv)::type;
+            constexpr int S = decltype(sl)::value;
+            return image_order ? scatter_grp<T, TL, GV, true, S>(p, grid, dbg, stream) : scatter_grp<T, TL, GV, false, S>(p, grid, dbg, stream);
+        };
+        using four = std::integral_constant<int, kOwnSlots>;
+        using five = std::integral_constant<int, 5>;
+        static_assert(own_slots(MSDA_F32, false) == 5 && own_slots(MSDA_BF16, true) == 5 && own_slots(MSDA_F16, true) == 5 &&
+                      own_slots(MSDA_BF16_LOC32, true) == 5 && own_slots(MSDA_F16_LOC32, true) == 5 && own_slots(MSDA_BF16, false) == kOwnSlots &&
+                      own_slots(MSDA_F16, false) == kOwnSlots && own_slots(MSDA_BF16_LOC32, false) == kOwnSlots && own_slots(MSDA_F16_LOC32, false) == kOwnSlots,
+                      "the instantiations below are the ones own_slots names");
+        if (p.own_pix != slots * kOwnQuads || slots > own_slots(dtype, storage_typed) || (slots != kOwnSlots && slots != 5))
+            return fail(MSDA_ERR_ARG, "msda backward: no owner-computes scatter kernel for this band size%s");
         if constexpr (sizeof(T) == 2) {
-            if (storage_typed) return image_order ? scatter_grp<T, TL, T, true>(p, grid, dbg, stream) : scatter_grp<T, TL, T, false>(p, grid, dbg, stream);
+            if (storage_typed) return slots == 5 ? go(type_tag<T>{}, five{}) : go(type_tag<T>{}, four{});
+            return go(type_tag<float>{}, four{});
+        } else {
+            return slots == 5 ? go(type_tag<float>{}, five{}) : go(type_tag<float>{}, four{});
         }
-        return image_order ? scatter_grp<T, TL, float, true>(p, grid, dbg, stream) : scatter_grp<T, TL, float, false>(p, grid, dbg, stream);
     });
 }
 
