@@ -133,7 +133,7 @@ int launch_backward(int dtype, const Params &p, const Knobs &k, const Shape &s, 
         pg.rec_mask = sc.rec_mask;
         pg.own_pix = sc.own_pix;
         if (sc.run_owner)
-            rc = launch_scatter_grp(dtype, p.gv_storage != 0, pg, grid * (1024 / kOwnThreads), (k.scatter_dbg & (511 | 4096)) | (sc.fused_zero ? 512 : 0),
+            rc = launch_scatter_grp(dtype, p.gv_storage != 0, pg, grid * (1024 / kOwnThreads), (k.scatter_dbg & kSdbgOwnMask) | (sc.fused_zero ? kOwnFusedZero : 0),
                                     sc.image_order, stream);
         if (rc || !sc.run_mfma) return rc;
         return launch_scatter_mfma(dtype, p.gv_storage != 0, p, sc.l0, sc.mfma_tiles, stream);
@@ -142,7 +142,7 @@ int launch_backward(int dtype, const Params &p, const Knobs &k, const Shape &s, 
     const int cap_bytes = k.scatter_lds_kb * 1024;
     rc = launch_zero_unowned(p, cap_bytes / 8, 4, stream);
     if (rc) return rc;
-    return launch_scatter_lds(dtype, p.D / 4, p, grid, cap_bytes, k.scatter_dbg, stream);      // 4 channels per lane
+    return launch_scatter_lds(dtype, p.D / 4, p, grid, cap_bytes, k.scatter_dbg & kSdbgLdsMask, stream);      // 4 channels per lane
 }
 
 int run(int dtype, const Params &p_in, const Knobs &k, bool bwd, hipStream_t stream, int grads = kGradAll)
@@ -158,9 +158,9 @@ int run(int dtype, const Params &p_in, const Knobs &k, bool bwd, hipStream_t str
     p.cull_points = bwd && p.bbox && k.bwd_cull != 2 && owner_scatter_applicable(p, elem_bytes(dtype), k);
     if (!p.cull_points) p.bsum = nullptr;
     p.wide_stores = bwd && aligned16(p.glocA) && aligned16(p.gawA) && (p.LB == 0 || (aligned16(p.glocB) && aligned16(p.gawB))) &&
-                    (k.dbg & 64) == 0;                        // (measurement: MSDA_DBG=64 keeps the narrow stores)
+                    (k.dbg & kDbgNarrowStores) == 0;          // (measurement: keeps the narrow stores)
     p.wide_loads = aligned16(p.locA) && aligned16(p.awA) && (p.LB == 0 || (aligned16(p.locB) && aligned16(p.awB))) &&
-                   (k.dbg & 128) == 0;                        // (measurement: MSDA_DBG=128 keeps the narrow loads)
+                   (k.dbg & kDbgNarrowLoads) == 0;           // (measurement: keeps the narrow loads)
     if (p.groups == 0 || p.Lq == 0) return MSDA_OK;
     if (!k.force_generic && fast_path_takes(dtype, p, k, bwd)) {
         Shape s;

@@ -378,7 +378,7 @@ int launch_cull_summary(const Params &p, hipStream_t stream);
 // per-point records (p.cull_points) or (min, max) intervals (their route has rec_mask = every level).
 int launch_cull_records(int dtype, const Params &p, hipStream_t stream);
 int launch_scatter_lds(int dtype, int G, const Params &p, unsigned grid, int cap_bytes, int dbg, hipStream_t stream);
-int launch_scatter_grp(int dtype, bool storage_typed_grad_value, const Params &p, unsigned grid, int dbg, bool image_order,
+int launch_scatter_grp(int dtype, bool storage_typed_grad_value, const Params &p, unsigned grid, int flags, bool image_order,
                        hipStream_t stream);
 // msda_mfma.hip: grad_value of the trailing levels [l0, L) (at most 2, `tiles` = mfma_scatter_tiles(their pixels)) on the matrix pipe
 int launch_scatter_mfma(int dtype, bool storage_typed_grad_value, const Params &p, int l0, int tiles, hipStream_t stream);

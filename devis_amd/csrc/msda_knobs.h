@@ -25,15 +25,15 @@ struct Knobs {
     int bwd_cull = 1;                   // 0: no culling structure, 2: (min, max) intervals instead of per-point records
     int bwd_all_records = 0;            // measurement: the gather pass leaves records for every level (a later scatter-only call may walk them)
     int scatter_lds_kb = 144;
-    int scatter_dbg = 0;                // MSDA_SCATTER_DBG without bits 256 / 2048: measurement bits the scatter kernels read
-    int scatter_order = 0;              // owner-computes scatter's item order: 0 = rule, 1 = level order (MSDA_SCATTER_DBG bit 256),
-                                        // 2 = image order wherever the bands can be sorted (bit 2048)
+    int scatter_dbg = 0;                // MSDA_SCATTER_DBG without kSdbgOrderMask: the bits the planner and the scatter kernels read (table: msda_params.h)
+    int scatter_order = 0;              // owner-computes scatter's item order: 0 = rule, 1 = level order (MSDA_SCATTER_DBG kSdbgLevelOrder),
+                                        // 2 = image order wherever the bands can be sorted (kSdbgImageOrder)
     int scatter_own = -1;               // owner-computes scatter: -1 auto, 0 off (the LDS-atomic scatter instead)
     int scatter_mfma = -1;              // matrix-pipe scatter of the coarse levels (msda_mfma.hip): -1 auto, 0 off, 1 wherever it applies
     int scatter_part = 0;               // measurement: 1 = only the owner-computes kernel of a scatter that runs both, 2 = only the matrix-pipe kernel
     int force_generic = 0;
     int det_route = 0;                  // MSDA_GRAD_DETERMINISTIC grad_value: 0 auto, 1 = route (a) (any shape), 2 = route (b) (LDS bands)
-    int dbg = 0;
+    int dbg = 0;                        // MSDA_DBG: tile kernels and launcher (kDbg*, msda_params.h)
     unsigned forced = 0;                // bit i: the variable of kKnobs[i] was SET in the environment, whatever its value: a knob
                                         // forced to its default (MSDA_FWD_RS=-1 for a rules-only A/B run) still wins over a pin
 };

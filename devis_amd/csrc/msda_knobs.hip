@@ -23,8 +23,8 @@ int knob_value(Parse parse, const char *text)
     switch (parse) {
         case Parse::IsOne: return v == 1;
         case Parse::IsAtomic: return strcmp(text, "atomic") == 0;
-        case Parse::DbgBits: return v & ~(256 | 2048);
-        case Parse::OrderBits: return (v & 256) ? 1 : (v & 2048) ? 2 : 0;
+        case Parse::DbgBits: return v & ~kSdbgOrderMask;
+        case Parse::OrderBits: return (v & kSdbgLevelOrder) ? 1 : (v & kSdbgImageOrder) ? 2 : 0;
         default: return v;
     }
 }

@@ -49,7 +49,7 @@ struct Params {
     int cull_points;            // bbox entries are 4 x int16 top tap rows, one per POINT (PA, PB <= 4), not (min, max)
     int wide_stores;            // bwd: the four gradient arrays are 16-byte aligned (resident-slab gather pass: whole-row stores)
     int wide_loads;             // loc / attn arrays are 16-byte aligned (resident-slab kernels: whole-row loads)
-    int dbg;                    // measurement hooks (MSDA_DBG env), 0 in production
+    int dbg;                    // measurement hooks (MSDA_DBG env: the kDbg* bits below), 0 in production
     int gv_storage;             // bwd: grad_value is in the STORAGE type (16-bit), not the arithmetic type (owner-computes scatter only)
     int own_levels;             // bwd: the owner-computes scatter handles levels [0, own_levels); the trailing (coarse) levels are
                                 // the matrix-pipe scatter's (msda_mfma.hip).  = L when that kernel does not run
@@ -74,6 +74,55 @@ constexpr int kGradDet = MSDA_GRAD_DETERMINISTIC;
 constexpr int mfma_rows(int MT) { return MT * 32 - 16; }                 // pixel rows per k-chunk of a tile: pixels + 1 trash row <= this
 
 // ------------------------------------------------------------------------------------------------
+// the measurement bits: MSDA_SCATTER_DBG and MSDA_DBG (read only with MSDA_ENABLE_HOOKS=1, msda_knobs.h)
+// ------------------------------------------------------------------------------------------------
+// THE table of both words: every reader tests these names, devis_amd/tuning.py carries the same names and values for tests and
+// scripts (tests/test_plan_cpu.py compares the two), INTEGRATION.md prints it.  A ROUTE bit sends the call another way and keeps
+// its results: tests may set it.  An ABLATION bit cuts work out of a kernel to time the rest: the results are WRONG by
+// construction.  "owner" = msda_bwd_value_grp_kernel, "LDS" = msda_bwd_value_lds_kernel (msda_scatter.hip); the two kernels
+// give some ablation bits different meanings, hence two names for one value.
+//
+// MSDA_SCATTER_DBG, route bits (results kept)
+constexpr int kSdbgStaticStride = 16;       // owner + LDS: items by static stride, never by work tickets.  Results kept
+constexpr int kSdbgLevelOrder = 256;        // knob parser: Knobs::scatter_order = 1, the planner keeps the owner kernel's level-by-level item order.  Results kept
+constexpr int kSdbgSeparateZero = 1024;     // planner: the zero-fill stays a launch of its own (ScatterPlan::fused_zero = false).  Results kept
+constexpr int kSdbgImageOrder = 2048;       // knob parser: Knobs::scatter_order = 2, image order wherever the planner can count the bands.  Results kept
+constexpr int kSdbgNoBandRotation = 4096;   // owner: the static stride never rotates the bands by the (clip, frame) index.  Results kept
+constexpr int kSdbgNoFourSlotRule = 8192;   // planner: few-item calls keep five pixels per owner quad as well.  Results kept
+constexpr int kSdbgOrderMask = kSdbgLevelOrder | kSdbgImageOrder;   // the parser takes these out of Knobs::scatter_dbg (256 wins over 2048)
+constexpr int kSdbgRouteMask = kSdbgStaticStride | kSdbgOrderMask | kSdbgSeparateZero | kSdbgNoBandRotation | kSdbgNoFourSlotRule;
+// MSDA_SCATTER_DBG, ablation bits (timing only: WRONG results)
+constexpr int kSdbgOwnNoWalk = 1;           // owner: lists are built and never walked.  Results WRONG
+constexpr int kSdbgOwnNoLink = 2;           // owner: rows are staged, no corner is linked into a list.  Results WRONG
+constexpr int kSdbgLdsScanOnly = 2;         // LDS: the survivors are listed and never scanned.  Results WRONG
+constexpr int kSdbgOwnNoStage = 4;          // owner: no grad_out row is staged, the walk reads whatever the rows hold.  Results WRONG
+constexpr int kSdbgLdsNoSources = 4;        // LDS: an item has no source frames, only its zero band is flushed.  Results WRONG
+constexpr int kSdbgOwnCullOnly = 8;         // owner: the culling pass runs, its survivor list is dropped.  Results WRONG
+constexpr int kSdbgLdsNoAdds = 8;           // LDS: everything but the LDS adds.  Results WRONG
+constexpr int kSdbgOwnLevelShift = 5, kSdbgOwnLevelMask = 7;    // owner: field (word >> 5) & 7 = level + 1: the items of that level only (0: all).  Results WRONG
+constexpr int kSdbgOwnLevelField = kSdbgOwnLevelMask << kSdbgOwnLevelShift;
+constexpr int kSdbgAblationMask = kSdbgOwnNoWalk | kSdbgOwnNoLink | kSdbgOwnNoStage | kSdbgOwnCullOnly | kSdbgOwnLevelField;
+// what of Knobs::scatter_dbg each kernel reads: the launcher (msda_api.hip) passes nothing else
+constexpr int kSdbgOwnMask = kSdbgStaticStride | kSdbgNoBandRotation | kSdbgAblationMask;
+constexpr int kSdbgLdsMask = kSdbgStaticStride | kSdbgLdsScanOnly | kSdbgLdsNoSources | kSdbgLdsNoAdds;
+// Not an environment bit: the owner kernel's second argument is a word of launch FLAGS, kSdbgOwnMask of the environment's bits
+// and this one, which the launcher sets from ScatterPlan::fused_zero and from nothing else -- the zero-fill of the pixels outside
+// every level runs in the kernel's prologue.  (Value 512: above the kernel's environment bits 0..7, never parsed into them.)
+constexpr int kOwnFusedZero = 512;
+static_assert((kSdbgRouteMask & kSdbgAblationMask) == 0 && ((kSdbgRouteMask | kSdbgAblationMask) & kOwnFusedZero) == 0,
+              "MSDA_SCATTER_DBG: a bit is a route bit, an ablation bit or the launch flag");
+//
+// MSDA_DBG (Knobs::dbg; the tile kernels see it as Params::dbg), route bits (results kept)
+constexpr int kDbgTileRotateHeads = 32;     // tile kernels: heads rotate over the workgroups, breaks the head <-> XCD affinity.  Results kept
+constexpr int kDbgNarrowStores = 64;        // launcher: Params::wide_stores = 0 whatever the alignment of the gradient arrays.  Results kept
+constexpr int kDbgNarrowLoads = 128;        // launcher: Params::wide_loads = 0 whatever the alignment of loc / attn.  Results kept
+constexpr int kDbgRouteMask = kDbgTileRotateHeads | kDbgNarrowStores | kDbgNarrowLoads;
+// MSDA_DBG, ablation bits (timing only: WRONG results)
+constexpr int kDbgTileNoWriteOut = 8;       // backward tile kernel: grad_loc / grad_attn are computed and not stored.  Results WRONG
+constexpr int kDbgTileNoRowSum = 16;        // backward tile kernel: no cross-lane sum of the four corner dots.  Results WRONG
+constexpr int kDbgAblationMask = kDbgTileNoWriteOut | kDbgTileNoRowSum;
+
+// ------------------------------------------------------------------------------------------------
 // launch geometry shared by kernels and dispatcher
 // ------------------------------------------------------------------------------------------------
 constexpr int kRowSlots = kPch + 1;         // tile kernels: 16-byte record slots per row (odd: LDS banks)
@@ -81,7 +130,7 @@ constexpr int kTileMaxWaves = 8;            // forward tile kernel: waves of one
 // owner-computes scatter
 constexpr int kOwnThreads = 1024;                   // (512: two workgroups per CU out of phase with each other)
 constexpr int kOwnQuads = kOwnThreads / 4;
-constexpr int kOwnSlots = 4;                        // pixels per owner quad (LDS scatter, per-point owner kernel; the least of own_slots)
+constexpr int kOwnSlots = 4;                        // pixels per owner quad: the least of own_slots (few-item calls, 16-bit types with float grad_value)
 constexpr int kOwnPix = kOwnQuads * kOwnSlots;      // pixels per band
 // The group-granular owner kernel (msda_bwd_value_grp_kernel) keeps FIVE pixels per owner quad where its instantiation has the
 // registers for them at 4 workgroups' worth of waves per SIMD (no VGPR spill, no scratch: profiles/own5_resource_usage.txt):

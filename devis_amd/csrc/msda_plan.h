@@ -51,7 +51,8 @@ struct ScatterPlan {
     int mfma_tiles = 0;                 // kOwner: tiles of the matrix-pipe kernel, 0 = it does not run
     bool run_owner = false, run_mfma = false;   // kOwner: which of the two kernels run (MSDA_SCATTER_PART)
     int own_pix = kOwnPix;              // kOwner: pixels per band of the owner kernel for this call (Params::own_pix)
-    bool fused_zero = false;            // kOwner: the zero-fill rides in the owner kernel's prologue (bit 512 of its dbg)
+    bool fused_zero = false;            // kOwner: the zero-fill rides in the owner kernel's prologue: the launcher sets the kernel's
+                                        // launch flag kOwnFusedZero (msda_params.h) from this and from nothing else
     bool image_order = false;           // kOwner: the owner kernel's items in image order
     unsigned rec_mask = ~0u;            // levels the gather pass leaves culling records for (Params::rec_mask)
     bool interval_records = false;      // the gather pass leaves (min, max) interval records: only the tile kernel writes those

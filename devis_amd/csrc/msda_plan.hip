@@ -375,7 +375,7 @@ static void plan_matrix_pipe(int dtype, const Shape &s, const Params &p, const K
 
 // Items of the owner-computes scatter in image order for long candidate ranges of a TEMPORAL call (the encoder's fused call: the
 // frames of one band run side by side and share the rows and points of the queries near it), when the host knows the band count
-// (scatter_order 1, MSDA_SCATTER_DBG bit 256: the level-by-level order).  Plain calls keep the heaviest-first order: measured on one box,
+// (scatter_order 1, MSDA_SCATTER_DBG kSdbgLevelOrder: the level-by-level order).  Plain calls keep the heaviest-first order: measured on one box,
 // image order / level order: 800x1333 T = 6 one clip 2.76 / 2.86 ms, 360x640 T = 6 0.54 / 0.55, but the single-frame
 // encoder call of BASELINE configs[1] (N = 8, bf16) 0.92 / 0.63 and the SwinL one (N = 6, fp16) 0.23 / 0.17 -- with
 // `clip` outermost the batch is 8 serial tails.
@@ -414,8 +414,8 @@ ScatterPlan plan_scatter(int dtype, const Shape &s, const Params &p, const Knobs
     // clip of the 360x640 decoder call replayed from a graph, 288 items for 256 workgroups: 0.124 -> 0.130 ms at five slots,
     // with 60 queries 0.0573 -> 0.0606; the SwinL fp16 encoder call image by image + 1.2 % (profiles/own5_ab.log, section 4b).
     // From 16 clips on (3072 items) five slots win; between 2 and 16 clips nothing was measured.  Without the host copy of the
-    // shapes the items cannot be counted and the call keeps the larger bands.  (MSDA_SCATTER_DBG bit 8192: never -- tests)
-    if (owner && pix > kOwnPix && p.shapes_host && (k.scatter_dbg & 8192) == 0) {
+    // shapes the items cannot be counted and the call keeps the larger bands.  (MSDA_SCATTER_DBG kSdbgNoFourSlotRule: never -- tests)
+    if (owner && pix > kOwnPix && p.shapes_host && (k.scatter_dbg & kSdbgNoFourSlotRule) == 0) {
         long long bands = 0;
         for (int l = 0; l < sc.l0; ++l) {
             const long long nb = own_band_count<long long>(p.shapes_host[2 * l], p.shapes_host[2 * l + 1], pix);
@@ -444,9 +444,9 @@ ScatterPlan plan_scatter(int dtype, const Shape &s, const Params &p, const Knobs
                                      : (k.bwd_cull != 0 && !(k.bwd_cull != 2 && owner_scatter_applicable(p, s.esz, k)));
     if (!owner) return sc;
     // When every level's row fits a band (the host copy of the shapes says so) no pixel takes the float-atomic branch, and the
-    // zero-fill of the pixels outside the levels -- normally none -- rides in the scatter kernel's prologue (bit 512) instead of
+    // zero-fill of the pixels outside the levels -- normally none -- rides in the scatter kernel's prologue (launch flag kOwnFusedZero) instead of
     // a launch of its own in front of it: one dependent dispatch less per backward (one clip from a HIP graph 0.127 -> see r04 logs)
-    sc.fused_zero = p.shapes_host != nullptr && (k.scatter_dbg & 1024) == 0;
+    sc.fused_zero = p.shapes_host != nullptr && (k.scatter_dbg & kSdbgSeparateZero) == 0;
     for (int l = 0; sc.fused_zero && l < p.L; ++l) sc.fused_zero = p.shapes_host[2 * l + 1] > 0 && own_row_fits(p.shapes_host[2 * l + 1]);
     sc.image_order = owner_image_order(p, k, sc.l0, pix);
     sc.run_owner = !(sc.mfma_tiles && k.scatter_part == 2);

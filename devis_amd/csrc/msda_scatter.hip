@@ -53,6 +53,7 @@ namespace {
 constexpr int kScatterThreads = 1024;
 constexpr int kScatterList = 3072;         // capacity of the survivor list (12 KiB of the 16 KiB LDS left by the band)
 
+// dbg: the kSdbgLdsMask bits of MSDA_SCATTER_DBG (msda_params.h), 0 in production
 template <typename T, typename TL, int G, bool DET>        // T: grad_out, TL: sampling_loc / attn_weight
 __global__ void __launch_bounds__(kScatterThreads)
 msda_bwd_value_lds_kernel(const Params p, int cap_slots, int dbg, const DetArgs det)
@@ -95,7 +96,7 @@ msda_bwd_value_lds_kernel(const Params p, int cap_slots, int dbg, const DetArgs 
     // stride leaves most CUs idle behind the unlucky ones (encoder shape, 1 clip: 2.85 -> see DESIGN).
     __shared__ long long s_item;
     // plenty of items per workgroup: a static stride balances well enough and skips the ticket traffic
-    const bool dynamic = p.workspace != nullptr && (dbg & 16) == 0 && n_items < (int64_t)16 * gridDim.x;
+    const bool dynamic = p.workspace != nullptr && (dbg & kSdbgStaticStride) == 0 && n_items < (int64_t)16 * gridDim.x;
     const int lane8 = blockIdx.x % 8;
     for (int64_t it = blockIdx.x;; it += gridDim.x) {
         int64_t item = it;
@@ -154,7 +155,7 @@ msda_bwd_value_lds_kernel(const Params p, int cap_slots, int dbg, const DetArgs 
             const int tw = lane, n_tw = p.frames * p.window;
             const bool hit = tw < n_tw && p.ftab[tw] == f;
             const u64 bal = __ballot(hit);
-            if (lane == 0) { s_src_t[0] = f; s_src_vl[0] = l; s_nsrc = (dbg & 4) ? 0 : 1 + (int)__popcll(bal); }
+            if (lane == 0) { s_src_t[0] = f; s_src_vl[0] = l; s_nsrc = (dbg & kSdbgLdsNoSources) ? 0 : 1 + (int)__popcll(bal); }
             if (hit) {
                 const int n = 1 + (int)__popcll(bal & ((1ull << lane) - 1ull)), t = tw / p.window;
                 s_src_t[n] = t; s_src_vl[n] = (tw - t * p.window) * L + l;
@@ -285,7 +286,7 @@ msda_bwd_value_lds_kernel(const Params p, int cap_slots, int dbg, const DetArgs 
             // of a corner it does own -- 4*VEC independent ds_add_f64 per lane, no exec-mask juggling.
             // Terms are the fp32 products the reference hands to atomicAdd (cuh:125-152), widened to
             // fp64 (one v_cvt_f64_f32) and summed in fp64.
-            if (dbg & 8) {          // measurement: everything but the LDS adds
+            if (dbg & kSdbgLdsNoAdds) {          // measurement: everything but the LDS adds
                 float acc = 0.f;
 #pragma unroll
                 for (int c = 0; c < VEC; ++c) acc += h.g[c];
@@ -373,7 +374,7 @@ msda_bwd_value_lds_kernel(const Params p, int cap_slots, int dbg, const DetArgs 
             // next pass's (x, y, attn) fly while this pass's hits are processed
 #pragma unroll
             for (int c = 0; c < NC; ++c) fetch(base + kPass + c * kScatterThreads + tid, cx[c], cy[c], ca[c], cq[c]);
-            if (dbg & 2) continue;
+            if (dbg & kSdbgLdsScanOnly) continue;
             // ---- merge: every round each lane offers its first unprocessed hit
 #pragma unroll 1
             for (int round = 0; round < NC; ++round) {
@@ -549,18 +550,17 @@ msda_cull_summary_kernel(const Params p)
 // integer exchange, not a float atomic).  The owners then walk their lists with plain LDS reads
 // (8 B entry + 2 x 16 B of the row per lane) and accumulate in fp32 registers: ~650 B of plain LDS traffic
 // per hit instead of 2 KiB of atomics.  Same items (clip, source frame, head, band of pixel rows of one
-// level), same per-point culling records from the gather pass, same survivor list as
-// msda_bwd_value_points_kernel; bands are sized by the owners' registers (own_band_pixels: 1280 or 1024 pixels, cut into
+// level) and same per-point culling records from the gather pass as the LDS scatter (msda_bwd_value_lds_kernel); bands are sized by the owners' registers (own_band_pixels: 1280 or 1024 pixels, cut into
 // bands of equal height by own_band_count / own_band_rows, msda_params.h; a row wider than kOwnPix is "direct") instead of by LDS.
 // The sum of a pixel's terms is an fp32 sum in list order (the reference's atomicAdd order is arbitrary too,
 // cuh:125-152); terms are the products (w_corner * attn) * grad_out[c].
 constexpr unsigned kOwnNil = 0xffffffffu;
 
-// ---- group-granular variant -------------------------------------------------------------------------------------
+// ---- the kernel: group-granular (msda_bwd_value_grp_kernel, the only owner-computes kernel) ----------------------------------
 // A chunk is kGrpChunk (row, level) GROUPS -- the <= 4 sampling points one query puts on one level of one source frame --
-// instead of 768 single points: the points of a group share their grad_out row, so the row is staged ONCE per group
-// (the owner kernel above stages it once per point: 22 M 128-byte LDS-DMA requests per launch, 3/4 of them duplicates
-// on the levels that are a single band), a chunk holds up to 4 x 512 = 2048 hits (fewer barriers and exposed latencies
+// not single points: the points of a group share their grad_out row, so the row is staged ONCE per group
+// (a per-point kernel, since removed, staged it once per point: 22 M 128-byte LDS-DMA requests per launch, 3/4 of them
+// duplicates on the levels that are a single band), a chunk holds up to 4 x 512 = 2048 hits (fewer barriers and exposed latencies
 // per hit, longer lists = better lock-step efficiency of the walk), and the survivor list holds groups (1 entry per
 // cull thread, 6 KiB instead of 19).  Thread t of pass j handles point (t & 3) of group 256 j + t / 4; a group's 16
 // entries are one 128-byte block, so the row of an entry at LDS address A is (A - entries) >> 7.
@@ -585,9 +585,10 @@ __device__ __forceinline__ int per_item(int x)
 }
 
 // SLOTS: pixels per owner quad = accumulator sets per thread (own_slots, msda_params.h); a band is kOwnQuads * SLOTS pixels.
+// flags: the launch flag kOwnFusedZero and the kSdbgOwnMask bits of MSDA_SCATTER_DBG (msda_params.h; 0 or kOwnFusedZero in production).
 template <typename T, typename TL, typename GV, bool SORTED, int SLOTS>        // SORTED: items in image order (long candidate ranges); TL: storage type of sampling_loc / attn_weight (T, or float with a 16-bit T)
 __global__ void __launch_bounds__(kOwnThreads, 4)
-msda_bwd_value_grp_kernel(const Params p, int dbg)
+msda_bwd_value_grp_kernel(const Params p, int flags)
 {
     constexpr int kBandPix = kOwnQuads * SLOTS;                 // pixels per band
     constexpr int D = 32, kRowB = D * 4;                        // bytes of one staged grad_out row (fp32)
@@ -638,7 +639,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
     for (int i = tid; i < kBandPix; i += kOwnThreads) head[i] = kOwnNil;
     __syncthreads();
     const int NB = s_first[L];
-    if (dbg & 512) {
+    if (flags & kOwnFusedZero) {
         // the zero-fill of msda_zero_unowned_kernel, dealt over this kernel's threads: pixels of `value` rows outside every level
         // (spatial_shapes that do not tile [0, S)); the host only sets the bit when no level takes the float-atomic branch, so
         // nothing else in this launch writes these pixels
@@ -687,7 +688,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
     }
     const int clips = p.groups / p.frames;
     const unsigned n_items = (unsigned)clips * (unsigned)p.frames * (unsigned)p.M * (unsigned)NB;      // (< 2^31: host)
-    const bool dynamic = p.workspace != nullptr && (dbg & 16) == 0 && n_items < 16u * gridDim.x;
+    const bool dynamic = p.workspace != nullptr && (flags & kSdbgStaticStride) == 0 && n_items < 16u * gridDim.x;
     // static stride only: does the walk of one workgroup -- (item / M) in steps of gridDim / M -- share a factor with the band count?
     // (then it meets the same few bands of every frame and prepare() rotates the bands by the (clip, frame) index)
     unsigned stride_gcd = 1u;
@@ -704,7 +705,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
         stride_gcd = a;
         if (step % nb == 0u && (step / nb) % nb == 0u) rot_div = step / nb;
     }
-    const bool rotate_bands = stride_gcd > 1u && (dbg & 4096) == 0;
+    const bool rotate_bands = stride_gcd > 1u && (flags & kSdbgNoBandRotation) == 0;
     const bool clip_major = (long long)p.Lq * (1 + p.window) <= 4096;       // see prepare()
     const int lane8 = blockIdx.x % 8;
     const int strideA = p.M * p.LA * p.PA, strideB = p.M * p.LB * p.PB;      // loc/attn elements per query
@@ -763,7 +764,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
                 // static stride: the bands of one (clip, frame) adjacent.  A workgroup walks (item / M) in steps of gridDim / M (64):
                 // with a band count that shares a factor with it (24 bands: every third band only) it would meet the same few bands
                 // of every frame, all heavy or all light (round 6: the 800x1333 pyramid without its last level 0.51 -> 0.67 ms), so
-                // THEN the bands are rotated by the (clip, frame) index (0.445 ms; MSDA_SCATTER_DBG = 4096: never).  Without a common
+                // THEN the bands are rotated by the (clip, frame) index (0.445 ms; MSDA_SCATTER_DBG kSdbgNoBandRotation: never).  Without a common
                 // factor the plain order stays: rotating it cost the same pyramid WITH its last level (25 bands) 0.516 -> 0.553 ms.
                 m = (int)(item % M);
                 unsigned rest = item / M;
@@ -812,7 +813,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
         const long long *s_src_tab = s_src_tab2[cur], *s_src_loc = s_src_loc2[cur];
         const int *s_src_q0 = s_src_q02[cur], *s_src_gmv = s_src_gmv2[cur];
         const int s_nsrc = s_nsrc2[cur];
-        if (((dbg >> 5) & 7) != 0 && l != ((dbg >> 5) & 7) - 1) {       // (measurement: MSDA_SCATTER_DBG = 32 * (level + 1): that level only)
+        if (((flags >> kSdbgOwnLevelShift) & kSdbgOwnLevelMask) != 0 && l != ((flags >> kSdbgOwnLevelShift) & kSdbgOwnLevelMask) - 1) {       // (measurement: the level field of MSDA_SCATTER_DBG = level + 1: that level only)
             if (wave == 0) prepare(it + 1u, cur ^ 1);
             __syncthreads();
             continue;
@@ -867,7 +868,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
         static_assert(kOwnChunk % (kOwnThreads / kWave) == 0 && RPWV % HPI == 0, "rows per wave");
         u32x4 raw_rows[kHalf ? RPWV / HPI : 1];
         auto stage_rows = [&](int base, int n) {
-            if (direct || (dbg & 4)) return;
+            if (direct || (flags & kSdbgOwnNoStage)) return;
             const T *go = static_cast<const T *>(p.grad_out) + m * D + per_item(lane % LPR) * (16 / (int)sizeof(T));
             // (all list entries, then all first-query rows, then the loads: read one by one inside the per-instruction branches
             // below, the two dependent LDS round trips of every instruction ran back to back)
@@ -897,7 +898,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
         };
         auto stage_rows_finish = [&](int n) {
             if constexpr (kHalf) {
-                if (direct || (dbg & 4)) return;
+                if (direct || (flags & kSdbgOwnNoStage)) return;
 #pragma unroll
                 for (int i = 0; i < RPWV / HPI; ++i) {
                     const int r0w = wave * RPWV + HPI * i;
@@ -937,7 +938,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
                                 for (int ch = 0; ch < D; ++ch) atomic_accumulate(dst + ch, wgt[c] * Store<T>::get(gr + ch));
                             }
                         }
-                } else if (!(dbg & 2)) {
+                } else if (!(flags & kSdbgOwnNoLink)) {
 #pragma unroll
                     for (int c = 0; c < 4; ++c)
                         if (own[c]) {
@@ -950,7 +951,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
         };
         // ---- owners walk their pixels' lists (references are absolute LDS addresses; the row is (A - entries) >> 7)
         auto walk = [&]() {
-            if (direct || (dbg & 1)) return;
+            if (direct || (flags & kSdbgOwnNoWalk)) return;
             // this lane's two 16-byte pieces of a row, relative to the 128-byte group of the entry's own address
             const unsigned row_k1 = lds_addr(rows) - ents_lds + (unsigned)off1, row_k2 = lds_addr(rows) - ents_lds + (unsigned)(off1 ^ 64);
 #pragma unroll
@@ -1089,7 +1090,7 @@ msda_bwd_value_grp_kernel(const Params p, int dbg)
             __syncthreads();
             listed += s_cnt[ci];
             ci = (ci + 1) % 3;
-            if (dbg & 8) listed = 0;                    // measurement: cull only
+            if (flags & kSdbgOwnCullOnly) listed = 0;                    // measurement: cull only
             // chunks are processed when the list could not take another cull batch, or at the end: an item of <= 2 batches
             // (every decoder call) is culled completely first and its chunks then run back to back, each one's point loads
             // issued under the previous one's walk
@@ -1230,13 +1231,13 @@ int scatter_lds_g(int G, const Params &p, unsigned grid, int cap_bytes, int dbg,
 }
 
 template <typename T, typename TL, typename GV, bool SORTED, int SLOTS>
-int scatter_grp(const Params &p, unsigned grid, int dbg, hipStream_t stream)
+int scatter_grp(const Params &p, unsigned grid, int flags, hipStream_t stream)
 {
     static LdsGrant granted;
     const auto kern = &msda_bwd_value_grp_kernel<T, TL, GV, SORTED, SLOTS>;
     if (const int rc = grant_lds(reinterpret_cast<const void *>(kern), (size_t)grp_lds_bytes<SLOTS>(), granted,
                                  "the group-granular owner-computes scatter kernel")) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kOwnThreads), (size_t)grp_lds_bytes<SLOTS>(), stream, p, dbg);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kOwnThreads), (size_t)grp_lds_bytes<SLOTS>(), stream, p, flags);
     if (SORTED)
         return check_launch(std::is_same<GV, float>::value ? "msda backward (owner-computes scatter kernel, group-granular, items in image order)"
                                                            : "msda backward (owner-computes scatter kernel, group-granular, items in image order, grad_value in the storage type)");
@@ -1291,7 +1292,7 @@ int launch_scatter_lds_det(int dtype, int G, const Params &p, unsigned grid, int
 }
 
 // `image_order`: the items in image order (the dispatcher's rule, msda_plan.hip owner_image_order), else heaviest first
-int launch_scatter_grp(int dtype, bool storage_typed, const Params &p, unsigned grid, int dbg, bool image_order, hipStream_t stream)
+int launch_scatter_grp(int dtype, bool storage_typed, const Params &p, unsigned grid, int flags, bool image_order, hipStream_t stream)
 {
     return dispatch_types(dtype, [&](auto t, auto tl) {
         using T = typename decltype(t)::type;
@@ -1302,7 +1303,7 @@ int launch_scatter_grp(int dtype, bool storage_typed, const Params &p, unsigned 
         auto go = [&](auto gv, auto sl) {
             using GV = typename decltype(gv)::type;
             constexpr int S = decltype(sl)::value;
-            return image_order ? scatter_grp<T, TL, GV, true, S>(p, grid, dbg, stream) : scatter_grp<T, TL, GV, false, S>(p, grid, dbg, stream);
+            return image_order ? scatter_grp<T, TL, GV, true, S>(p, grid, flags, stream) : scatter_grp<T, TL, GV, false, S>(p, grid, flags, stream);
         };
         using four = std::integral_constant<int, kOwnSlots>;
         using five = std::integral_constant<int, 5>;

@@ -35,7 +35,7 @@ __device__ __forceinline__ void tile_coords(const Params &p, int &m, int &group,
     // head = blockIdx % M -> XCD affinity (see file header); tiles of one group are consecutive
     m = blockIdx.x % p.M;
     const int tile = blockIdx.x / p.M;
-    if (p.dbg & 32) m = (m + tile) % p.M;      // measurement: break the head <-> XCD affinity
+    if (p.dbg & kDbgTileRotateHeads) m = (m + tile) % p.M;      // measurement: break the head <-> XCD affinity
     const int tiles_per_group = (p.Lq + RPW - 1) / RPW;
     group = tile / tiles_per_group;
     q0 = (tile - group * tiles_per_group) * RPW;
@@ -409,7 +409,7 @@ msda_bwd_tile_kernel(const Params p)
                         for (int c = 0; c < VEC; ++c) atomic_accumulate(gvalue + o.w + c, wa3 * g[c]);
                     }
                 }
-                if (!(p.dbg & 16)) row_sum4<G>(d0, d1, d2, d3);
+                if (!(p.dbg & kDbgTileNoRowSum)) row_sum4<G>(d0, d1, d2, d3);
                 const bool mine = sub == (pp & (G - 1));
                 k0 = mine ? d0 : k0; k1 = mine ? d1 : k1; k2 = mine ? d2 : k2; k3 = mine ? d3 : k3;
                 if ((pp & (G - 1)) == G - 1 || pp == np - 1) {      // wave-uniform
@@ -437,7 +437,7 @@ msda_bwd_tile_kernel(const Params p)
             __syncthreads();
             // coalesced write-out: the chunk's 2*np grad_loc and np grad_attn elements of a row are
             // contiguous in memory; the row's G lanes write them G elements per instruction
-            if (r < rows_valid && !(p.dbg & 8)) {
+            if (r < rows_valid && !(p.dbg & kDbgTileNoWriteOut)) {
                 const int64_t idx0 = row * LP + p0;
                 const float *res = reinterpret_cast<const float *>(s_e + r * kRowSlots);
                 for (int el = sub; el < 2 * np; el += G)

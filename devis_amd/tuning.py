@@ -49,6 +49,26 @@ SCATTER_ROUTES = (("levels", {"scatter_order": 1}), ("image", {"scatter_order": 
                   ("nomfma", {"scatter_mfma": 0}), ("image+mfma", {"scatter_order": 2, "scatter_mfma": 1}))
 MARGIN = 0.95           # an alternative is pinned only when it takes less than this fraction of the rules' time (3 % pins flipped between two audits)
 
+# The bits of MSDA_SCATTER_DBG and MSDA_DBG (read only with MSDA_ENABLE_HOOKS=1) under the names and values of THE table,
+# csrc/msda_params.h, which says who reads each bit (tests/test_plan_cpu.py compares the two).  ROUTE bits keep the results;
+# ABLATION bits are for timing and give wrong results.  Where the owner-computes and the LDS scatter kernel read one bit
+# differently it has two names.
+kSdbgStaticStride, kSdbgLevelOrder, kSdbgSeparateZero, kSdbgImageOrder, kSdbgNoBandRotation, kSdbgNoFourSlotRule = 16, 256, 1024, 2048, 4096, 8192
+kSdbgOrderMask = kSdbgLevelOrder | kSdbgImageOrder
+kSdbgRouteMask = kSdbgStaticStride | kSdbgOrderMask | kSdbgSeparateZero | kSdbgNoBandRotation | kSdbgNoFourSlotRule
+kSdbgOwnNoWalk, kSdbgOwnNoLink, kSdbgOwnNoStage, kSdbgOwnCullOnly = 1, 2, 4, 8
+kSdbgLdsScanOnly, kSdbgLdsNoSources, kSdbgLdsNoAdds = 2, 4, 8
+kSdbgOwnLevelShift, kSdbgOwnLevelMask = 5, 7            # field (word >> 5) & 7 = level + 1: that level only
+kSdbgOwnLevelField = kSdbgOwnLevelMask << kSdbgOwnLevelShift
+kSdbgAblationMask = kSdbgOwnNoWalk | kSdbgOwnNoLink | kSdbgOwnNoStage | kSdbgOwnCullOnly | kSdbgOwnLevelField
+kSdbgOwnMask = kSdbgStaticStride | kSdbgNoBandRotation | kSdbgAblationMask
+kSdbgLdsMask = kSdbgStaticStride | kSdbgLdsScanOnly | kSdbgLdsNoSources | kSdbgLdsNoAdds
+kOwnFusedZero = 512                                     # the owner kernel's launch flag: never read from the environment
+kDbgTileRotateHeads, kDbgNarrowStores, kDbgNarrowLoads = 32, 64, 128
+kDbgRouteMask = kDbgTileRotateHeads | kDbgNarrowStores | kDbgNarrowLoads
+kDbgTileNoWriteOut, kDbgTileNoRowSum = 8, 16
+kDbgAblationMask = kDbgTileNoWriteOut | kDbgTileNoRowSum
+
 
 class _Knobs:
     """Route knobs through the environment (MSDA_ENABLE_HOOKS=1 + msda_reload_knobs), restored on exit."""
@@ -67,7 +87,7 @@ class _Knobs:
         os.environ["MSDA_ENABLE_HOOKS"] = "1"
         for name, v in (settings or {}).items():
             if name == "scatter_order":
-                os.environ["MSDA_SCATTER_DBG"] = str({1: 256, 2: 2048}[int(v)])
+                os.environ["MSDA_SCATTER_DBG"] = str({1: kSdbgLevelOrder, 2: kSdbgImageOrder}[int(v)])
             else:
                 os.environ[_KNOB_ENV[name]] = str(int(v))
         if phases is not None:

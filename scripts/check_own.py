@@ -1,5 +1,6 @@
-"""GPU probe: scatter-pass timing for kernel variants (MSDA_SCATTER_DBG bits 8..9 select the owner-computes variant;
-MSDA_SCATTER_OWN=0 is the LDS-atomic scatter)."""
+"""GPU probe: scatter-pass time of the two scatter kernels on four call shapes, and the largest difference of their grad_value:
+the LDS-atomic scatter (MSDA_SCATTER_OWN=0) against the owner-computes scatter (the default route; MSDA_SCATTER_DBG = 0, no
+measurement bit set -- the bits are listed in devis_amd/csrc/msda_params.h)."""
 import os, sys
 os.environ.setdefault("MSDA_ENABLE_HOOKS", "1")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

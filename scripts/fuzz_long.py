@@ -6,13 +6,14 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, torch
 from helpers import make_inputs, make_temporal_inputs, oracle_fwd_bwd, round_to, temporal_reference
 from devis_amd import _native
+from devis_amd.tuning import kSdbgStaticStride
 from devis_amd.functions import MSDeformAttnFunction, MSDeformAttnTemporalFunction
 DEV = "cuda:0"
 os.environ["MSDA_ENABLE_HOOKS"] = "1"
 from devis_amd import _native as _native_mod
-ROUTES = [{}, {"MSDA_SCATTER_DBG": "16"}, {"MSDA_BWD_CULL": "2"}, {"MSDA_BWD_CULL": "0"}, {"MSDA_SCATTER_LDS_KB": "6", "MSDA_SCATTER_OWN": "0"},
+ROUTES = [{}, {"MSDA_SCATTER_DBG": str(kSdbgStaticStride)}, {"MSDA_BWD_CULL": "2"}, {"MSDA_BWD_CULL": "0"}, {"MSDA_SCATTER_LDS_KB": "6", "MSDA_SCATTER_OWN": "0"},
           {"MSDA_SCATTER_OWN": "0"}, {"MSDA_FWD_RS": "1", "MSDA_BWD_RS": "1"}, {"MSDA_FWD_RS": "0", "MSDA_BWD_RS": "0"},
-          {"MSDA_FWD_RS": "1", "MSDA_BWD_RS": "1", "MSDA_SCATTER_DBG": "16"}, {"MSDA_BWD_RS": "1", "MSDA_BWD_CULL": "0"},
+          {"MSDA_FWD_RS": "1", "MSDA_BWD_RS": "1", "MSDA_SCATTER_DBG": str(kSdbgStaticStride)}, {"MSDA_BWD_RS": "1", "MSDA_BWD_CULL": "0"},
           {"MSDA_BWD_MODE": "atomic"}, {"MSDA_FWD_RS": "1", "MSDA_FWD_RS_NT": "4"},
           {"MSDA_BWD_RS": "1", "MSDA_BWD_RS_FSPLIT": "1"}, {"MSDA_BWD_RS": "1", "MSDA_BWD_RS_FSPLIT": "2", "MSDA_FWD_RS": "1", "MSDA_FWD_RS_NT": "2"},
           {"MSDA_BWD_RS": "1", "MSDA_BWD_RS_FSPLIT": "4"}, {"MSDA_BWD_RS": "1", "MSDA_BWD_RS_TPW": "2", "MSDA_BWD_RS_FSPLIT": "0"},

@@ -16,7 +16,7 @@ import torch
 
 import bench
 import scatter_ab
-from devis_amd import _native
+from devis_amd import _native, tuning
 
 bench.PYRAMIDS["S"] = scatter_ab.SWIN
 KEYS = ("MSDA_SCATTER_DBG", "MSDA_SCATTER_OWN", "MSDA_FWD_RS", "MSDA_FWD_RS_NT", "MSDA_BWD_RS", "MSDA_BWD_RS_TPW", "MSDA_BWD_RS_FSPLIT", "MSDA_FWD_WIN", "MSDA_BWD_WIN")
@@ -74,7 +74,7 @@ def main():
         cases = [c for c in cases if c[0] == "enc"]
     if len(sys.argv) > 1 and sys.argv[1] == "scatter":
         # grad_value scatter: automatic against the level-by-level item order and the static schedule
-        alts = (("level order", {"MSDA_SCATTER_DBG": 256}), ("static", {"MSDA_SCATTER_DBG": 16}))
+        alts = (("level order", {"MSDA_SCATTER_DBG": tuning.kSdbgLevelOrder}), ("static", {"MSDA_SCATTER_DBG": tuning.kSdbgStaticStride}))
         todo = [("dec", pyr, c, dt) for pyr in ("A", "S", "B") for dt in (torch.float32, torch.bfloat16) for c in ((6, 8, 10, 12) if len(sys.argv) > 2 else (1, 4, 16, 32))]
         todo += [("enc", pyr, 1, dt) for pyr in ("A", "S", "B") for dt in (torch.float32, torch.bfloat16)]
         todo += [(kind, pyr, n, dt) for pyr in ("A", "S", "B") for dt in (torch.float32, torch.bfloat16)

@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 import bench
-from devis_amd import _native
+from devis_amd import _native, tuning        # tuning: the names of the MSDA_SCATTER_DBG bits (csrc/msda_params.h)
 
 DEV = torch.device("cuda:0")
 SWIN = [(60, 96), (30, 48), (15, 24), (8, 12)]
@@ -100,8 +100,10 @@ def sweep(name):
     knobs()
     bwd()
     out = []
-    for label, dbg in (("full", 0), ("no walk", 1), ("no link", 2), ("no rows", 4), ("no walk/link/rows", 7), ("cull only", 8),
-                       ("L0", 32), ("L1", 64), ("L2", 96), ("L3", 128), ("static order", 16)):
+    level = lambda l: (l + 1) << tuning.kSdbgOwnLevelShift       # the owner kernel's level field: that level only
+    for label, dbg in (("full", 0), ("no walk", tuning.kSdbgOwnNoWalk), ("no link", tuning.kSdbgOwnNoLink), ("no rows", tuning.kSdbgOwnNoStage),
+                       ("no walk/link/rows", tuning.kSdbgOwnNoWalk | tuning.kSdbgOwnNoLink | tuning.kSdbgOwnNoStage), ("cull only", tuning.kSdbgOwnCullOnly),
+                       ("L0", level(0)), ("L1", level(1)), ("L2", level(2)), ("L3", level(3)), ("static order", tuning.kSdbgStaticStride)):
         knobs(MSDA_BWD_PHASES=2, MSDA_SCATTER_DBG=dbg)
         out.append("%s %.4f" % (label, bench._event_ms(bwd, reps)))
     knobs()
@@ -133,8 +135,8 @@ def main():
         t_g = bench._event_ms(bwd, reps)
         knobs(MSDA_BWD_PHASES=2)
         t_s = bench._event_ms(bwd, reps)
-        if name in ("encA", "encB", "cfg1", "cfg4enc"):       # the other item order (MSDA_SCATTER_DBG=256: level by level, heaviest first)
-            knobs(MSDA_BWD_PHASES=2, MSDA_SCATTER_DBG=256)
+        if name in ("encA", "encB", "cfg1", "cfg4enc"):       # the other item order (kSdbgLevelOrder: level by level, heaviest first)
+            knobs(MSDA_BWD_PHASES=2, MSDA_SCATTER_DBG=tuning.kSdbgLevelOrder)
             note += "  scatter, level-by-level item order %.4f" % bench._event_ms(bwd, reps)
         knobs()
         print("%-22s %-11s fwd %.4f  gather %.4f  scatter %.4f ms%s" % (tag, name, t_f, t_g, t_s, note), flush=True)

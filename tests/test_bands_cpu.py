@@ -17,6 +17,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from devis_amd.tuning import kSdbgImageOrder, kSdbgNoFourSlotRule        # MSDA_SCATTER_DBG bits by name (csrc/msda_params.h)
 from test_plan_cpu import CSRC, HOOKS, probe, shape      # noqa: F401  (probe: the session's planner probe, a fixture)
 
 F32, BF16, F16, BF16_LOC32, F16_LOC32 = 0, 2, 3, 4, 5        # include/msda.h, msda_dtype
@@ -169,7 +170,7 @@ def test_width_limit_of_the_fused_zero_fill_and_of_a_storage_typed_grad_value(pr
 def test_band_count_of_the_image_order(band_probe):
     """owner_image_order sorts up to 256 (level, band) pairs: a tall level beside the 45 x 80 one puts the total on both sides of
     it, which counts the 45 x 80 level's own bands -- 3 at five slots, 4 at four."""
-    env = {**HOOKS, "MSDA_SCATTER_DBG": "2048", "MSDA_SCATTER_MFMA": "0"}            # image order wherever the bands can be sorted
+    env = {**HOOKS, "MSDA_SCATTER_DBG": str(kSdbgImageOrder), "MSDA_SCATTER_MFMA": "0"}            # image order wherever the bands can be sorted
     for dtype, gv in [(F32, 0), (BF16, 1), (BF16, 0), (F16_LOC32, 0)]:
         pix = QUADS * slots(dtype, gv)
         per = pix // 80
@@ -190,10 +191,10 @@ PYR_A = [(45, 80), (23, 40), (12, 20), (6, 10)]
 def test_few_item_calls_stay_on_four_slots(band_probe):
     """plan_scatter: a call of at most two items per workgroup of the persistent grid (256 at 256 CUs), counted at five slots,
     keeps 1024-pixel bands -- its launch lasts as long as its heaviest band; larger calls take what own_slots allows.  One clip
-    of the decoder call is 6 x 8 x (3 + 1 + 1 + 1) = 288 items, two clips 576.  MSDA_SCATTER_DBG bit 8192 switches the rule off."""
+    of the decoder call is 6 x 8 x (3 + 1 + 1 + 1) = 288 items, two clips 576.  MSDA_SCATTER_DBG kSdbgNoFourSlotRule switches the rule off."""
     one, two, many, half = band_probe([(F32, 0, PYR_A, 300, 1), (F32, 0, PYR_A, 300, 2), (F32, 0, PYR_A, 300, 16), (BF16, 1, PYR_A, 300, 1)])
     assert [o["own_pix"] for o in (one, two, many, half)] == ["1024", "1280", "1280", "1024"], (one, two, many, half)
-    forced = band_probe([(F32, 0, PYR_A, 300, 1), (BF16, 1, PYR_A, 300, 1), (BF16, 0, PYR_A, 300, 16)], {**HOOKS, "MSDA_SCATTER_DBG": "8192"})
+    forced = band_probe([(F32, 0, PYR_A, 300, 1), (BF16, 1, PYR_A, 300, 1), (BF16, 0, PYR_A, 300, 16)], {**HOOKS, "MSDA_SCATTER_DBG": str(kSdbgNoFourSlotRule)})
     assert [o["own_pix"] for o in forced] == ["1280", "1280", "1024"], forced          # (four is all a float grad_value beside bf16 has)
     # the boundary: one level of 45 x 80 (3 bands at five slots), single-frame calls of c images: 24 c items against 512
     a, b = band_probe([(F32, 0, [(45, 80)], 300, 21, 1, 0), (F32, 0, [(45, 80)], 300, 22, 1, 0)])
@@ -207,7 +208,7 @@ def test_every_band_count_follows_the_chosen_size(band_probe):
     env = {**HOOKS, "MSDA_SCATTER_MFMA": "0"}
     call = (F32, 0, [(25, 42), (13, 21)], 40, 1, 2, 1)
     small = band_probe([call], env)[0]
-    forced = band_probe([call], {**env, "MSDA_SCATTER_DBG": "8192"})[0]
+    forced = band_probe([call], {**env, "MSDA_SCATTER_DBG": str(kSdbgNoFourSlotRule)})[0]
     assert (small["own_pix"], bit(small, 0), bit(small, 1)) == ("1024", 1, 0), small
     assert (forced["own_pix"], bit(forced, 0), bit(forced, 1)) == ("1280", 0, 0), forced
     for o in (small, forced):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from devis_amd.tuning import kSdbgNoFourSlotRule
 from helpers import PYR_A, make_temporal_inputs, temporal_reference
 
 pytestmark = pytest.mark.gpu
@@ -85,7 +86,7 @@ def _check(got, ref, tol, gv_tol=None):
 def owner_only(monkeypatch):
     monkeypatch.setenv("MSDA_SCATTER_MFMA", "0")          # every level is the owner kernel's
     # ... with as many slots as its instantiation takes: these calls are a few dozen items, which the planner would keep on four
-    monkeypatch.setenv("MSDA_SCATTER_DBG", "8192")
+    monkeypatch.setenv("MSDA_SCATTER_DBG", str(kSdbgNoFourSlotRule))
 
 
 @pytest.fixture()

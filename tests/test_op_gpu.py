@@ -10,12 +10,14 @@ import pytest
 import torch
 
 from conftest import OP_FIXTURES, golden
+from devis_amd.tuning import kSdbgNoBandRotation, kSdbgNoFourSlotRule, kSdbgSeparateZero, kSdbgStaticStride
 from helpers import (PYR_A, localise, make_inputs, make_temporal_inputs, oracle_fwd_bwd, round_to,
                      temporal_reference)
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
+STATIC = str(kSdbgStaticStride)        # MSDA_SCATTER_DBG: static item stride
 
 
 def _run_op(d, dtype, step=64):
@@ -273,15 +275,21 @@ def test_full_size_properties_cfg3():
 @pytest.mark.parametrize("env", [{"MSDA_BWD_MODE": "atomic"},            # one-kernel backward, global float atomics
                                  {"MSDA_SCATTER_LDS_KB": "1"},           # no level row fits LDS -> "direct" branch
                                  {"MSDA_SCATTER_LDS_KB": "8"},           # many thin bands, straddling points
-                                 {"MSDA_SCATTER_DBG": "16"},             # static item order: the software pipeline
-                                 {"MSDA_SCATTER_DBG": "16", "MSDA_SCATTER_LDS_KB": "8"},
+                                 {"MSDA_SCATTER_DBG": STATIC},           # static item order: the software pipeline
+                                 {"MSDA_SCATTER_DBG": STATIC, "MSDA_SCATTER_LDS_KB": "8"},
                                  {"MSDA_BWD_CULL": "2"},                 # interval culling records (legacy scatter)
-                                 {"MSDA_BWD_CULL": "2", "MSDA_SCATTER_DBG": "16"},
+                                 {"MSDA_BWD_CULL": "2", "MSDA_SCATTER_DBG": STATIC},
                                  {"MSDA_BWD_CULL": "0"},                 # no culling table at all
                                  {"MSDA_SCATTER_OWN": "0"},             # LDS-atomic scatter instead of owner-computes
-                                 {"MSDA_SCATTER_OWN": "0", "MSDA_SCATTER_DBG": "16"},
+                                 {"MSDA_SCATTER_OWN": "0", "MSDA_SCATTER_DBG": STATIC},
                                  {"MSDA_FWD_RS": "1", "MSDA_BWD_RS": "1"},                       # resident-slab gather pass on a tiny shape
-                                 {"MSDA_FWD_RS": "1", "MSDA_BWD_RS": "1", "MSDA_SCATTER_DBG": "16"}])
+                                 {"MSDA_FWD_RS": "1", "MSDA_BWD_RS": "1", "MSDA_SCATTER_DBG": STATIC},
+                                 # the other route bits of MSDA_SCATTER_DBG (csrc/msda_params.h: a route bit keeps the results).  The
+                                 # temporal case below has two one-band levels and a static stride that shares a factor with them: its
+                                 # bands rotate under the static order alone and stay put with kSdbgNoBandRotation added
+                                 {"MSDA_SCATTER_DBG": str(kSdbgStaticStride | kSdbgNoBandRotation)},
+                                 {"MSDA_SCATTER_DBG": str(kSdbgSeparateZero)},       # the zero-fill as a launch of its own
+                                 {"MSDA_SCATTER_DBG": str(kSdbgNoFourSlotRule)}])    # five pixels per owner quad on a few-item call
 def test_backward_alternate_routes(env, monkeypatch):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -296,6 +304,14 @@ def test_backward_alternate_routes(env, monkeypatch):
     got = _run_temporal(dt, torch.float32)
     for a, b in zip(got, ref):
         assert _maxabs(a, b) <= 2e-5 * max(1.0, np.abs(b).max())
+    if env == {"MSDA_SCATTER_DBG": str(kSdbgSeparateZero)}:
+        # the bit is what it is named after: the route names the zero-fill launch with it and not without it
+        t = [torch.from_numpy(dt[k]).to(DEV) for k in ("value", "shapes", "lsi", "ftab", "loc_c", "aw_c", "loc_t", "aw_t", "grad_out")]
+        with_bit = _direct_temporal_backward_route(*t, 1)
+        monkeypatch.delenv("MSDA_SCATTER_DBG")
+        without = _direct_temporal_backward_route(*t, 1)
+        assert "owner-computes" in with_bit and "zero-fill of pixels outside the bands" in with_bit, with_bit
+        assert "owner-computes" in without and "zero-fill" not in without, without
 
 
 def test_backward_without_workspace_static_schedule():
@@ -648,7 +664,7 @@ def test_head_major_value_layout(route, monkeypatch):
         assert _maxabs(a, b) <= 2e-5 * max(1.0, np.abs(b).max())
 
 
-@pytest.mark.parametrize("env", [{}, {"MSDA_SCATTER_DBG": "16"}, {"MSDA_BWD_CULL": "2"}])
+@pytest.mark.parametrize("env", [{}, {"MSDA_SCATTER_DBG": STATIC}, {"MSDA_BWD_CULL": "2"}])
 def test_scatter_survivor_list_overflow(env, monkeypatch):
     """More surviving points per cull batch than the survivor list holds (dense single-band levels, long
     candidate ranges): the prefix-scan-and-retry path, in dynamic and static item order."""

@@ -200,3 +200,70 @@ def test_scatter_dbg_splits_into_order_and_debug_bits(probe, text, order, dbg):
     assert (int(k["knob_scatter_order"]), int(k["knob_scatter_dbg"])) == (order, dbg), k
     off = probe([shape(shapes=TINY)], {"MSDA_SCATTER_DBG": text})[0]           # without MSDA_ENABLE_HOOKS=1: not read
     assert (off["knob_scatter_order"], off["knob_scatter_dbg"]) == ("0", "0"), off
+
+
+# ---- 4. the table of the measurement bits (csrc/msda_params.h) and its Python twin (devis_amd/tuning.py) ----------------------
+
+def _header_bits():
+    """{name: value} of the header's kSdbg* / kDbg* constants and kOwnFusedZero, read as text in file order: a value is a number
+    or an expression over the names before it (| & ~ << and parentheses mean the same in Python)."""
+    import re
+    with open(os.path.join(CSRC, "msda_params.h")) as f:
+        text = f.read()
+    bits = {}
+    for decl in re.findall(r"^constexpr int ((?:kSdbg|kDbg|kOwnFusedZero)[^;]*);", text, re.M):
+        for item in decl.split(","):           # (constexpr int a = 1, b = 2;)
+            name, expr = (s.strip() for s in item.split("="))
+            assert re.fullmatch(r"[\w\s|&~()<]+", expr), item
+            bits[name] = eval(expr, {"__builtins__": {}}, dict(bits))
+    return bits
+
+
+def test_bit_names_of_the_tuning_module_are_the_headers():
+    """Both directions: every constant of the header's table is in devis_amd/tuning.py with the same value, and the module names
+    no bit the header does not."""
+    from devis_amd import tuning
+    header = _header_bits()
+    assert len(header) >= 25 and header["kSdbgStaticStride"] == 16 and header["kOwnFusedZero"] == 512, header
+    module = {n: v for n, v in vars(tuning).items() if n.startswith(("kSdbg", "kDbg", "kOwnFusedZero"))}
+    assert module == header, (sorted(set(module) ^ set(header)), {n: (module[n], header[n]) for n in set(module) & set(header) if module[n] != header[n]})
+
+
+def test_bit_groups_are_consistent():
+    """A bit of MSDA_SCATTER_DBG is a route bit or an ablation bit, never both; the two masks (the order bits are route bits) cover
+    every named bit; the launch flag is no environment bit; the owner kernel is passed no bit only the host reads."""
+    b = _header_bits()
+    masks = ("kSdbgRouteMask", "kSdbgAblationMask", "kSdbgOrderMask", "kSdbgOwnMask", "kSdbgLdsMask", "kSdbgOwnLevelShift", "kSdbgOwnLevelMask")
+    named = 0
+    for name, v in b.items():
+        if name.startswith("kSdbg") and name not in masks:
+            named |= v
+    route, ablation, order = b["kSdbgRouteMask"], b["kSdbgAblationMask"], b["kSdbgOrderMask"]
+    assert route & ablation == 0
+    assert route | ablation | order == named and named == 1 | 2 | 4 | 8 | 16 | 224 | 256 | 1024 | 2048 | 4096 | 8192, (route, ablation, named)
+    assert order == 256 | 2048 and b["kSdbgOwnLevelField"] == b["kSdbgOwnLevelMask"] << b["kSdbgOwnLevelShift"] == 224
+    assert b["kOwnFusedZero"] == 512 and b["kOwnFusedZero"] & (route | ablation | order) == 0
+    host_only = b["kSdbgSeparateZero"] | b["kSdbgNoFourSlotRule"]
+    assert host_only == 1024 | 8192 and b["kSdbgOwnMask"] & (host_only | order | b["kOwnFusedZero"]) == 0
+    assert b["kSdbgOwnMask"] == 255 | 4096 and b["kSdbgLdsMask"] == 2 | 4 | 8 | 16          # what each kernel tests, by value
+    assert b["kSdbgLdsMask"] & (host_only | order | b["kOwnFusedZero"]) == 0
+    # MSDA_DBG
+    assert b["kDbgRouteMask"] & b["kDbgAblationMask"] == 0
+    assert (b["kDbgRouteMask"], b["kDbgAblationMask"]) == (32 | 64 | 128, 8 | 16)
+    assert b["kDbgRouteMask"] | b["kDbgAblationMask"] == sum(v for n, v in b.items() if n.startswith("kDbg") and not n.endswith("Mask"))
+
+
+def test_no_bare_literal_tests_a_debug_word():
+    """The project's own source, as text: no `dbg` / `flags` / `scatter_dbg` is tested against a number (& or >>, then a digit)
+    in csrc/msda_*.hip and msda_*.h -- every test names its bit."""
+    import glob
+    import re
+    files = sorted(glob.glob(os.path.join(CSRC, "msda_*.hip")) + glob.glob(os.path.join(CSRC, "msda_*.h")))
+    assert len(files) >= 14, files
+    pat = re.compile(r"(?:dbg|flags)\s*(?:&|>>)\s*\(?\s*~?\s*\d")
+    hits = []
+    for path in files:
+        with open(path) as f:
+            hits += ["%s:%d: %s" % (os.path.basename(path), i, ln.strip()) for i, ln in enumerate(f, 1) if pat.search(ln)]
+    assert not hits, "\n".join(hits)
+    assert pat.search("if (dbg & 16)") and pat.search("(k.scatter_dbg & (511 | 4096))") and pat.search("(flags >> 5) & 7")
