@@ -337,3 +337,193 @@ def unpatch_tracker(tracker_module, matcher_module, previous):
     matcher_module.HungarianInferenceMatcher.compute_frame_average_iou_cost = previous["compute_frame_average_iou_cost"]
     if "get_formatted_result" in previous:          # (patched with gpu_binary_iou=True)
         tracker_module.Track.get_formatted_result = previous["get_formatted_result"]
+
+
+# ---- the criterion: matching and box losses (include/boxmatch.h) ---------------------------------------------------------
+
+def _solver():
+    from scipy.optimize import linear_sum_assignment
+    return linear_sum_assignment
+
+
+def _like_predictions(boxes, dtype):
+    """Target boxes as :func:`devis_amd.match_cost` / :func:`devis_amd.box_losses` take them beside predictions of ``dtype``:
+    as they are when they have that dtype (or float32 beside a 16-bit one), else converted."""
+    if boxes.dtype == dtype or (boxes.dtype == torch.float32 and dtype in (torch.bfloat16, torch.float16)):
+        return boxes
+    return boxes.to(dtype)
+
+
+def _costs_on_host(matcher, logits, boxes, tgt_labels, tgt_boxes, l1):
+    """One :func:`devis_amd.match_cost` call and ONE device-to-host transfer that carries the cost and the status: the
+    host's [L, R, T] cost.  Raises what the reference's indexing and asserts raise."""
+    from . import ops
+    cost, status = ops.match_cost(logits, boxes.to(logits.dtype), tgt_labels.long(), _like_predictions(tgt_boxes, logits.dtype),
+                                  cost_class=matcher.cost_class, cost_bbox=matcher.cost_bbox, cost_giou=matcher.cost_giou,
+                                  l1=l1, alpha=matcher.focal_alpha)
+    packed = torch.cat([cost.reshape(-1), status.to(cost.dtype)]).cpu()        # the one synchronising transfer
+    bad_pred, bad_tgt, bad_label = (int(v) for v in packed[cost.numel():])
+    if bad_label:
+        raise IndexError("%d target label(s) outside [0, %d)" % (bad_label, logits.shape[-1]))
+    if bad_pred or bad_tgt:           # (the reference's asserts in multi_giou / generalized_box_iou)
+        raise AssertionError("%d prediction and %d target box(es) with x1 < x0 or y1 < y0" % (bad_pred, bad_tgt))
+    return packed[:cost.numel()].reshape(cost.shape).numpy()
+
+
+def _on_device_of(index, like):
+    """A host index tensor on ``like``'s device without a synchronising copy."""
+    if like.device.type == "cpu":
+        return index
+    return index.pin_memory().to(like.device, non_blocking=True)
+
+
+def _devis_indices(matcher, dicts, targets):
+    """``DeVISHungarianMatcher.forward`` for every dict of ``dicts`` (one cost call for all of them): per dict the
+    reference's return value -- a list with the triple of batch element 0."""
+    F, Q = matcher.num_frames, matcher.num_out
+    first = dicts[0]["pred_logits"]
+    if first.shape[0] == 0:                 # (the reference's loop does not run: it returns None)
+        return [None] * len(dicts)
+    tgt_ids, tgt_bbox, tgt_valid = targets[0]["labels"], targets[0]["boxes"], targets[0]["valid"]
+    num_tgt = len(tgt_ids) // F
+    frames = torch.arange(F)
+    if num_tgt == 0:
+        out = []
+        for d in dicts:
+            base = frames.long().to(d["pred_logits"].device)
+            out.append([(base * Q, base, torch.zeros(F, device=d["pred_logits"].device, dtype=torch.bool))])
+        return out
+    C = first.shape[-1]
+    if len(dicts) == 1:
+        logits, boxes = first[0][None], dicts[0]["pred_boxes"][0][None]
+    else:
+        logits = torch.stack([d["pred_logits"][0] for d in dicts])
+        boxes = torch.stack([d["pred_boxes"][0] for d in dicts])
+    cost = _costs_on_host(matcher, logits.reshape(len(dicts), F, Q, C), boxes.reshape(len(dicts), F, Q, 4),
+                          tgt_ids.reshape(num_tgt, F), tgt_bbox.reshape(num_tgt, F, 4),
+                          "sum" if matcher.use_l1_distance_sum else "mean")
+    valid = tgt_valid.reshape(num_tgt, F)
+    solve, out = _solver(), []
+    for c in cost:
+        out_i, tgt_i = (torch.as_tensor(v, dtype=torch.int64) for v in solve(c))
+        index_i = (frames[None] * Q + out_i[:, None]).reshape(-1)
+        index_j = (frames[None] + tgt_i[:, None] * F).reshape(-1)
+        index_valid = valid[_on_device_of(tgt_i, valid)].reshape(-1).type(torch.bool)
+        out.append([(index_i, index_j, index_valid)])
+    return out
+
+
+def _image_indices(matcher, dicts, targets):
+    """``HungarianMatcher.forward`` for every dict of ``dicts`` (one cost call for all of them)."""
+    first = dicts[0]["pred_logits"]
+    B, Q, C = first.shape
+    if len(dicts) == 1:
+        logits, boxes = first[None], dicts[0]["pred_boxes"][None]
+    else:
+        logits, boxes = torch.stack([d["pred_logits"] for d in dicts]), torch.stack([d["pred_boxes"] for d in dicts])
+    tgt_ids = torch.cat([v["labels"] for v in targets])
+    tgt_bbox = torch.cat([v["boxes"] for v in targets])
+    cost = _costs_on_host(matcher, logits.reshape(len(dicts), 1, B * Q, C), boxes.reshape(len(dicts), 1, B * Q, 4),
+                          tgt_ids.reshape(-1, 1), tgt_bbox.reshape(-1, 1, 4), "sum")
+    sizes = [len(v["boxes"]) for v in targets]
+    starts = [sum(sizes[:i]) for i in range(len(sizes))]
+    solve, out = _solver(), []
+    for c in cost:
+        c = c.reshape(B, Q, c.shape[-1])
+        pairs = [solve(c[i, :, s:s + n]) for i, (s, n) in enumerate(zip(starts, sizes))]
+        out.append([(torch.as_tensor(i, dtype=torch.int64), torch.as_tensor(j, dtype=torch.int64)) for i, j in pairs])
+    return out
+
+
+def make_matcher_forward(previous, indices_of):
+    """A ``forward`` of a matcher class on :func:`devis_amd.match_cost`; ``previous`` is what it replaces (and what runs with
+    ``focal_loss=False``)."""
+    @torch.no_grad()
+    def forward(self, outputs, targets):
+        if not self.focal_loss:
+            return previous(self, outputs, targets)
+        return indices_of(self, [outputs], targets)[0]
+    forward.indices_of = indices_of
+    return forward
+
+
+def loss_boxes(self, outputs, targets, indices, num_boxes):
+    """A drop-in for the reference's ``SetCriterion.loss_boxes`` (``self`` is the criterion) on :func:`devis_amd.box_losses`:
+    the same choice of boxes -- image matchings ``(src, tgt)`` and DeVIS's ``(src, tgt, mask)`` ones, masked when the first
+    clip's mask selects nothing -- then one operator call instead of ``l1_loss`` and the diagonal of an N x N GIoU matrix.
+    The reference's two degenerate-box asserts (a synchronisation each) are not reproduced.  Returns
+    ``{"loss_bbox", "loss_giou"}``."""
+    from .ops import box_losses
+    assert 'pred_boxes' in outputs
+    if len(indices[0]) == 3:
+        if not torch.any(indices[0][2]):
+            target_boxes = torch.cat([t['boxes'][i[mask]] for t, (_, i, mask) in zip(targets, indices)], dim=0)
+            idx = self._get_src_permutation_masked_idx(indices)
+        else:
+            target_boxes = torch.cat([t['boxes'][i] for t, (_, i, _) in zip(targets, indices)], dim=0)
+            idx = self._get_src_permutation_idx(indices, True)
+    else:
+        target_boxes = torch.cat([t['boxes'][i] for t, (_, i) in zip(targets, indices)], dim=0)
+        idx = self._get_src_permutation_idx(indices)
+    src_boxes = outputs['pred_boxes'][idx]
+    return box_losses(src_boxes, _like_predictions(target_boxes, src_boxes.dtype), num_boxes)
+
+
+def make_criterion_forward(previous, matcher_forwards):
+    """``SetCriterion.forward`` with the matchings of the top-level dict and of every aux dict made by ONE cost call, one
+    transfer and one assignment per dict (``patch_criterion(batch_aux=True)``): the replaced ``forward`` gets shallow copies
+    of the dicts that carry ``"indices"``, which it honours.  Anything the patched matchers do not cover passes straight
+    through."""
+    def forward(self, outputs, targets):
+        patched = matcher_forwards.get(type(self.matcher))
+        aux = outputs.get("aux_outputs", ())
+        pending = [d for d in (outputs, *aux) if "indices" not in d]
+        shapes = {(tuple(d["pred_logits"].shape), tuple(d["pred_boxes"].shape), d["pred_logits"].dtype) for d in pending}
+        if (patched is None or type(self.matcher).forward is not patched or not self.matcher.focal_loss or len(pending) < 2
+                or len(shapes) != 1):
+            return previous(self, outputs, targets)
+        with torch.no_grad():
+            found = iter(patched.indices_of(self.matcher, [{k: v for k, v in d.items() if k != "aux_outputs"} for d in pending],
+                                            targets))
+        with_indices = lambda d: d if "indices" in d else dict(d, indices=next(found))      # noqa: E731
+        top = with_indices(outputs)
+        if "aux_outputs" in outputs:
+            top = dict(top, aux_outputs=[with_indices(d) for d in aux])
+        return previous(self, top, targets)
+    return forward
+
+
+def patch_criterion(criterion_module, matcher_module, *, batch_aux=False):
+    """Opt-in: make the reference's criterion and matchers (``src.models.criterion``, ``src.models.matcher``) run on
+    :func:`devis_amd.match_cost` and :func:`devis_amd.box_losses`.  ``DeVISHungarianMatcher.forward`` and
+    ``HungarianMatcher.forward`` become one cost call, one device-to-host transfer (cost and status together),
+    ``scipy.optimize.linear_sum_assignment`` and index tensors built without a loop over the matches; everything the caller
+    sees is the reference's -- values, dtypes, devices, the DeVIS matcher's return after batch element 0 and its triple for a
+    clip without targets (no launch).  A degenerate box raises AssertionError and a label outside the classes IndexError,
+    from the status.  With ``focal_loss=False`` the replaced method runs.  ``SetCriterion.loss_boxes`` becomes
+    :func:`loss_boxes`.  ``SetCriterion.loss_masks`` is not touched (:func:`patch_mask_losses`).
+
+    ``batch_aux=True`` also wraps ``SetCriterion.forward`` (:func:`make_criterion_forward`): the decoder layers' matchings
+    share one cost call and one transfer.  The caller's dicts are not mutated.
+
+    Takes effect at once, also for objects that already exist.  Returns what was replaced (to undo the patch;
+    :func:`unpatch_criterion`).  The other patches are separate choices."""
+    crit, devis, image = criterion_module.SetCriterion, matcher_module.DeVISHungarianMatcher, matcher_module.HungarianMatcher
+    previous = {"loss_boxes": crit.loss_boxes, "devis_forward": devis.forward, "image_forward": image.forward}
+    if batch_aux:
+        previous["criterion_forward"] = crit.forward
+    crit.loss_boxes = loss_boxes
+    devis.forward = make_matcher_forward(previous["devis_forward"], _devis_indices)
+    image.forward = make_matcher_forward(previous["image_forward"], _image_indices)
+    if batch_aux:
+        crit.forward = make_criterion_forward(previous["criterion_forward"], {devis: devis.forward, image: image.forward})
+    return previous
+
+
+def unpatch_criterion(criterion_module, matcher_module, previous):
+    """Undo :func:`patch_criterion` (tests)."""
+    criterion_module.SetCriterion.loss_boxes = previous["loss_boxes"]
+    matcher_module.DeVISHungarianMatcher.forward = previous["devis_forward"]
+    matcher_module.HungarianMatcher.forward = previous["image_forward"]
+    if "criterion_forward" in previous:          # (patched with batch_aux=True)
+        criterion_module.SetCriterion.forward = previous["criterion_forward"]

@@ -35,6 +35,10 @@ through the C ABI, the same numbers -- and whose fake implementation gives shape
                                include/maskbiou.h) -> int32 (inter [Na, Nb, F], area_a [Na, F], area_b [Nb, F])
 ``mask_binary_iou``            the binary mask IoU matrix made of them (:func:`mask_binary_iou`) -> float64 [Na, Nb]; both
                                are inference operators
+``match_cost``                 the Hungarian matchers' cost matrix (:func:`match_cost`; include/boxmatch.h) -> (cost
+                               [L, R, T], status int32 [3]); no autograd formula
+``box_loss_terms``             the box losses of matched pairs (:func:`box_loss_terms`) -> (l1 [N], giou [N]);
+                               ``box_loss_terms_backward`` computes grad_src
 =============================  ==========================================================================================
 
 Everything that reads the host or keeps Python state -- the ``spatial_shapes`` host hint, the frame-table cache, the
@@ -55,6 +59,7 @@ from torch import Tensor
 
 from . import _native
 from .functions import attention_maps as _A
+from .functions import box_matching as _X
 from .functions import deform_conv as _D
 from .functions import mask_binary_iou as _B
 from .functions import mask_head_stage as _S
@@ -942,3 +947,112 @@ def mask_binary_iou(a, b, size, *, reduce="volume"):
         return mask_binary_iou_op(a, b, size, reduce)
     with torch.no_grad():
         return _B._binary_iou(a, b, size, reduce)
+
+
+# ---- the criterion's matching cost and box losses (include/boxmatch.h) ----------------------------------------------------
+
+@_op("match_cost")
+def match_cost_op(logits: Tensor, boxes: Tensor, tgt_labels: Tensor, tgt_boxes: Tensor, cost_class: float, cost_bbox: float,
+                  cost_giou: float, l1: str, alpha: float) -> tuple[Tensor, Tensor]:
+    """``match_cost`` with every argument given: (cost [L, R, T], status int32 [3])."""
+    return _X._match_cost(logits, boxes, tgt_labels, tgt_boxes, cost_class, cost_bbox, cost_giou, l1, alpha)
+
+
+@match_cost_op.register_fake
+def _(logits, boxes, tgt_labels, tgt_boxes, cost_class, cost_bbox, cost_giou, l1, alpha):
+    L, _F_, R, T = _X.check_match(logits, boxes, tgt_labels, tgt_boxes)[:4]
+    _X.check_l1(l1)
+    return _empty(logits, (L, R, T), _native.acc_dtype(logits.dtype)), _empty(logits, (3,), torch.int32)
+
+
+def match_cost(logits, boxes, tgt_labels, tgt_boxes, *, cost_class=1.0, cost_bbox=1.0, cost_giou=1.0, l1="mean", alpha=0.25):
+    """The cost matrix DeVIS's Hungarian matchers hand to the assignment solver (``DeVISHungarianMatcher.forward``,
+    ``HungarianMatcher.forward`` with ``focal_loss``) on the HIP kernel of include/boxmatch.h, for ``L`` independent problems
+    of ``R`` rows and ``T`` targets over ``F`` frames::
+
+        cost[l, r, t] = cost_class * mean_f cls(logits[l, f, r, tgt_labels[t, f]])
+                      + cost_bbox  * L1(boxes[l, :, r], tgt_boxes[t])
+                      + cost_giou  * (-mean_f GIoU(boxes[l, f, r], tgt_boxes[t, f]))
+        cls(x) = alpha * (1-p)^2 * (-log(p + 1e-8)) - (1-alpha) * p^2 * (-log(1 - p + 1e-8)),  p = sigmoid(x)
+
+    ``logits`` [L, F, R, C] and ``boxes`` [L, F, R, 4] (cxcywh) of one dtype (f32 / f64 / bf16 / f16), ``tgt_labels`` int64
+    [T, F], ``tgt_boxes`` [T, F, 4] in that dtype or float32 beside a 16-bit one.  ``l1`` is ``"mean"`` (the mean over frames
+    and coordinates of ``|box - tgt|``) or ``"sum"`` (the mean over frames of the sum over coordinates: ``cdist(p=1)``,
+    DeVIS's ``USE_SUM_L1_DISTANCE``).  GIoU is the reference's ``generalized_box_iou`` with its ``1e-6`` terms.
+
+    Returns ``(cost [L, R, T], status int32 [3])``, ``cost`` in float32 (float64 for float64 inputs).  ``status`` counts,
+    without a synchronisation, what the reference asserts on: [0] prediction boxes and [1] target boxes with ``x1 < x0`` or
+    ``y1 < y0``, [2] labels outside ``[0, C)`` -- such a label is never used as an index, and its entries are NaN.  A NaN
+    input gives NaN in the entries that read it and nowhere else.  No gradient: an input that requires one while gradients
+    are recorded raises.  GPU tensors only.  One launch, no workspace; an entry has the same bits alone and in any larger
+    call."""
+    l1 = _X.check_l1(l1)
+    _I.check_no_grad("match_cost", [("logits", logits), ("boxes", boxes), ("tgt_boxes", tgt_boxes)])
+    args = (float(cost_class), float(cost_bbox), float(cost_giou), l1, float(alpha))
+    if torch.compiler.is_compiling():
+        return match_cost_op(logits, boxes, tgt_labels, tgt_boxes, *args)
+    with torch.no_grad():
+        return _X._match_cost(logits, boxes, tgt_labels, tgt_boxes, *args)
+
+
+@_op("box_loss_terms")
+def box_loss_terms_op(src: Tensor, target: Tensor) -> tuple[Tensor, Tensor]:
+    """``box_loss_terms`` as an op: (l1 [N], giou [N])."""
+    return _X._forward(src, target)
+
+
+@box_loss_terms_op.register_fake
+def _(src, target):
+    N = _X.check_pairs(src, target)[0]
+    acc = _native.acc_dtype(src.dtype)
+    return _empty(src, (N,), acc), _empty(src, (N,), acc)
+
+
+@_op("box_loss_terms_backward")
+def box_loss_terms_backward(grad_l1: Tensor, grad_giou: Tensor, src: Tensor, target: Tensor) -> Tensor:
+    """grad_src [N, 4] in src's dtype."""
+    return _X._backward(grad_l1, grad_giou, src, target)
+
+
+@box_loss_terms_backward.register_fake
+def _(grad_l1, grad_giou, src, target):
+    return _empty(src, src.shape)
+
+
+def _setup_box_loss_terms(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _backward_box_loss_terms(ctx, grad_l1, grad_giou):
+    if not ctx.needs_input_grad[0]:
+        return None, None
+    src, target = ctx.saved_tensors
+    return box_loss_terms_backward(grad_l1, grad_giou, src, target), None
+
+
+box_loss_terms_op.register_autograd(_backward_box_loss_terms, setup_context=_setup_box_loss_terms)
+
+
+def box_loss_terms(src_boxes, target_boxes):
+    """The per-pair terms of DeVIS's box losses (``SetCriterion.loss_boxes``) on the HIP kernels of include/boxmatch.h::
+
+        l1   = F.l1_loss(src_boxes, target_boxes, reduction="none").sum(1)                                        [N]
+        giou = 1 - diag(generalized_box_iou(box_cxcywh_to_xyxy(src_boxes), box_cxcywh_to_xyxy(target_boxes)))     [N]
+
+    without the N x N matrix.  ``src_boxes`` [N, 4] cxcywh (f32 / f64 / bf16 / f16), ``target_boxes`` [N, 4] in that dtype or
+    float32 beside a 16-bit one.  The results are float32 (float64 for float64 boxes).  Only ``src_boxes`` has a gradient --
+    torch autograd's, also at the ties of ``max`` / ``min`` (halves), at ``clamp(min=0)`` (passes at 0) and at ``|0|`` (0);
+    a target that requires one raises; there is no double backward.  Forward and backward are one launch each.  The
+    reference's two degenerate-box asserts are not reproduced.  GPU tensors only.  Every result is bitwise reproducible."""
+    _X._require(not target_boxes.requires_grad, "box_loss_terms: target_boxes has no gradient (detach it)")
+    if torch.compiler.is_compiling():
+        return box_loss_terms_op(src_boxes, target_boxes)
+    return _X.BoxLossTermsFunction.apply(src_boxes, target_boxes)
+
+
+def box_losses(src_boxes, target_boxes, num_boxes):
+    """DeVIS's pair of box losses from the matched boxes: ``{"loss_bbox": sum of the L1 terms / num_boxes, "loss_giou": sum of
+    the GIoU terms / num_boxes}`` of :func:`box_loss_terms`.  ``num_boxes`` is a number or a tensor, as in the reference; the
+    two tiny reductions stay in torch."""
+    l1, giou = box_loss_terms(src_boxes, target_boxes)
+    return {"loss_bbox": l1.sum() / num_boxes, "loss_giou": giou.sum() / num_boxes}
