@@ -362,12 +362,39 @@ def _costs_on_host(matcher, logits, boxes, tgt_labels, tgt_boxes, l1):
                                   cost_class=matcher.cost_class, cost_bbox=matcher.cost_bbox, cost_giou=matcher.cost_giou,
                                   l1=l1, alpha=matcher.focal_alpha)
     packed = torch.cat([cost.reshape(-1), status.to(cost.dtype)]).cpu()        # the one synchronising transfer
-    bad_pred, bad_tgt, bad_label = (int(v) for v in packed[cost.numel():])
+    _raise_on_cost_counts(*(int(v) for v in packed[cost.numel():]), logits.shape[-1])
+    return packed[:cost.numel()].reshape(cost.shape).numpy()
+
+
+def _raise_on_cost_counts(bad_pred, bad_tgt, bad_label, num_classes=None):
+    """What the reference's indexing and asserts raise, from the counts of :func:`devis_amd.match_cost`'s status."""
     if bad_label:
-        raise IndexError("%d target label(s) outside [0, %d)" % (bad_label, logits.shape[-1]))
+        raise IndexError("%d target label(s) outside %s" % (bad_label, "the classes" if num_classes is None else "[0, %d)" % num_classes))
     if bad_pred or bad_tgt:           # (the reference's asserts in multi_giou / generalized_box_iou)
         raise AssertionError("%d prediction and %d target box(es) with x1 < x0 or y1 < y0" % (bad_pred, bad_tgt))
-    return packed[:cost.numel()].reshape(cost.shape).numpy()
+
+
+def raise_on_match_status(status, num_classes=None):
+    """The deferred check of a matching made without a transfer (``patch_criterion(gpu_assignment=True)``), and the one
+    place that reads its status: ``status`` is ``matcher.last_match_status`` -- the three counts of
+    :func:`devis_amd.match_cost` followed by the two of :func:`devis_amd.linear_assignment` -- or either operator's own
+    status (told apart by their lengths 3 and 2), or None (a matching that launched nothing).  Synchronises.  Raises
+    IndexError for labels outside the classes and AssertionError for degenerate boxes, as the host path of the patched
+    matchers does, and ValueError with scipy's messages for a cost matrix with NaN or ``-inf`` entries and for an infeasible
+    one.  ``num_classes`` only completes the IndexError's message."""
+    if status is None:
+        return
+    counts = [int(v) for v in status.reshape(-1).tolist()]
+    if len(counts) not in (2, 3, 5):
+        raise ValueError("raise_on_match_status: a status of 5, 3 or 2 counts is expected, got %d" % len(counts))
+    if len(counts) != 2:
+        _raise_on_cost_counts(*counts[:3], num_classes)
+    if len(counts) != 3:
+        invalid, infeasible = counts[-2:]
+        if invalid:
+            raise ValueError("matrix contains invalid numeric entries (%d problem(s))" % invalid)
+        if infeasible:
+            raise ValueError("cost matrix is infeasible (%d problem(s))" % infeasible)
 
 
 def _on_device_of(index, like):
@@ -411,6 +438,42 @@ def _devis_indices(matcher, dicts, targets):
         index_valid = valid[_on_device_of(tgt_i, valid)].reshape(-1).type(torch.bool)
         out.append([(index_i, index_j, index_valid)])
     return out
+
+
+def _devis_indices_on_device(matcher, dicts, targets):
+    """:func:`_devis_indices` without a transfer (``patch_criterion(gpu_assignment=True)``): :func:`devis_amd.match_cost`,
+    :func:`devis_amd.linear_assignment` on that cost as it lies, and the index arithmetic on the device, for all of
+    ``dicts`` in one call each.  The triples have the reference's values and dtypes; ``index_i`` and ``index_j`` are on the
+    predictions' device.  The five status counts are left, unread, as ``matcher.last_match_status``
+    (:func:`raise_on_match_status`).  What the shapes put outside this route -- no batch element, a clip without targets, a
+    problem beyond the operator's limits -- takes :func:`_devis_indices`."""
+    from . import ops
+    from .functions import assignment
+    F, Q = matcher.num_frames, matcher.num_out
+    first = dicts[0]["pred_logits"]
+    tgt_ids, tgt_bbox, tgt_valid = targets[0]["labels"], targets[0]["boxes"], targets[0]["valid"]
+    num_tgt = len(tgt_ids) // F
+    if first.shape[0] == 0 or num_tgt == 0 or not assignment.fits(Q, num_tgt):
+        matcher.last_match_status = None
+        return _devis_indices(matcher, dicts, targets)
+    L, C = len(dicts), first.shape[-1]
+    if L == 1:
+        logits, boxes = first[0][None], dicts[0]["pred_boxes"][0][None]
+    else:
+        logits = torch.stack([d["pred_logits"][0] for d in dicts])
+        boxes = torch.stack([d["pred_boxes"][0] for d in dicts])
+    logits = logits.reshape(L, F, Q, C)
+    cost, cost_status = ops.match_cost(logits, boxes.reshape(L, F, Q, 4).to(logits.dtype), tgt_ids.reshape(num_tgt, F).long(),
+                                       _like_predictions(tgt_bbox.reshape(num_tgt, F, 4), logits.dtype),
+                                       cost_class=matcher.cost_class, cost_bbox=matcher.cost_bbox, cost_giou=matcher.cost_giou,
+                                       l1="sum" if matcher.use_l1_distance_sum else "mean", alpha=matcher.focal_alpha)
+    out_i, tgt_i, solve_status = ops.linear_assignment(cost)
+    matcher.last_match_status = torch.cat([cost_status, solve_status])
+    frames = torch.arange(F, device=out_i.device)
+    index_i = (frames * Q + out_i[:, :, None]).reshape(L, -1)
+    index_j = (frames + tgt_i[:, :, None] * F).reshape(L, -1)
+    index_valid = tgt_valid.reshape(num_tgt, F)[tgt_i.to(tgt_valid.device)].reshape(L, -1).type(torch.bool)
+    return [[(index_i[l], index_j[l], index_valid[l])] for l in range(L)]
 
 
 def _image_indices(matcher, dicts, targets):
@@ -493,7 +556,7 @@ def make_criterion_forward(previous, matcher_forwards):
     return forward
 
 
-def patch_criterion(criterion_module, matcher_module, *, batch_aux=False):
+def patch_criterion(criterion_module, matcher_module, *, batch_aux=False, gpu_assignment=False):
     """Opt-in: make the reference's criterion and matchers (``src.models.criterion``, ``src.models.matcher``) run on
     :func:`devis_amd.match_cost` and :func:`devis_amd.box_losses`.  ``DeVISHungarianMatcher.forward`` and
     ``HungarianMatcher.forward`` become one cost call, one device-to-host transfer (cost and status together),
@@ -506,6 +569,16 @@ def patch_criterion(criterion_module, matcher_module, *, batch_aux=False):
     ``batch_aux=True`` also wraps ``SetCriterion.forward`` (:func:`make_criterion_forward`): the decoder layers' matchings
     share one cost call and one transfer.  The caller's dicts are not mutated.
 
+    ``gpu_assignment=True`` (an opt-in of its own, which combines freely with ``batch_aux``) takes the transfer out of
+    ``DeVISHungarianMatcher.forward``: :func:`devis_amd.linear_assignment` solves the cost where it lies and the index
+    tensors are formed on the device (:func:`_devis_indices_on_device`), so the matcher neither synchronises nor calls scipy.
+    The triples have the reference's values and dtypes, but ``index_i`` and ``index_j`` are on the predictions' device, not on
+    the host; the criterion's losses index with them as they are.  Nothing is raised by the matcher: the status counts of both
+    operators are left as ``matcher.last_match_status`` for :func:`raise_on_match_status`, to be called where a
+    synchronisation is welcome.  A clip without targets, ``focal_loss=False`` and a problem with a side over 1024 take the
+    paths described above.  ``HungarianMatcher`` keeps the host path: its consumer reads the indices on the host.  The losses
+    after the matcher still synchronise (boolean-mask indexing, ``torch.any``): this removes the matcher's synchronisation only.
+
     Takes effect at once, also for objects that already exist.  Returns what was replaced (to undo the patch;
     :func:`unpatch_criterion`).  The other patches are separate choices."""
     crit, devis, image = criterion_module.SetCriterion, matcher_module.DeVISHungarianMatcher, matcher_module.HungarianMatcher
@@ -513,7 +586,7 @@ def patch_criterion(criterion_module, matcher_module, *, batch_aux=False):
     if batch_aux:
         previous["criterion_forward"] = crit.forward
     crit.loss_boxes = loss_boxes
-    devis.forward = make_matcher_forward(previous["devis_forward"], _devis_indices)
+    devis.forward = make_matcher_forward(previous["devis_forward"], _devis_indices_on_device if gpu_assignment else _devis_indices)
     image.forward = make_matcher_forward(previous["image_forward"], _image_indices)
     if batch_aux:
         crit.forward = make_criterion_forward(previous["criterion_forward"], {devis: devis.forward, image: image.forward})

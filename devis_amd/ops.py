@@ -39,6 +39,8 @@ through the C ABI, the same numbers -- and whose fake implementation gives shape
                                [L, R, T], status int32 [3]); no autograd formula
 ``box_loss_terms``             the box losses of matched pairs (:func:`box_loss_terms`) -> (l1 [N], giou [N]);
                                ``box_loss_terms_backward`` computes grad_src
+``linear_assignment``          the assignment the matchers make of that cost (:func:`linear_assignment`; include/assign.h)
+                               -> (rows int64 [L, n], cols int64 [L, n], status int32 [2]); no autograd formula
 =============================  ==========================================================================================
 
 Everything that reads the host or keeps Python state -- the ``spatial_shapes`` host hint, the frame-table cache, the
@@ -58,6 +60,7 @@ import torch
 from torch import Tensor
 
 from . import _native
+from .functions import assignment as _G
 from .functions import attention_maps as _A
 from .functions import box_matching as _X
 from .functions import deform_conv as _D
@@ -1056,3 +1059,39 @@ def box_losses(src_boxes, target_boxes, num_boxes):
     two tiny reductions stay in torch."""
     l1, giou = box_loss_terms(src_boxes, target_boxes)
     return {"loss_bbox": l1.sum() / num_boxes, "loss_giou": giou.sum() / num_boxes}
+
+
+# ---- the matchers' assignment (include/assign.h) ---------------------------------------------------------------------------
+
+@_op("linear_assignment")
+def linear_assignment_op(cost: Tensor) -> tuple[Tensor, Tensor, Tensor]:
+    """``linear_assignment`` as an op: (rows int64 [L, n], cols int64 [L, n], status int32 [2])."""
+    return _G._solve(cost)
+
+
+@linear_assignment_op.register_fake
+def _(cost):
+    L, R, T = _G.check_cost(cost)
+    n = torch.sym_min(R, T)
+    return _empty(cost, (L, n), torch.int64), _empty(cost, (L, n), torch.int64), _empty(cost, (2,), torch.int32)
+
+
+def linear_assignment(cost):
+    """``scipy.optimize.linear_sum_assignment`` of ``L`` independent problems on the HIP kernel of include/assign.h, without a
+    transfer: ``cost`` [L, R, T] in float32 or float64 -- :func:`match_cost`'s output as it lies -- gives
+    ``(rows [L, n], cols [L, n], status int32 [2])`` with ``n = min(R, T)``, int64 indices on ``cost``'s device, the pairs of a
+    problem ordered by ascending row as scipy orders them.  The method is scipy's (the shortest augmenting paths of Crouse
+    2016) in double; among columns of equal shortest-path value one without a row is taken first, then the lowest index, so a
+    unique optimum gives scipy's indices and a tied one gives an assignment of scipy's total.
+
+    ``status`` counts, without a synchronisation, the problems scipy raises on: [0] those with a NaN or ``-inf`` entry
+    ("matrix contains invalid numeric entries"), [1] those ``+inf`` entries make infeasible ("cost matrix is infeasible").
+    Such a problem gets the pairs ``(k, k)``; the others are unaffected.  :func:`devis_amd.raise_on_match_status` reads the
+    counts and raises.  Sides up to 1024.  No gradient: an input that requires one while gradients are recorded raises.
+    GPU tensors only.  One launch of one wave per problem; the result is bitwise reproducible, and a problem has the same one
+    alone and in any larger call."""
+    _I.check_no_grad("linear_assignment", [("cost", cost)])
+    if torch.compiler.is_compiling():
+        return linear_assignment_op(cost)
+    with torch.no_grad():
+        return _G._solve(cost)
