@@ -577,7 +577,8 @@ def patch_criterion(criterion_module, matcher_module, *, batch_aux=False, gpu_as
     operators are left as ``matcher.last_match_status`` for :func:`raise_on_match_status`, to be called where a
     synchronisation is welcome.  A clip without targets, ``focal_loss=False`` and a problem with a side over 1024 take the
     paths described above.  ``HungarianMatcher`` keeps the host path: its consumer reads the indices on the host.  The losses
-    after the matcher still synchronise (boolean-mask indexing, ``torch.any``): this removes the matcher's synchronisation only.
+    after the matcher still synchronise (boolean-mask indexing, ``torch.any``): this removes the matcher's synchronisation only
+    (the label loss stops synchronising with :func:`patch_label_loss`).
 
     Takes effect at once, also for objects that already exist.  Returns what was replaced (to undo the patch;
     :func:`unpatch_criterion`).  The other patches are separate choices."""
@@ -600,3 +601,39 @@ def unpatch_criterion(criterion_module, matcher_module, previous):
     matcher_module.HungarianMatcher.forward = previous["image_forward"]
     if "criterion_forward" in previous:          # (patched with batch_aux=True)
         criterion_module.SetCriterion.forward = previous["criterion_forward"]
+
+
+def loss_labels_focal(self, outputs, targets, indices, num_boxes, log=True):
+    """A drop-in for the reference's ``SetCriterion.loss_labels_focal`` (``self`` is the criterion) on
+    :func:`devis_amd.label_losses`: the matcher's index tensors go to the operator as they lie -- ``rows = cat_i(i * N +
+    src_i)``, ``labels = cat_i(targets[i]["labels"][J_i])`` (an integer gather) and, for DeVIS's ``(src, tgt, mask)``
+    triples, ``valid = cat_i(mask_i)`` as a tensor, where the reference indexes with the boolean mask and synchronises; image
+    matchings ``(src, tgt)`` have no mask.  Index tensors on the host are moved to the logits' device without a synchronising
+    copy.  With device indices (``patch_criterion(gpu_assignment=True)``) nothing here synchronises.  Returns ``{"loss_ce"}``
+    and, with ``log``, ``"class_error"``.  A match whose row or label is out of range is ignored, not raised on: the
+    operator's ``counts[2:]`` tell (:func:`devis_amd.label_loss_terms`)."""
+    from . import ops
+    assert 'pred_logits' in outputs
+    src_logits = outputs['pred_logits']
+    N = src_logits.shape[1]
+    here = lambda t: t if t.device == src_logits.device else _on_device_of(t, src_logits)      # noqa: E731
+    rows = torch.cat([here(entry[0]) + i * N for i, entry in enumerate(indices)])
+    labels = torch.cat([here(t["labels"])[here(entry[1])] for t, entry in zip(targets, indices)]).long()
+    valid = torch.cat([here(entry[2]) for entry in indices]) if len(indices[0]) == 3 else None
+    return ops.label_losses(src_logits, rows.long(), labels, valid, num_boxes, alpha=self.focal_alpha, log=log)
+
+
+def patch_label_loss(criterion_module):
+    """Opt-in: make the reference's criterion (``src.models.criterion``) compute its label loss with
+    :func:`loss_labels_focal` -- the fused HIP operator instead of boolean-mask indexing, a one-hot tensor,
+    sigmoid_focal_loss and accuracy.  Takes effect at once, also for criteria that already exist (the method is looked up on
+    the class).  Returns the replaced function (to undo the patch; :func:`unpatch_label_loss`).  The other patches are
+    separate choices."""
+    previous = criterion_module.SetCriterion.loss_labels_focal
+    criterion_module.SetCriterion.loss_labels_focal = loss_labels_focal
+    return previous
+
+
+def unpatch_label_loss(criterion_module, previous):
+    """Undo :func:`patch_label_loss` (tests)."""
+    criterion_module.SetCriterion.loss_labels_focal = previous

@@ -41,6 +41,9 @@ through the C ABI, the same numbers -- and whose fake implementation gives shape
                                ``box_loss_terms_backward`` computes grad_src
 ``linear_assignment``          the assignment the matchers make of that cost (:func:`linear_assignment`; include/assign.h)
                                -> (rows int64 [L, n], cols int64 [L, n], status int32 [2]); no autograd formula
+``label_loss_terms``           the criterion's label loss (:func:`label_loss_terms`; include/labelloss.h) -> (focal_sum [],
+                               counts int32 [4], target_classes int32 [B, N]); ``label_loss_terms_backward`` computes
+                               grad_logits
 =============================  ==========================================================================================
 
 Everything that reads the host or keeps Python state -- the ``spatial_shapes`` host hint, the frame-table cache, the
@@ -64,6 +67,7 @@ from .functions import assignment as _G
 from .functions import attention_maps as _A
 from .functions import box_matching as _X
 from .functions import deform_conv as _D
+from .functions import label_loss as _Y
 from .functions import mask_binary_iou as _B
 from .functions import mask_head_stage as _S
 from .functions import mask_iou as _I
@@ -1095,3 +1099,85 @@ def linear_assignment(cost):
         return linear_assignment_op(cost)
     with torch.no_grad():
         return _G._solve(cost)
+
+
+# ---- the criterion's label loss (include/labelloss.h) ----------------------------------------------------------------------
+
+@_op("label_loss_terms")
+def label_loss_terms_op(logits: Tensor, rows: Tensor, labels: Tensor, valid: Optional[Tensor],
+                        alpha: float) -> tuple[Tensor, Tensor, Tensor]:
+    """``label_loss_terms`` with every argument given: (focal_sum [], counts int32 [4], target_classes int32 [B, N])."""
+    return _Y._forward(logits, rows, labels, valid, alpha)
+
+
+@label_loss_terms_op.register_fake
+def _(logits, rows, labels, valid, alpha):
+    B, N = _Y.check_labels(logits, rows, labels, valid)[:2]
+    return (_empty(logits, (), _native.acc_dtype(logits.dtype)), _empty(logits, (4,), torch.int32),
+            _empty(logits, (B, N), torch.int32))
+
+
+@_op("label_loss_terms_backward")
+def label_loss_terms_backward(grad_sum: Tensor, logits: Tensor, target_classes: Tensor, alpha: float) -> Tensor:
+    """grad_logits [B, N, C] in logits' dtype."""
+    return _Y._backward(grad_sum, logits, target_classes, alpha)
+
+
+@label_loss_terms_backward.register_fake
+def _(grad_sum, logits, target_classes, alpha):
+    return _empty(logits, logits.shape)
+
+
+def _setup_label_loss_terms(ctx, inputs, output):
+    ctx.alpha = inputs[4]
+    ctx.save_for_backward(inputs[0], output[2])
+
+
+def _backward_label_loss_terms(ctx, grad_sum, grad_counts, grad_classes):
+    if not ctx.needs_input_grad[0]:
+        return None, None, None, None, None
+    logits, target_classes = ctx.saved_tensors
+    return label_loss_terms_backward(grad_sum, logits, target_classes, ctx.alpha), None, None, None, None
+
+
+label_loss_terms_op.register_autograd(_backward_label_loss_terms, setup_context=_setup_label_loss_terms)
+
+
+def label_loss_terms(logits, rows, labels, valid=None, *, alpha=0.25):
+    """The terms of DeVIS's label loss (``SetCriterion.loss_labels_focal``) on the fused HIP kernels of
+    include/labelloss.h, from the matcher's index tensors as they lie::
+
+        target_classes = full([B, N], C);  target_classes.view(-1)[rows[valid]] = labels[valid]
+        focal_sum = sigmoid_focal_loss(logits, one_hot(target_classes, C + 1)[..., :C], alpha, gamma=2) summed over all elements
+        counts    = [matches, matches whose query's argmax is their label, bad rows, bad labels]
+
+    ``logits`` [B, N, C] (f32 / f64 / bf16 / f16), ``rows`` int64 [M] -- the flattened query ``b * N + src`` of each match --,
+    ``labels`` int64 [M], ``valid`` bool or uint8 [M] or None for all valid: a tensor operand, not a boolean index.  A match
+    counts when it is valid, ``0 <= row < B * N`` and ``0 <= label <= C`` (``C`` is "no object": counted, no positive); the
+    others are ignored.  Of several matches of one query the one with the highest position wins (``index_put_``'s order on
+    the CPU).  ``alpha < 0`` switches the class weighting off.
+
+    Returns ``(focal_sum [], counts int32 [4], target_classes int32 [B, N])``, ``focal_sum`` in float32 (float64 for float64
+    logits).  ``counts[1]`` takes the lowest class index on a tie, and a query with a NaN logit is never correct;
+    ``counts[2]`` / ``counts[3]`` are the valid matches with a row outside ``[0, B * N)`` / a label outside ``[0, C]``.  Only
+    ``focal_sum`` is differentiable, and only with respect to ``logits``; there is no double backward.  The forward is one
+    launch (two beyond ``labelloss_tile`` logits), the backward one; no one-hot tensor is allocated and no call synchronises.
+    GPU tensors only.  Every result is bitwise reproducible and does not depend on the order of the matches."""
+    if logits.requires_grad:
+        _native.dtype_code(logits.dtype)       # (raises on a dtype the unit lacks)
+    if torch.compiler.is_compiling():
+        return label_loss_terms_op(logits, rows, labels, valid, float(alpha))
+    return _Y.LabelLossTermsFunction.apply(logits, rows, labels, valid, float(alpha))
+
+
+def label_losses(logits, rows, labels, valid, num_boxes, *, alpha=0.25, log=True):
+    """DeVIS's label loss from the logits and the matcher's indices: ``{"loss_ce": focal_sum / num_boxes}`` of
+    :func:`label_loss_terms` and, with ``log``, ``"class_error"``: 100 minus the matched queries' top-1 accuracy in percent
+    -- the reference's ``accuracy``, 0 for no matches included -- as a device scalar, without a synchronisation.
+    ``num_boxes`` is a number or a tensor, as in the reference; the division stays in torch."""
+    focal_sum, counts, _ = label_loss_terms(logits, rows, labels, valid, alpha=alpha)
+    losses = {"loss_ce": focal_sum / num_boxes}
+    if log:
+        matched, correct = counts[0], counts[1]
+        losses["class_error"] = 100 - torch.where(matched > 0, 100 * correct / matched, torch.zeros_like(focal_sum))
+    return losses
