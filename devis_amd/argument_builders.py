@@ -637,3 +637,83 @@ def patch_label_loss(criterion_module):
 def unpatch_label_loss(criterion_module, previous):
     """Undo :func:`patch_label_loss` (tests)."""
     criterion_module.SetCriterion.loss_labels_focal = previous
+
+
+def _fusable(self, masks, pos_embeds):
+    """The position-encoding module all of ``pos_embeds`` were deferred by, when one :func:`devis_amd.encoder_position_embedding`
+    call gives what the reference computes from them: every level deferred by the same module from that level's own mask, with
+    the same ``.to(dtype)``, and dtypes the kernels write.  None otherwise."""
+    from .modules.position_encoding import DeferredPositionEmbedding
+    from .functions.position_embedding import OUT_DTYPES
+    if not pos_embeds or not all(isinstance(p, DeferredPositionEmbedding) for p in pos_embeds):
+        return None
+    first = pos_embeds[0]
+    for p, m in zip(pos_embeds, masks):
+        same_mask = p.mask is m or (p.mask.data_ptr() == m.data_ptr() and p.mask.shape == m.shape and p.mask.stride() == m.stride())
+        if p.module is not first.module or p.dtype != first.dtype or not same_mask or p._tensor is not None:
+            return None
+    temporal_embed = getattr(first.module, "temporal_embed", None)
+    if first.dtype not in (None,) + OUT_DTYPES or self.level_embed.dtype not in OUT_DTYPES or \
+            (temporal_embed is not None and temporal_embed.dtype not in OUT_DTYPES) or first.module.num_pos_feats % 2:
+        return None
+    return first.module
+
+
+def prepare_data_deferred(self, srcs, masks, pos_embeds):
+    """``DeformableTransformer.prepare_data`` under :func:`patch_position_encoding` (same arguments, same six results).  When
+    every level's position embedding is a :class:`devis_amd.DeferredPositionEmbedding` of one module, ``lvl_pos_embed_flatten``,
+    ``mask_flatten`` and ``valid_ratios`` come from ONE :func:`devis_amd.encoder_position_embedding` call -- the per-level
+    ``[N, C, H, W]`` tensors, their ``.to(dtype)``, transposes, ``+ level_embed`` and ``cat`` never run --; otherwise the
+    deferred ones are materialised and :func:`prepare_data` takes over.  ``spatial_shapes`` / ``level_start_index`` come from
+    :func:`interned_pyramid` either way."""
+    from . import ops
+    from .modules.position_encoding import DeferredPositionEmbedding
+    module = _fusable(self, masks, pos_embeds)
+    if module is None:
+        return prepare_data(self, srcs, masks, [p.materialize() if isinstance(p, DeferredPositionEmbedding) else p for p in pos_embeds])
+    dtype = pos_embeds[0].dtype
+    src_flatten = torch.cat([src.flatten(2).transpose(1, 2) for src in srcs], 1)
+    lvl_pos_embed_flatten, mask_flatten, valid_ratios = ops.encoder_position_embedding(
+        list(masks), self.level_embed[:len(masks)], getattr(module, "temporal_embed", None), num_pos_feats=module.num_pos_feats,
+        temperature=module.temperature, normalize=module.normalize, scale=module.scale if module.normalize else None,
+        round_dtype=None if dtype in (None, torch.float32) else dtype)
+    spatial_shapes, level_start_index = interned_pyramid([src.shape[-2:] for src in srcs], src_flatten.device)
+    return src_flatten, mask_flatten, lvl_pos_embed_flatten, spatial_shapes, level_start_index, valid_ratios
+
+
+def patch_position_encoding(position_encoding_module, deformable_transformer_module):
+    """Opt-in, EAGER ONLY (a :class:`devis_amd.DeferredPositionEmbedding` is a Python object, not a tensor: a traced or compiled
+    model calls :func:`devis_amd.encoder_position_embedding` itself): make the forward of the reference's
+    ``PositionEmbeddingSine`` and ``PositionEmbeddingSineWithLearnableTemporal`` (``src.models.position_encoding``) return a
+    deferred embedding, and ``DeformableTransformer.prepare_data`` (``src.models.deformable_transformer``)
+    :func:`prepare_data_deferred`, which computes the encoder's positional input with one fused operator call.
+
+    Order with :func:`patch_transformer`: call ``patch_transformer`` FIRST and this patch second, and the fused
+    ``prepare_data`` is the installed one.  In the other order ``patch_transformer`` puts its own ``prepare_data`` over the
+    fused one: results are still right -- the deferred embeddings materialise on their first use, through the ``[N, C, H, W]``
+    kernel -- but nothing is fused.  Undo in the reverse order of patching.
+
+    Takes effect at once, also for modules that already exist.  Returns what was replaced (to undo the patch;
+    :func:`unpatch_position_encoding`).  The other patches are separate choices."""
+    from .modules.position_encoding import deferred_forward
+    sine = position_encoding_module.PositionEmbeddingSine
+    temporal = position_encoding_module.PositionEmbeddingSineWithLearnableTemporal
+    top = deformable_transformer_module.DeformableTransformer
+    previous = {"sine_forward": sine.__dict__.get("forward"), "temporal_forward": temporal.__dict__.get("forward"),
+                "prepare_data": top.__dict__.get("prepare_data")}
+    sine.forward = deferred_forward
+    temporal.forward = deferred_forward
+    top.prepare_data = prepare_data_deferred
+    return previous
+
+
+def unpatch_position_encoding(position_encoding_module, deformable_transformer_module, previous):
+    """Undo :func:`patch_position_encoding` (tests)."""
+    for cls, name, key in ((position_encoding_module.PositionEmbeddingSine, "forward", "sine_forward"),
+                           (position_encoding_module.PositionEmbeddingSineWithLearnableTemporal, "forward", "temporal_forward"),
+                           (deformable_transformer_module.DeformableTransformer, "prepare_data", "prepare_data")):
+        if previous[key] is None:           # (the class inherited it)
+            if name in cls.__dict__:
+                delattr(cls, name)
+        else:
+            setattr(cls, name, previous[key])

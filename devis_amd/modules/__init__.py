@@ -4,3 +4,5 @@ from .ms_deform_attn import (MSDeformAttn, TemporalMSDeformAttnBase,  # noqa: F4
 from .deform_conv import ModulatedDeformableConv2d  # noqa: F401  (reference src/models/deformable_segmentation.py)
 from .attention_maps import MultiScaleMHAttentionMap  # noqa: F401  (reference src/models/deformable_segmentation.py)
 from .mask_head import MaskHeadConv  # noqa: F401  (reference src/models/deformable_segmentation.py)
+from .position_encoding import (PositionEmbeddingSine,  # noqa: F401  (reference src/models/position_encoding.py)
+                                PositionEmbeddingSineWithLearnableTemporal)

@@ -44,6 +44,11 @@ through the C ABI, the same numbers -- and whose fake implementation gives shape
 ``label_loss_terms``           the criterion's label loss (:func:`label_loss_terms`; include/labelloss.h) -> (focal_sum [],
                                counts int32 [4], target_classes int32 [B, N]); ``label_loss_terms_backward`` computes
                                grad_logits
+``sine_position_embedding``    the sine embedding of one padding mask (:func:`sine_position_embedding`; include/posembed.h)
+                               -> pos [N, C, H, W]; no autograd formula
+``encoder_position_embedding`` the encoder's positional input of all levels (:func:`encoder_position_embedding`) -> (pos
+                               [N, S, C], mask_flatten bool [N, S], valid_ratios [N, L, 2]);
+                               ``encoder_position_embedding_backward`` computes the gradients of the two embeddings
 =============================  ==========================================================================================
 
 Everything that reads the host or keeps Python state -- the ``spatial_shapes`` host hint, the frame-table cache, the
@@ -74,6 +79,7 @@ from .functions import mask_iou as _I
 from .functions import mask_losses as _L
 from .functions import mask_rle as _R
 from .functions import ms_deform_attn_func as _F
+from .functions import position_embedding as _P
 
 
 def _namespace():
@@ -1181,3 +1187,117 @@ def label_losses(logits, rows, labels, valid, num_boxes, *, alpha=0.25, log=True
         matched, correct = counts[0], counts[1]
         losses["class_error"] = 100 - torch.where(matched > 0, 100 * correct / matched, torch.zeros_like(focal_sum))
     return losses
+
+
+# ---- the encoder's positional input (include/posembed.h) -------------------------------------------------------------------
+
+@_op("sine_position_embedding")
+def sine_position_embedding_op(mask: Tensor, num_pos_feats: int, temperature: float, normalize: bool, scale: Optional[float],
+                               out_dtype: Optional[torch.dtype]) -> Tensor:
+    """``sine_position_embedding`` with every argument given: pos [N, 2 * num_pos_feats, H, W]."""
+    return _P._sine(mask, num_pos_feats, temperature, normalize, scale, out_dtype)
+
+
+@sine_position_embedding_op.register_fake
+def _(mask, num_pos_feats, temperature, normalize, scale, out_dtype):
+    N, (H, W), _, out_dtype = _P.check_sine(mask, num_pos_feats, normalize, scale, out_dtype)
+    return _empty(mask, (N, 2 * num_pos_feats, H, W), out_dtype)
+
+
+def sine_position_embedding(mask, *, num_pos_feats, temperature=10000, normalize=False, scale=None, out_dtype=None):
+    """DeVIS's ``PositionEmbeddingSine.forward`` of a padding mask on the HIP kernels of include/posembed.h::
+
+        y_embed, x_embed = (~mask).cumsum(1), (~mask).cumsum(2)          # then, with normalize, / (last + 1e-6) * scale
+        pos = cat(sin | cos of y_embed / dim_t, sin | cos of x_embed / dim_t).permute(0, 3, 1, 2)
+
+    ``mask`` bool [N, H, W] with any strides (True is padding); ``num_pos_feats`` even; ``scale`` (default ``2 * pi``) needs
+    ``normalize``; ``out_dtype`` float32 (the default), bfloat16 or float16: float32 arithmetic with the reference's
+    operations in the reference's order, rounded once at the store.  Returns ``[N, 2 * num_pos_feats, H, W]``, without a
+    gradient (a mask has none).  Two launches: the counts -- integer prefix sums by wave ballots -- and the write pass.  GPU
+    tensors only."""
+    if torch.compiler.is_compiling():
+        return sine_position_embedding_op(mask, num_pos_feats, float(temperature), bool(normalize), scale, out_dtype)
+    with torch.no_grad():
+        return _P._sine(mask, num_pos_feats, float(temperature), bool(normalize), scale, out_dtype)
+
+
+@_op("encoder_position_embedding")
+def encoder_position_embedding_op(masks: List[Tensor], level_embed: Tensor, temporal_embed: Optional[Tensor],
+                                  num_pos_feats: Optional[int], temperature: float, normalize: bool, scale: Optional[float],
+                                  round_dtype: Optional[torch.dtype],
+                                  out_dtype: Optional[torch.dtype]) -> tuple[Tensor, Tensor, Tensor]:
+    """``encoder_position_embedding`` with every argument given: (pos [N, S, C], mask_flatten bool [N, S], valid_ratios
+    float32 [N, L, 2])."""
+    return _P._encoder(masks, level_embed, temporal_embed, num_pos_feats, temperature, normalize, scale, round_dtype, out_dtype)
+
+
+@encoder_position_embedding_op.register_fake
+def _(masks, level_embed, temporal_embed, num_pos_feats, temperature, normalize, scale, round_dtype, out_dtype):
+    N, sizes, C, _, _, out_dtype = _P.check_encoder(masks, level_embed, temporal_embed, num_pos_feats, normalize, scale,
+                                                    round_dtype, out_dtype)
+    S = sum(h * w for h, w in sizes)
+    return (_empty(level_embed, (N, S, C), out_dtype), _empty(level_embed, (N, S), torch.bool),
+            _empty(level_embed, (N, len(sizes), 2), torch.float32))
+
+
+@_op("encoder_position_embedding_backward")
+def encoder_position_embedding_backward(grad_pos: Tensor, heights: List[int], widths: List[int], want_level: bool,
+                                        want_temporal: bool) -> tuple[Tensor, Tensor]:
+    """(grad_level_embed float32 [L, C], grad_temporal_embed float32 [N, C]); the one that is not wanted is empty."""
+    return _P._encoder_backward(grad_pos, heights, widths, want_level, want_temporal)
+
+
+@encoder_position_embedding_backward.register_fake
+def _(grad_pos, heights, widths, want_level, want_temporal):
+    N, _, C = grad_pos.shape
+    return (_empty(grad_pos, (len(heights), C) if want_level else (0,), torch.float32),
+            _empty(grad_pos, (N, C) if want_temporal else (0,), torch.float32))
+
+
+def _setup_encoder_position_embedding(ctx, inputs, output):
+    masks, level_embed, temporal_embed = inputs[:3]
+    ctx.heights, ctx.widths = [m.shape[1] for m in masks], [m.shape[2] for m in masks]
+    ctx.dtypes = (level_embed.dtype, None if temporal_embed is None else temporal_embed.dtype)
+
+
+def _backward_encoder_position_embedding(ctx, grad_pos, grad_mask, grad_ratios):
+    want_level, want_temporal = ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.dtypes[1] is not None
+    nothing = (None,) * 9
+    if not (want_level or want_temporal):
+        return nothing
+    grad_level, grad_temporal = encoder_position_embedding_backward(grad_pos, ctx.heights, ctx.widths, want_level, want_temporal)
+    return (None, grad_level.to(ctx.dtypes[0]) if want_level else None,
+            grad_temporal.to(ctx.dtypes[1]) if want_temporal else None) + nothing[3:]
+
+
+encoder_position_embedding_op.register_autograd(_backward_encoder_position_embedding,
+                                                setup_context=_setup_encoder_position_embedding)
+
+
+def encoder_position_embedding(masks, level_embed, temporal_embed=None, *, num_pos_feats=None, temperature=10000,
+                               normalize=True, scale=None, round_dtype=None, out_dtype=None):
+    """The encoder's positional input from the padding masks of all levels, on the HIP kernels of include/posembed.h: what
+    DeVIS's position encoding, the ``.to(dtype)`` of its callers and ``DeformableTransformer.prepare_data`` make of them::
+
+        pos_l        = PositionEmbeddingSine(num_pos_feats, temperature, normalize, scale)(masks[l])    # [N, C, H_l, W_l]
+        pos_l        = (pos_l + temporal_embed[:, :, None, None]).to(round_dtype)                       # each where given
+        pos          = cat_l(pos_l.flatten(2).transpose(1, 2) + level_embed[l], 1)                      # [N, S, C]
+        mask_flatten = cat_l(masks[l].flatten(1), 1);   valid_ratios = stack_l(get_valid_ratio(masks[l]), 1)
+
+    ``masks``: a list of bool [N, H_l, W_l] with any strides; ``level_embed`` [L, C] and ``temporal_embed`` [N, C] or None,
+    in any floating dtype (the kernels read them as float32); ``num_pos_feats`` defaults to ``C // 2`` and must be even;
+    ``scale`` (default ``2 * pi``) needs ``normalize``.  Arithmetic is float32 with the reference's operations in the
+    reference's order.  ``round_dtype`` (bfloat16 / float16) rounds ``sine + temporal`` before the level embedding is added,
+    as ``.to(dtype)`` does in the reference; ``out_dtype`` defaults to what torch's promotion gives the reference
+    (``promote_types(round_dtype or float32, level_embed.dtype)``) and is rounded once at the store.
+
+    Returns ``(pos [N, S, C], mask_flatten bool [N, S], valid_ratios float32 [N, L, 2])``.  Only ``pos`` is differentiable,
+    with respect to ``level_embed`` and ``temporal_embed``: their gradients are segmented column sums of ``grad_pos`` in a
+    fixed order, without atomics -- bitwise reproducible --, and only the ones autograd asks for are computed.  Two launches
+    forward, two backward.  GPU tensors only."""
+    masks = list(masks)
+    if torch.compiler.is_compiling():
+        return encoder_position_embedding_op(masks, level_embed, temporal_embed, num_pos_feats, float(temperature),
+                                             bool(normalize), scale, round_dtype, out_dtype)
+    return _P.EncoderPositionEmbeddingFunction.apply(level_embed, temporal_embed, num_pos_feats, float(temperature),
+                                                     bool(normalize), scale, round_dtype, out_dtype, *masks)
