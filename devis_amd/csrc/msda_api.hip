@@ -114,7 +114,10 @@ int launch_backward(int dtype, const Params &p, const Knobs &k, const Shape &s, 
         switch (g.kind) {
             case GatherPlan::kRecordsOnly: rc = pq.workspace ? launch_cull_records(dtype, pq, stream) : MSDA_OK; break;
             case GatherPlan::kWindow: rc = launch_bwd_win(dtype, pq, g.win, stream); break;
-            case GatherPlan::kSlab: rc = launch_bwd_rs(dtype, s.l0_host, pq, g.parts, g.grid, stream, g.frame_split); break;
+            case GatherPlan::kSlab:
+                pq.walk_down = g.walk_down ? 1 : 0;
+                rc = launch_bwd_rs(dtype, s.l0_host, pq, g.parts, g.grid, stream, g.frame_split);
+                break;
             default: rc = launch_bwd_tile(dtype, s.G, false, pq, s.blocks, s.tile_lds, stream);
         }
         if (!rc && pq.cull_points && pq.bsum) rc = launch_cull_summary(pq, stream);      // block summaries of the records just written
@@ -152,6 +155,7 @@ int run(int dtype, const Params &p_in, const Knobs &k, bool bwd, hipStream_t str
     p.own_levels = p.L;
     p.rec_mask = ~0u;
     p.own_pix = kOwnPix;
+    p.walk_down = 0;
     p.dbg = k.dbg;
     // culling records per point (4 x int16) when the owner-computes scatter will read them; (min, max) intervals for the
     // LDS-atomic scatter (MSDA_BWD_CULL=2 forces them)

@@ -34,6 +34,8 @@ struct Knobs {
     int force_generic = 0;
     int det_route = 0;                  // MSDA_GRAD_DETERMINISTIC grad_value: 0 auto, 1 = route (a) (any shape), 2 = route (b) (LDS bands)
     int dbg = 0;                        // MSDA_DBG: tile kernels and launcher (kDbg*, msda_params.h)
+    int walk = -1;                      // resident-slab gather pass: -1 = the planner's size rule (msda_params.h, kWalkDownBytes), 0 = every XCD
+                                        // takes its workgroups first to last, 1 = last to first.  Results kept
     unsigned forced = 0;                // bit i: the variable of kKnobs[i] was SET in the environment, whatever its value: a knob
                                         // forced to its default (MSDA_FWD_RS=-1 for a rules-only A/B run) still wins over a pin
 };
@@ -69,6 +71,7 @@ inline const KnobDef kKnobs[] = {
     {"MSDA_FORCE_GENERIC", nullptr, &Knobs::force_generic, Parse::IsOne},
     {"MSDA_DET_ROUTE", nullptr, &Knobs::det_route, Parse::Int},
     {"MSDA_DBG", nullptr, &Knobs::dbg, Parse::Int},
+    {"MSDA_WALK", nullptr, &Knobs::walk, Parse::Int},
 };
 constexpr int kNumKnobs = sizeof(kKnobs) / sizeof(kKnobs[0]);
 static_assert(kNumKnobs <= 32, "Knobs::forced has one bit per knob");

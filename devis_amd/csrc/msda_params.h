@@ -57,7 +57,16 @@ struct Params {
                                 // selects the kernel's slot count at the launch, the planner counted the bands with it
     unsigned rec_mask;          // bwd: bit l = the gather pass leaves culling records for level l and the owner-computes scatter reads
                                 // them; clear for the matrix-pipe levels and for levels that are ONE band (every group a candidate)
+    int walk_down;              // bwd: the resident-slab gather pass takes its workgroups in the reverse of the forward's order
+                                // (GatherPlan::walk_down, kWalkDownBytes below): speed only, every workgroup computes what it did
 };
+
+// The gather pass of a call too large for the last-level cache walks its work DOWNWARDS.  Forward and gather pass give every
+// XCD the same clips in the same ascending order, so between the two uses of a `value` line lies the forward's whole footprint,
+// and a 256 MiB memory-side cache (LRU-like) keeps nothing for the second use.  In the reverse order the maps the forward read
+// last are the first the gather pass reads.  A call whose footprint (value + sampling points + out) stays below this size fits
+// the cache either way and keeps the ascending order.
+constexpr long long kWalkDownBytes = 256ll << 20;
 
 struct Level { int H, W, start, pad; };   // start = first pixel of the level inside the CLIP slab
 

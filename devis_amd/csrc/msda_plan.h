@@ -32,6 +32,7 @@ struct Shape {
     bool rs_ok;                         // rs_fits
     int rs_tiles_per_clip, l0_host;     // resident-slab kernels: 16-row tiles per clip, first slab level
     long long outside, l2_budget;       // bytes of one (clip, head)'s levels below l0_host; see rs_tiles_per_wave
+    long long footprint;                // bytes of value + sampling points (locations and weights) + out of the call: walk_down_rule
 };
 
 bool shape_of(int dtype, const Params &p, bool bwd, int cus, Shape &s);         // false: the problem is too large for one launch
@@ -64,6 +65,7 @@ struct GatherPlan {
     WinPlan win;                        // kWindow
     int parts = 0, frame_split = 0;     // kSlab: workgroups per (clip, head) -- or per (clip, head, frame) with frame_split
     unsigned grid = 0;                  // kSlab
+    bool walk_down = false;             // kSlab: every XCD takes its run of workgroups last first, the reverse of the forward's walk (walk_down_rule)
 };
 GatherPlan plan_gather(const Shape &s, const Params &p, const Knobs &k, int grads, bool interval_records);
 

@@ -411,7 +411,13 @@ msda_bwd_rs_kernel(const Params p, int slab_bytes, int parts, int frame_split)
     const int l0 = sh.l0;
 
     const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u;       // clip-major XCD mapping, heads in their plain order (see the forward)
-    const unsigned lin = xcd * (nwg / 8u) + min(xcd, nwg % 8u) + blockIdx.x / 8u;
+    // Params::walk_down: the XCD keeps its run of whole clips -- the forward's lines of them are in ITS L2 -- and takes it last
+    // first: the forward ended on the last clip of the run, its last head slot and the last source frame, and what it read there
+    // is what the last-level cache still holds (msda_params.h, kWalkDownBytes).  Heads then in the forward's slot order: the last
+    // four slots are the heads the forward had in flight at its end (16 clips fp32, this pass up / down with the plain head
+    // order / down with the forward's: 0.3985 / 0.3915 / 0.3875 ms, profiles/walk_order_ab.log).
+    const unsigned run0 = xcd * (nwg / 8u) + min(xcd, nwg % 8u), run_n = nwg / 8u + (xcd < nwg % 8u ? 1u : 0u);
+    const unsigned lin = run0 + (p.walk_down ? run_n - 1u - blockIdx.x / 8u : blockIdx.x / 8u);
     // frame_split (round 4): a workgroup = (clip, head, SOURCE FRAME, part of the clip's tiles) instead of (clip, head, part)
     // walking the frames: nothing is carried from one source frame to the next in this pass, so the frame loop can be a grid
     // dimension -- one slab per workgroup, no barrier or staging between frames
@@ -419,7 +425,9 @@ msda_bwd_rs_kernel(const Params p, int slab_bytes, int parts, int frame_split)
     const unsigned rest = lin / (unsigned)parts;
     const int f_only = frame_split ? (int)(rest % (unsigned)p.frames) : -1;
     const unsigned rest2 = frame_split ? rest / (unsigned)p.frames : rest;
-    const int m = (int)(rest2 % (unsigned)p.M);
+    const int slot = (int)(rest2 % (unsigned)p.M);
+    const bool alternate = p.walk_down && !kHalf && !(p.M & 1) && p.v_pix == p.M * D && p.v_head == D;      // (the forward's condition)
+    const int m = alternate ? (2 * slot) % p.M + (2 * slot) / p.M : slot;
     const int clip = (int)(rest2 / (unsigned)p.M);
     const int tiles_per_group = (p.Lq + RPW - 1) / RPW, tiles_per_clip = p.frames * tiles_per_group;
     const int tpw = (tiles_per_clip + parts - 1) / parts;
@@ -704,6 +712,9 @@ int bwd_rs(const Params &p, int parts, unsigned grid, hipStream_t stream, int fr
     const auto kern = &msda_bwd_rs_kernel<T, TL, PL0>;
     if (const int rc = grant_lds(reinterpret_cast<const void *>(kern), total, granted, "the resident-slab gather-pass kernel")) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kRsThreads), total, stream, p, kRsSlabBytes, parts, frame_split);
+    if (p.walk_down)
+        return check_launch(frame_split ? "msda backward (resident-slab kernel, grad_loc/grad_attn, one source frame per workgroup), last workgroup first"
+                                        : "msda backward (resident-slab kernel, grad_loc/grad_attn), last workgroup first");
     return check_launch(frame_split ? "msda backward (resident-slab kernel, grad_loc/grad_attn, one source frame per workgroup)"
                                     : "msda backward (resident-slab kernel, grad_loc/grad_attn)");
 }
