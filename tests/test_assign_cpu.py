@@ -21,6 +21,36 @@ F64 = torch.float64
 SHAPES = [(1, 1), (1, 5), (5, 1), (2, 2), (7, 7), (50, 4), (4, 50), (64, 9), (65, 9), (9, 65), (128, 3), (1024, 2), (2, 1024)]
 RANK_ONE = [(7, 7), (24, 24), (25, 300), (65, 65)]
 TIED = [(12, 5), (5, 12), (9, 9)]
+# The wide shapes: a longer side above 128 (4, 8 and 16 columns per lane), a shorter side above 65 (several rounds of 64 lanes
+# over the rows, a path back across several column slots), cost blocks too large to stage, rows above 63 in the candidate key.
+# WIDE_VARIANTS states the instantiation each of them selects.
+WIDE = [(150, 150), (130, 90), (90, 130), (200, 260), (40, 300), (300, 40), (513, 70), (70, 513)]
+LIMIT = (1024, 1024)                    # one float32 problem: both key fields at full width
+WIDE_RANK_ONE = [(130, 130), (129, 200)]
+WIDE_TIED = [(70, 130), (130, 70), (140, 140)]
+
+# csrc/assign.hip restated: launch_k's steps of the longer side, kStageBytes, and `transposed = R > T`
+LANE_COLUMNS = ((64, 1), (128, 2), (256, 4), (512, 8), (1024, 16))
+STAGE_BYTES = 48 << 10
+
+
+def variant(shape, itemsize):
+    """(K, staged, transposed) of solve_kernel for a cost of ``shape`` with entries of ``itemsize`` bytes."""
+    n, m = min(shape), max(shape)
+    return next(k for limit, k in LANE_COLUMNS if m <= limit), n * m * itemsize <= STAGE_BYTES, shape[0] > shape[1]
+
+
+# shape -> (the float32 variant, the float64 variant)
+WIDE_VARIANTS = {
+    (150, 150): ((4, False, False), (4, False, False)),
+    (130, 90): ((4, True, True), (4, False, True)),
+    (90, 130): ((4, True, False), (4, False, False)),
+    (200, 260): ((8, False, False), (8, False, False)),
+    (40, 300): ((8, True, False), (8, False, False)),
+    (300, 40): ((8, True, True), (8, False, True)),
+    (513, 70): ((16, False, True), (16, False, True)),
+    (70, 513): ((16, False, False), (16, False, False)),
+}
 
 _CASES = {}
 
@@ -67,7 +97,7 @@ def special_cases():
 
 # ---- oracle ----------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("shape", SHAPES + WIDE, ids=lambda s: "x".join(map(str, s)))
 def test_oracle_gives_scipys_indices_on_generic_costs(shape):
     for k in range(3):
         c, (rows, cols) = generic_case(shape, k)
@@ -76,22 +106,56 @@ def test_oracle_gives_scipys_indices_on_generic_costs(shape):
         assert np.array_equal(got[0], rows) and np.array_equal(got[1], cols), (shape, k)
 
 
-@pytest.mark.parametrize("shape", RANK_ONE, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("shape", RANK_ONE + WIDE_RANK_ONE, ids=lambda s: "x".join(map(str, s)))
 def test_oracle_gives_scipys_indices_on_the_rank_one_family(shape):
     c, (rows, cols) = rank_one_case(shape)
     got = assign_oracle.solve(c)
     assert np.array_equal(got[0], rows) and np.array_equal(got[1], cols)
     n, m = min(shape), max(shape)
     # sorted factors: the optimum pairs the n largest of the long side with the short side in order
-    assert np.array_equal(got[1] if shape[0] <= shape[1] else got[0], np.arange(m - n, m))
+    mine, in_order = got[1] if shape[0] <= shape[1] else got[0], np.arange(m - n, m)
+    if shape in RANK_ONE:
+        assert np.array_equal(mine, in_order)
+    else:
+        # The entries are products rounded to float32.  At these sizes two neighbouring factors can lie closer than that
+        # rounding (129 x 200 has one such pair): the optimum of the rounded cost -- scipy's and the oracle's alike -- may then
+        # exchange neighbours, and is no dearer than the pairing in order.
+        wide = c.astype(np.float64) if shape[0] <= shape[1] else c.astype(np.float64).T
+        assert np.abs(mine - in_order).max() <= 1 and sorted(mine.tolist()) == in_order.tolist()
+        assert wide[np.arange(n), mine].sum() <= wide[np.arange(n), in_order].sum()
 
 
-@pytest.mark.parametrize("shape", TIED, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("shape", TIED + WIDE_TIED, ids=lambda s: "x".join(map(str, s)))
 def test_oracle_total_equals_scipys_on_tied_costs(shape):
     c, (rows, cols), total = tied_case(shape)
     n = min(shape)
     assert len(rows) == n and np.all(np.diff(rows) > 0) and len(set(cols.tolist())) == n
     assert float(c[rows, cols].sum()) == total
+
+
+def test_the_wide_shapes_select_every_variant_of_the_kernel_with_four_or_more_columns_per_lane():
+    """Which (K, staged, transposed) each wide shape runs, from the thresholds of csrc/assign.hip restated above: when one of
+    them moves, this says which variant lost its cases.  The solver's GPU tests run every shape named here in both types,
+    except LIMIT (float32 only)."""
+    source = open(os.path.join(ROOT, "devis_amd", "csrc", "assign.hip")).read()
+    assert "constexpr int kStageBytes = 48 << 10;" in source and "const bool transposed = R > Tn;" in source
+    assert re.findall(r"if \(m <= (\d+)\) return launch<T, (\d+)>", source) == [(str(m), str(k)) for m, k in LANE_COLUMNS[:-1]]
+    assert "return launch<T, 16>" in source and LANE_COLUMNS[-1] == (1024, 16)
+    assert set(WIDE_VARIANTS) == set(WIDE)
+    for shape in WIDE:
+        assert (variant(shape, 4), variant(shape, 8)) == WIDE_VARIANTS[shape], shape
+    assert variant(LIMIT, 4) == (16, False, False)
+    reached = {v for pair in WIDE_VARIANTS.values() for v in pair}
+    # a staged block with 16 columns per lane has a shorter side of at most 23: (1024, 2) and (2, 1024) of SHAPES are those
+    assert variant((1024, 2), 4) == variant((1024, 2), 8) == (16, True, True) and (1024, 2) in SHAPES
+    assert variant((2, 1024), 4) == variant((2, 1024), 8) == (16, True, False) and (2, 1024) in SHAPES
+    for k in (4, 8, 16):
+        for staged in (True, False):
+            for transposed in (True, False):
+                assert (k, staged, transposed) in reached or (k, staged) == (16, True), (k, staged, transposed)
+    # what the other families add: a shorter side above 64 under 2, 4 and more columns per lane, ties across the slots
+    assert [variant(s, 4)[0] for s in WIDE_RANK_ONE] == [4, 4] and [variant(s, 4)[0] for s in WIDE_TIED] == [4, 4, 4]
+    assert all(min(s) > 65 for s in WIDE_RANK_ONE + WIDE_TIED) and {variant(s, 4)[2] for s in WIDE_TIED} == {True, False}
 
 
 def test_oracle_classifies_invalid_and_infeasible_inputs_as_scipy_does():

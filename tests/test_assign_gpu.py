@@ -1,13 +1,16 @@
 """GPU tests of the linear sum assignment solver (include/assign.h): the indices against scipy on the same cost in double --
 with ``==``: the method and its arithmetic are scipy's, so on a cost whose optimum is unique there is nothing to tolerate --
-and against the numpy oracle of tests/assign_oracle.py, which shares the kernel's tie rule, where it is not unique."""
+and against the numpy oracle of tests/assign_oracle.py, which shares the kernel's tie rule, where it is not unique.  The shapes are those
+of tests/test_assign_cpu.py, where WIDE_VARIANTS states which instantiation of the kernel (columns per lane, staged or not,
+transposed or not) each of the wide ones selects."""
 import numpy as np
 import pytest
 import torch
 from scipy.optimize import linear_sum_assignment
 
 import assign_oracle
-from test_assign_cpu import RANK_ONE, SHAPES, TIED, generic_case, rank_one_case, special_cases, tied_case
+from test_assign_cpu import (LIMIT, RANK_ONE, SHAPES, TIED, WIDE, WIDE_RANK_ONE, WIDE_TIED, generic_case, rank_one_case,
+                             special_cases, tied_case)
 from test_boxmatch_cpu import devis_call, load_fixture, modules, same_tensors
 from test_boxmatch_gpu import cost_case, gpu_targets, on_gpu
 
@@ -44,7 +47,7 @@ def assert_pairs(got_rows, got_cols, want, what):
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=ids_of_dtype)
-@pytest.mark.parametrize("shape", SHAPES, ids=ids_of_shape)
+@pytest.mark.parametrize("shape", SHAPES + WIDE, ids=ids_of_shape)
 def test_indices_equal_scipys_for_one_problem_and_for_three(shape, dtype):
     cases = [generic_case(shape, k) if dtype == torch.float32 else float64_case(shape, k) for k in range(3)]
     rows, cols, status = solve(cases[0][0])
@@ -56,11 +59,22 @@ def test_indices_equal_scipys_for_one_problem_and_for_three(shape, dtype):
         assert_pairs(rows[l], cols[l], want, "problem %d of 3" % l)
 
 
+def test_the_largest_problem_equals_scipys():
+    """1024 x 1024 in float32, one problem: 16 columns per lane, none of them dead, and both index fields of the candidate
+    key up to 1023."""
+    c, want = generic_case(LIMIT)
+    rows, cols, status = solve(c)
+    assert rows.shape == cols.shape == (1, 1024) and status.tolist() == [0, 0]
+    assert_pairs(rows[0], cols[0], want, LIMIT)
+    assert int(cols.max()) == 1023 and sorted(cols[0].tolist()) == list(range(1024))
+
+
 @pytest.mark.parametrize("dtype", DTYPES, ids=ids_of_dtype)
-@pytest.mark.parametrize("shape", RANK_ONE + [(300, 25)], ids=ids_of_shape)
+@pytest.mark.parametrize("shape", RANK_ONE + [(300, 25)] + WIDE_RANK_ONE, ids=ids_of_shape)
 def test_the_rank_one_family_is_solved_exactly(shape, dtype):
     """Every augmentation walks the whole matching made so far: n(n+1)/2 steps, the bound of the kernel's counted loops.
-    25 x 300 and 300 x 25 hold several columns per lane in both orientations."""
+    25 x 300 and 300 x 25 hold several columns per lane in both orientations; 130 x 130 and 129 x 200 walk back along a path
+    that crosses the column slots of a lane, with the rows in three rounds of 64 lanes."""
     if shape == (300, 25):
         c = np.ascontiguousarray(rank_one_case((25, 300))[0].T)
         want = linear_sum_assignment(c.astype(np.float64))
@@ -72,7 +86,7 @@ def test_the_rank_one_family_is_solved_exactly(shape, dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=ids_of_dtype)
-@pytest.mark.parametrize("shape", TIED, ids=ids_of_shape)
+@pytest.mark.parametrize("shape", TIED + WIDE_TIED, ids=ids_of_shape)
 def test_tied_costs_equal_the_oracle_and_scipys_total(shape, dtype):
     c, want, total = tied_case(shape)
     rows, cols, status = solve(c.astype(np.float32 if dtype == torch.float32 else np.float64))

@@ -18,9 +18,11 @@ the oracle's two-rounding arithmetic applied to the operator's float32 sine valu
 
 Backward: the gradients the parity test uses are multiples of 1/8 in [-2, 2], so every float32 sum of them is exact in any
 order: the float32 yardstick (autograd of the oracle in float32 on the CPU) does not deviate from the float64 oracle at all,
-the bound of the same kind is ``4 * 0 + 1e-6``, and the segmentation and indexing are checked exactly.  Rounding and order
-are what the bitwise tests are for: with normal random gradients two runs, and a call with the levels permuted, give the
-same bits, within the project's 1e-4 (relative to the largest gradient) of the oracle."""
+the bound of the same kind is ``4 * 0 + 1e-6``, and the segmentation and indexing are checked exactly (three frames of at
+most 2015 tokens: the largest sum stays below 2^24 / 8).  The backward cases cover one and several channel blocks of both
+passes -- 64 channels per workgroup in the partial pass, 256 in the combine pass -- and the largest number of levels.
+Rounding and order are what the bitwise tests are for: with normal random gradients two runs, and a call with the levels
+permuted, give the same bits, within the project's 1e-4 (relative to the largest gradient) of the oracle."""
 import pytest
 import torch
 
@@ -45,6 +47,10 @@ CASES = {
     "23x37": (3, [(23, 37)], 16, True, False),
     "23x37-plain": (3, [(23, 37)], 16, False, True),    # unnormalised: arguments up to 37
     "pyramid": (3, PYRAMID, 16, True, True),            # four levels of unequal size
+    "3x300": (2, [(3, 300)], 8, True, True),            # two column jobs of the counts pass, the second ragged; five chunks a row
+    "2x257": (2, [(2, 257)], 8, True, False),           # the second column job has one lane
+    # POSEMBED_MAX_LEVELS levels: three of equal area, two of those identical
+    "levels8": (3, [(6, 9), (4, 7), (3, 4), (4, 3), (3, 4), (2, 2), (1, 5), (1, 1)], 8, True, True),
 }
 
 
@@ -136,7 +142,7 @@ def test_float32_embedding_is_within_the_yardsticks_error_of_the_oracle(name):
     assert torch.equal(mask_flatten.cpu(), r["oracle"][1]) and float((valid_ratios.cpu() - r["oracle"][2]).abs().max()) <= RATIO_ULPS
 
 
-@pytest.mark.parametrize("name", ["1x1", "2x130", "5x7-c12", "23x37-plain", "pyramid"])
+@pytest.mark.parametrize("name", ["1x1", "2x130", "5x7-c12", "23x37-plain", "pyramid", "levels8"])
 def test_both_layouts_agree(name):
     import devis_amd
     r = reference(name)
@@ -180,7 +186,7 @@ def test_other_settings_and_non_contiguous_masks():
 # ---- 16-bit outputs ----------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("name", ["5x7-c12", "pyramid", "1x1"])
+@pytest.mark.parametrize("name", ["5x7-c12", "pyramid", "1x1", "levels8"])
 def test_16_bit_outputs_are_the_float32_result_rounded_once(name, dtype):
     import devis_amd
     r = reference(name)
@@ -201,16 +207,23 @@ def test_16_bit_outputs_are_the_float32_result_rounded_once(name, dtype):
 
 # ---- backward ----------------------------------------------------------------------------------------------------------------
 
-BACKWARD = {"pyramid": PYRAMID, "chunks": [(40, 50), (3, 5)], "5x7": [(5, 7)]}          # name -> sizes; C = 8, N = 3
+# name -> (sizes, C); N = 3.  The partial pass covers 64 channels per workgroup, the combine pass 256.
+BACKWARD = {
+    "pyramid": (PYRAMID, 8), "chunks": ([(40, 50), (3, 5)], 8), "5x7": ([(5, 7)], 8),
+    "c72": ([(40, 50), (3, 5)], 72),                    # two channel blocks in the partial pass, the second with 8 live lanes
+    "c260": ([(5, 7), (3, 5)], 260),                    # five of them, and two in the combine pass, the second ragged
+    "c256": (PYRAMID, 256),                             # the model's width
+    "levels8": (CASES["levels8"][1], 8),
+}
 
 
 def backward_case(name, exact):
-    sizes = BACKWARD[name]
+    sizes, C = BACKWARD[name]
     g = torch.Generator().manual_seed(len(name))
     masks = [torch.rand(3, h, w, generator=g) < 0.3 for h, w in sizes]
     S = sum(h * w for h, w in sizes)
-    grad = torch.randint(-16, 17, (3, S, 8), generator=g).float() / 8 if exact else torch.randn(3, S, 8, generator=g)
-    return masks, torch.randn(len(sizes), 8, generator=g), torch.randn(3, 8, generator=g), grad
+    grad = torch.randint(-16, 17, (3, S, C), generator=g).float() / 8 if exact else torch.randn(3, S, C, generator=g)
+    return masks, torch.randn(len(sizes), C, generator=g), torch.randn(3, C, generator=g), grad
 
 
 def gradients(masks, level, temporal, grad, want=(True, True), **kw):
@@ -229,6 +242,8 @@ def test_backward_equals_autograd_of_the_oracle(name):
     masks, level, temporal, grad = backward_case(name, exact=True)
     if name == "chunks":
         assert 40 * 50 > 3 * _posembed.tile(_posembed.TILE_TOKENS)         # a segment of several chunks
+    per_block = _posembed.tile(_posembed.TILE_CHANNELS)
+    assert {"c72": 2, "c260": 5, "c256": 4}.get(name, 1) == -(-BACKWARD[name][1] // per_block)      # channel blocks of the partial pass
     lv, tp = level.double().requires_grad_(True), temporal.double().requires_grad_(True)
     posembed_oracle.encoder(masks, lv, tp)[0].backward(grad.double())
     lv32, tp32 = level.clone().requires_grad_(True), temporal.clone().requires_grad_(True)
@@ -265,8 +280,16 @@ def test_gradients_are_bitwise_reproducible_and_do_not_depend_on_the_order_of_th
 
 
 def test_only_the_requested_gradient_is_computed(monkeypatch):
+    only_the_requested_gradient("5x7", monkeypatch)
+
+
+def test_only_the_requested_gradient_is_computed_with_two_channel_blocks(monkeypatch):
+    only_the_requested_gradient("c72", monkeypatch)         # both null-pointer branches of the combine pass, C > 64
+
+
+def only_the_requested_gradient(name, monkeypatch):
     from devis_amd import _posembed
-    masks, level, temporal, grad = backward_case("5x7", exact=True)
+    masks, level, temporal, grad = backward_case(name, exact=True)
     both = gradients(masks, level, temporal, grad)
     seen, real = [], _posembed.backward
     monkeypatch.setattr(_posembed, "backward", lambda code, g, shape, ws, gl, gt: seen.append((gl is not None, gt is not None)) or real(code, g, shape, ws, gl, gt))
