@@ -10,7 +10,7 @@ There is no CPU path and no eager fallback: CPU tensors raise, a failing kernel 
 import torch
 
 from .. import _attmap, _native
-from ._common import _check_device, _require, _workspace
+from ._common import _check_device, _require, _workspace, eager_backward
 
 NEED_Q, NEED_K = _attmap.GRAD_Q, _attmap.GRAD_K
 NEED_ALL = NEED_Q | NEED_K
@@ -91,21 +91,23 @@ def _backward(grad_out, q, k, out, num_heads, scale, grads=NEED_ALL):
     return grad_q, grad_k
 
 
+def setup_context(ctx, inputs, output):
+    q, k, mask, num_heads, scale = inputs[:5]
+    ctx.num_heads, ctx.scale = num_heads, scale
+    ctx.save_for_backward(q, k, output)
+
+
+def backward(run, ctx, grad_out):
+    """The autograd formula; ``run`` is :func:`_backward`, or the backward op with its empty gradients mapped to None."""
+    q, k, out = ctx.saved_tensors
+    grads = grads_mask(ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+    grad_q, grad_k = run(grad_out, q, k, out, ctx.num_heads, ctx.scale, grads)
+    return grad_q, grad_k, None, None, None, None
+
+
 class AttentionMapsFunction(torch.autograd.Function):
     """``attention_maps`` for eager code: ``apply(q, k, mask, num_heads, scale, out_dtype)``.  The backward computes the
     gradients ``ctx.needs_input_grad`` names and no others."""
-
-    @staticmethod
-    def forward(ctx, q, k, mask, num_heads, scale, out_dtype):
-        out = _forward(q, k, mask, num_heads, scale, out_dtype)
-        ctx.num_heads, ctx.scale = num_heads, scale
-        ctx.save_for_backward(q, k, out)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        q, k, out = ctx.saved_tensors
-        grads = grads_mask(ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        grad_q, grad_k = _backward(grad_out, q, k, out, ctx.num_heads, ctx.scale, grads)
-        return grad_q, grad_k, None, None, None, None
+    forward = staticmethod(_forward)
+    setup_context = staticmethod(setup_context)
+    backward = eager_backward(backward, _backward)

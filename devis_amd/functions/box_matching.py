@@ -10,7 +10,7 @@ There is no CPU path and no eager fallback: CPU tensors raise, a failing kernel 
 import torch
 
 from .. import _boxmatch, _native
-from ._common import _check_device, _require
+from ._common import _check_device, _require, eager_backward
 
 L1 = {"mean": _boxmatch.L1_MEAN, "sum": _boxmatch.L1_SUM}
 
@@ -88,19 +88,21 @@ def _backward(grad_l1, grad_giou, src, target):
     return grad_src
 
 
+def setup_context(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def backward(run, ctx, grad_l1, grad_giou):
+    """The autograd formula; ``run`` is :func:`_backward` or the backward op."""
+    if not ctx.needs_input_grad[0]:
+        return None, None
+    src, target = ctx.saved_tensors
+    return run(grad_l1, grad_giou, src, target), None
+
+
 class BoxLossTermsFunction(torch.autograd.Function):
     """``box_loss_terms`` for eager code: ``apply(src [N, 4], target [N, 4])`` -> (l1, giou).  Saves the two inputs as they
     were given.  No backward launch when src needs no gradient."""
-
-    @staticmethod
-    def forward(ctx, src, target):
-        ctx.save_for_backward(src, target)
-        return _forward(src, target)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_l1, grad_giou):
-        if not ctx.needs_input_grad[0]:
-            return None, None
-        src, target = ctx.saved_tensors
-        return _backward(grad_l1, grad_giou, src, target), None
+    forward = staticmethod(_forward)
+    setup_context = staticmethod(setup_context)
+    backward = eager_backward(backward, _backward)

@@ -12,7 +12,7 @@ There is no CPU path and no eager fallback: CPU tensors raise, a failing kernel 
 import torch
 
 from .. import _labelloss, _native
-from ._common import _check_device, _require
+from ._common import _check_device, _require, eager_backward
 
 
 def check_labels(logits, rows, labels, valid):
@@ -66,23 +66,24 @@ def _backward(grad_sum, logits, target_classes, alpha):
     return grad_logits
 
 
+def setup_context(ctx, inputs, output):
+    ctx.alpha = inputs[4]
+    ctx.mark_non_differentiable(output[1], output[2])
+    ctx.save_for_backward(inputs[0], output[2])
+
+
+def backward(run, ctx, grad_sum, grad_counts, grad_classes):
+    """The autograd formula; ``run`` is :func:`_backward` or the backward op."""
+    if not ctx.needs_input_grad[0]:
+        return None, None, None, None, None
+    logits, target_classes = ctx.saved_tensors
+    return run(grad_sum, logits, target_classes, ctx.alpha), None, None, None, None
+
+
 class LabelLossTermsFunction(torch.autograd.Function):
     """``label_loss_terms`` for eager code: ``apply(logits [B, N, C], rows [M], labels [M], valid or None, alpha)`` ->
     (focal_sum, counts, target_classes).  Saves the logits as they were given and target_classes; only focal_sum is
     differentiable.  No backward launch when logits needs no gradient."""
-
-    @staticmethod
-    def forward(ctx, logits, rows, labels, valid, alpha):
-        focal_sum, counts, target_classes = _forward(logits, rows, labels, valid, alpha)
-        ctx.alpha = alpha
-        ctx.save_for_backward(logits, target_classes)
-        ctx.mark_non_differentiable(counts, target_classes)
-        return focal_sum, counts, target_classes
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_sum, grad_counts, grad_classes):
-        if not ctx.needs_input_grad[0]:
-            return None, None, None, None, None
-        logits, target_classes = ctx.saved_tensors
-        return _backward(grad_sum, logits, target_classes, ctx.alpha), None, None, None, None
+    forward = staticmethod(_forward)
+    setup_context = staticmethod(setup_context)
+    backward = eager_backward(backward, _backward)

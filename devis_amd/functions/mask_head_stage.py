@@ -11,7 +11,7 @@ There is no CPU path and no eager fallback: CPU tensors raise, a failing kernel 
 import torch
 
 from .. import _mhstage, _native
-from ._common import _check_device, _require, _workspace
+from ._common import _check_device, _require, _workspace, eager_backward
 
 NEED_X, NEED_WEIGHT, NEED_BIAS, NEED_SKIP = _mhstage.GRAD_X, _mhstage.GRAD_WEIGHT, _mhstage.GRAD_BIAS, _mhstage.GRAD_SKIP
 NEED_EXTRA = 16         # host only: a slice of grad_out
@@ -138,26 +138,31 @@ def grad_extra_of(grad_out, num_channels, extra_dtype):
     return grad_out[:, num_channels:].to(extra_dtype)
 
 
+def setup_context(ctx, inputs, output):
+    x, num_groups, weight, bias, eps, skip, skip_index, extra = inputs[:8]
+    out, mean, rstd = output
+    ctx.num_groups = num_groups
+    ctx.num_skip = 0 if skip is None else skip.shape[0]
+    ctx.extra_dtype = None if extra is None else extra.dtype
+    ctx.mark_non_differentiable(mean, rstd)
+    ctx.save_for_backward(x, weight, bias, mean, rstd, skip_index)
+
+
+def backward(run, ctx, grad_out, grad_mean, grad_rstd):
+    """The autograd formula; ``run`` is :func:`_backward`, or the backward op with its empty gradients mapped to None."""
+    x, weight, bias, mean, rstd, skip_index = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    grads = grads_mask(need[0], need[2], need[3], need[5], need[7])
+    gx, gw, gb, gs = run(grad_out, x, weight, bias, mean, rstd, skip_index, ctx.num_groups, ctx.num_skip, grads)
+    ge = grad_extra_of(grad_out, x.shape[1], ctx.extra_dtype) if grads & NEED_EXTRA else None
+    return gx, None, gw, gb, None, gs, None, ge, None
+
+
 class MaskHeadStageFunction(torch.autograd.Function):
-    """``mask_head_stage`` for eager code: ``apply(x, num_groups, weight, bias, eps, skip, skip_index, extra, out_dtype)``.
-    Saves x, weight, bias, mean, rstd and skip_index -- not out.  The backward computes the gradients
+    """``mask_head_stage`` for eager code: ``apply(x, num_groups, weight, bias, eps, skip, skip_index, extra, out_dtype)`` ->
+    (out, mean, rstd), the last two without a gradient: the formula's ``setup_context`` reads them from the output, as the op's
+    does.  Saves x, weight, bias, mean, rstd and skip_index -- not out.  The backward computes the gradients
     ``ctx.needs_input_grad`` names and no others."""
-
-    @staticmethod
-    def forward(ctx, x, num_groups, weight, bias, eps, skip, skip_index, extra, out_dtype):
-        out, mean, rstd = _forward(x, num_groups, weight, bias, eps, skip, skip_index, extra, out_dtype)
-        ctx.num_groups = num_groups
-        ctx.num_skip = 0 if skip is None else skip.shape[0]
-        ctx.extra_dtype = None if extra is None else extra.dtype
-        ctx.save_for_backward(x, weight, bias, mean, rstd, skip_index)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        x, weight, bias, mean, rstd, skip_index = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        grads = grads_mask(need[0], need[2], need[3], need[5], need[7])
-        gx, gw, gb, gs = _backward(grad_out, x, weight, bias, mean, rstd, skip_index, ctx.num_groups, ctx.num_skip, grads)
-        ge = grad_extra_of(grad_out, x.shape[1], ctx.extra_dtype) if grads & NEED_EXTRA else None
-        return gx, None, gw, gb, None, gs, None, ge, None
+    forward = staticmethod(_forward)
+    setup_context = staticmethod(setup_context)
+    backward = eager_backward(backward, _backward)

@@ -13,7 +13,7 @@ import math
 import torch
 
 from .. import _maskloss, _native
-from ._common import _check_device, _require
+from ._common import _check_device, _require, eager_backward
 
 
 def check_gamma(gamma):
@@ -75,21 +75,25 @@ def _backward(grad_focal, grad_dice, src, target, sums, alpha, gamma):
     return grad_src
 
 
+def setup_context(ctx, inputs, output):
+    src, target, alpha, gamma = inputs
+    ctx.alpha, ctx.gamma = alpha, gamma
+    ctx.mark_non_differentiable(output[2])
+    ctx.save_for_backward(src, target, output[2])
+
+
+def backward(run, ctx, grad_focal, grad_dice, grad_sums):
+    """The autograd formula; ``run`` is :func:`_backward` or the backward op."""
+    if not ctx.needs_input_grad[0]:
+        return None, None, None, None
+    src, target, sums = ctx.saved_tensors
+    return run(grad_focal, grad_dice, src, target, sums, ctx.alpha, ctx.gamma), None, None, None
+
+
 class MaskLossTermsFunction(torch.autograd.Function):
-    """``mask_loss_terms`` for eager code: ``apply(src [N, h, w], target [N, H, W], alpha, gamma)`` -> (focal, dice).  Saves
-    src, target as it was given and the [N, 3] sums.  No backward launch when src needs no gradient."""
-
-    @staticmethod
-    def forward(ctx, src, target, alpha, gamma):
-        focal, dice, sums = _forward(src, target, alpha, gamma)
-        ctx.alpha, ctx.gamma = alpha, gamma
-        ctx.save_for_backward(src, target, sums)
-        return focal, dice
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_focal, grad_dice):
-        if not ctx.needs_input_grad[0]:
-            return None, None, None, None
-        src, target, sums = ctx.saved_tensors
-        return _backward(grad_focal, grad_dice, src, target, sums, ctx.alpha, ctx.gamma), None, None, None
+    """``mask_loss_terms`` for eager code: ``apply(src [N, h, w], target [N, H, W], alpha, gamma)`` -> (focal, dice, sums), the
+    last without a gradient: the formula's ``setup_context`` reads it from the output, as the op's does.  Saves src, target as
+    it was given and the [N, 3] sums.  No backward launch when src needs no gradient."""
+    forward = staticmethod(_forward)
+    setup_context = staticmethod(setup_context)
+    backward = eager_backward(backward, _backward)

@@ -11,7 +11,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _native
-from ._common import _require
+from ._common import _require, none_slot
 
 
 def _check_inputs(named):
@@ -50,9 +50,16 @@ def _im2col_step(batch, im2col_step):
     return step
 
 
-def _forward(value, shapes, lsi, loc, aw, im2col_step, padding_mask=None):
+def _forward(value, shapes, lsi, loc, aw, im2col_step, padding_mask=None, check_spatial_size=False):
     """Host side of the forward (checks, output allocation, the reference's chunk loop): [N, Lq, M*D].  Shared by
-    :class:`MSDeformAttnFunction` and the custom op ``devis_amd::ms_deform_attn_forward`` (devis_amd/ops.py)."""
+    :class:`MSDeformAttnFunction` and the custom op ``devis_amd::ms_deform_attn_forward`` (devis_amd/ops.py).
+    ``check_spatial_size``: assert ``sum(H*W) == value.shape[1]`` as ``MSDeformAttn.forward`` does (ref
+    ms_deform_attn.py:96: a device read per call there), here against the cached host copy of ``shapes`` -- one read per
+    distinct tensor, none inside a HIP-graph capture."""
+    if check_spatial_size:
+        hint = _native.shapes_hint(shapes) if shapes.is_cuda else shapes.reshape(-1).tolist()
+        if hint is not None:
+            assert sum(int(hint[2 * l]) * int(hint[2 * l + 1]) for l in range(len(hint) // 2)) == value.shape[1]
     if padding_mask is not None:
         _require(padding_mask.dtype == torch.bool and padding_mask.device == value.device and
                  padding_mask.numel() == value.shape[0] * value.shape[1], "padding_mask must be a bool [N, S] tensor on value's device")
@@ -129,54 +136,46 @@ def _ops():
     return ops
 
 
+def _setup_attn(ctx, inputs, output):
+    # inputs: the 6 arguments of the reference's apply, the 7 with padding_mask, or the op's 8 (check_spatial_size last)
+    value, shapes, lsi, loc, aw, im2col_step, padding_mask = (tuple(inputs) + (None,))[:7]
+    ctx.im2col_step = im2col_step
+    ctx.save_for_backward(value, shapes, lsi, loc, aw, padding_mask)
+
+
+def _backward_attn(run, ctx, grad_output):
+    """The autograd formula of the operator; ``run`` is :func:`_backward`, or the two backward ops behind its signature
+    (``ops.run_ms_deform_attn_backward``)."""
+    value, shapes, lsi, loc, aw, padding_mask = ctx.saved_tensors
+    needs = ctx.needs_input_grad
+    grads = _grads_mask(needs[0], needs[3], needs[4])
+    grad_value, grad_loc, grad_aw = run(value, shapes, lsi, loc, aw, grad_output, ctx.im2col_step, padding_mask, grads)
+    # one gradient slot per argument of the op, so INCLUDING the optional padding_mask: autograd accepts trailing None
+    # gradients beyond the inputs apply() was given, so the 6-argument (reference) call works with the same tuple
+    return grad_value, None, None, grad_loc if needs[3] else None, grad_aw if needs[4] else None, None, None, None
+
+
 class MSDeformAttnFunction(Function):
     """Same call contract as the reference (``ms_deform_attn_func.py:21-38``):
     ``apply(value[N,S,M,D], spatial_shapes[L,2] i64, level_start_index[L] i64,
     sampling_locations[N,Lq,M,L,P,2], attention_weights[N,Lq,M,L,P], im2col_step) -> [N,Lq,M*D]``;
     gradients for arguments 0, 3 and 4 only; ``once_differentiable``.  Under ``torch.compile`` / ``torch.export``
-    both directions are the custom ops of devis_amd/ops.py (same host code, same kernels)."""
+    both directions are the custom ops of devis_amd/ops.py (same host code, same kernels, same formula)."""
 
     @staticmethod
-    def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations,
-                attention_weights, im2col_step, padding_mask=None):
-        # padding_mask (not in the reference's signature; used by MSDeformAttn only): the bool [N, S] mask `value`
-        # was produced under.  The backward then zeroes the masked rows of ITS grad_value (the gradient of ref
+    def forward(ctx, *inputs):
+        # a 7th argument, padding_mask (not in the reference's signature; used by MSDeformAttn only): the bool [N, S] mask
+        # `value` was produced under.  The backward then zeroes the masked rows of ITS grad_value (the gradient of ref
         # ms_deform_attn.py:102-103's masked_fill) before returning it, and project_value's backward skips that pass.
-        ctx.im2col_step = im2col_step
-        ctx.padding_mask = padding_mask
-        if torch.compiler.is_compiling():
-            output = _ops().ms_deform_attn_forward(value, value_spatial_shapes, value_level_start_index,
-                                                   sampling_locations, attention_weights, im2col_step, padding_mask)
-        else:
-            output = _forward(value, value_spatial_shapes, value_level_start_index, sampling_locations,
-                              attention_weights, im2col_step, padding_mask)
-        ctx.save_for_backward(value, value_spatial_shapes, value_level_start_index,
-                              sampling_locations, attention_weights)
+        output = (_ops().ms_deform_attn_forward if torch.compiler.is_compiling() else _forward)(*inputs)
+        _setup_attn(ctx, inputs, output)
         return output
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
-        value, shapes, lsi, loc, aw = ctx.saved_tensors
-        needs = ctx.needs_input_grad
-        grads = _grads_mask(needs[0], needs[3], needs[4])
-        if torch.compiler.is_compiling():
-            if grads == _native.GRAD_ALL:
-                grad_value, grad_loc, grad_aw = _ops().ms_deform_attn_backward(value, shapes, lsi, loc, aw, grad_output,
-                                                                               ctx.im2col_step, ctx.padding_mask)
-            else:
-                grad_value, grad_loc, grad_aw = _ops().none_slots(_ops().ms_deform_attn_backward_grads(
-                    value, shapes, lsi, loc, aw, grad_output, ctx.im2col_step, grads, ctx.padding_mask))
-        else:
-            grad_value, grad_loc, grad_aw = _backward(value, shapes, lsi, loc, aw, grad_output, ctx.im2col_step,
-                                                      ctx.padding_mask, grads)
-        if not needs[3]:
-            grad_loc = None
-        if not needs[4]:
-            grad_aw = None
-        # one gradient slot per forward argument INCLUDING the optional padding_mask: autograd accepts trailing None
-        # gradients beyond the inputs apply() was given, so the 6-argument (reference) call works with the same tuple
-        return grad_value, None, None, grad_loc, grad_aw, None, None
+        run = _ops().run_ms_deform_attn_backward if torch.compiler.is_compiling() else _backward
+        return _backward_attn(run, ctx, grad_output)
 
 
 def _check_temporal_shapes(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr,
@@ -240,6 +239,20 @@ def _temporal_backward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_
     return grad_value, gloc_c, gaw_c, gloc_t, gaw_t
 
 
+def _setup_temporal(ctx, inputs, output):
+    ctx.clips = inputs[8]
+    ctx.save_for_backward(*inputs[:8])
+
+
+def _backward_temporal(run, ctx, grad_output):
+    """The autograd formula of the fused call; ``run`` is :func:`_temporal_backward`, or the two backward ops behind its
+    signature (``ops.run_temporal_backward``)."""
+    needs = ctx.needs_input_grad
+    grads = _grads_mask(needs[0], *needs[4:8])
+    grad_value, *sampling = run(*ctx.saved_tensors, grad_output, ctx.clips, grads)
+    return (grad_value, None, None, None, *(g if need else None for g, need in zip(sampling, needs[4:8])), None)
+
+
 class MSDeformAttnTemporalFunction(Function):
     """Fused form of the per-frame loop of the temporal modules
     (``ms_deform_attn.py:325-364, 366-404, 435-460``): for each frame t of each clip
@@ -254,29 +267,16 @@ class MSDeformAttnTemporalFunction(Function):
     clips) -> [G, Lq, M*D]`` with ``G = clips*T``."""
 
     @staticmethod
-    def forward(ctx, value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr,
-                loc_temp, aw_temp, clips):
-        fn = _ops().temporal_forward if torch.compiler.is_compiling() else _temporal_forward
-        out = fn(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, loc_temp, aw_temp, clips)
-        ctx.clips = clips
-        ctx.save_for_backward(value, spatial_shapes, level_start_index, frame_table, loc_curr,
-                              aw_curr, loc_temp, aw_temp)
+    def forward(ctx, *inputs):
+        out = (_ops().temporal_forward if torch.compiler.is_compiling() else _temporal_forward)(*inputs)
+        _setup_temporal(ctx, inputs, out)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
-        needs = ctx.needs_input_grad
-        grads = _grads_mask(needs[0], *needs[4:8])
-        if not torch.compiler.is_compiling():
-            grad_value, gloc_c, gaw_c, gloc_t, gaw_t = _temporal_backward(*ctx.saved_tensors, grad_output, ctx.clips, grads)
-        elif grads == _native.GRAD_ALL:
-            grad_value, gloc_c, gaw_c, gloc_t, gaw_t = _ops().temporal_backward(*ctx.saved_tensors, grad_output, ctx.clips)
-        else:
-            grad_value, gloc_c, gaw_c, gloc_t, gaw_t = _ops().none_slots(
-                _ops().temporal_backward_grads(*ctx.saved_tensors, grad_output, ctx.clips, grads))
-        sampling = [g if need else None for g, need in zip((gloc_c, gaw_c, gloc_t, gaw_t), needs[4:8])]
-        return (grad_value, None, None, None, *sampling, None)
+        run = _ops().run_temporal_backward if torch.compiler.is_compiling() else _temporal_backward
+        return _backward_temporal(run, ctx, grad_output)
 
 
 def ms_deform_attn_core_pytorch(value, value_spatial_shapes, sampling_locations, attention_weights):
@@ -500,13 +500,24 @@ def _prep_forward(off_c, off_t, logit_c, logit_t, ref_c, ref_t, shapes, loc32=Fa
     return (loc_c, loc_t, aw_c, aw_t), (ref_c, ref_t, off_c, off_t)
 
 
-def _prep_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, ref_c, ref_t, shapes, off_c, off_t, ref_dtypes,
-                   need_ref_c, need_ref_t):
-    """Host side of :class:`MSDeformPrepFunction`'s backward (``ref_c`` / ``ref_t`` / ``off_c`` / ``off_t`` as
-    :func:`_prep_forward` returned them): (goff_c, goff_t, glogit_c, glogit_t, gref_c, gref_t)."""
+def _prep_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, off_c, off_t, ref_c, ref_t, shapes, loc32=False,
+                   need_ref_c=True, need_ref_t=True):
+    """Host side of :class:`MSDeformPrepFunction`'s backward, with the arguments of the op ``prep_backward``: (goff_c, goff_t,
+    glogit_c, glogit_t, gref_c, gref_t), a gradient that does not exist or is not asked for (``need_ref_*``) None, the
+    reference points' in the dtype of the ``ref_*`` given.  ``off_*`` / ``ref_*`` are the forward's inputs as they were given
+    (the op's autograd formula saves those), or as :func:`_prep_forward` returned them (the eager Function's): the conversions
+    below then return their argument, and nothing is copied or cast a second time.  A tensor with 0 slots stands for None."""
+    off_t, aw_t = none_slot(off_t), none_slot(aw_t)
     R, M, L, Pc, _ = off_c.shape
     W = 0 if off_t is None else off_t.shape[2] // L
     Pt = 1 if off_t is None else off_t.shape[3]
+    gloc_c, gaw_c = none_slot(gloc_c), none_slot(gaw_c)
+    gloc_t, gaw_t = (none_slot(gloc_t), none_slot(gaw_t)) if W else (None, None)
+    aw_c, aw_t = aw_c.contiguous(), None if aw_t is None else aw_t.contiguous()
+    ref_dtypes = (ref_c.dtype, _dtype_of(ref_t))
+    ref_c, ref_t = _check_prep_inputs(off_c, (("reference_points", ref_c), ("temporal reference_points", ref_t if W else None)),
+                                      shapes, aw_c.dtype)
+    off_c, off_t = off_c.contiguous(), None if off_t is None else off_t.contiguous()
     zeros = lambda like: torch.zeros_like(like, dtype=aw_c.dtype)        # (the sampling-side dtype: see _sampling_dtype)
     gloc_c = zeros(off_c) if gloc_c is None else gloc_c.contiguous()
     gaw_c = zeros(aw_c) if gaw_c is None else gaw_c.contiguous()
@@ -527,6 +538,38 @@ def _dtype_of(t):
     return t.dtype if isinstance(t, torch.Tensor) else None
 
 
+def _temporal_or_none(output, temporal):
+    """(loc_c, loc_t, aw_c, aw_t) of a prep Function: without a temporal part the op's 0-slot ``loc_t`` / ``aw_t`` are None."""
+    return output if temporal else (output[0], None, output[2], None)
+
+
+# What the two prep formulas save.  A ``setup_context`` sees inputs and outputs only, and the op's saves the inputs as they
+# were given; its backward op converts them again.  The eager Functions hand over (``converted``) what the forward's host
+# code made of them -- reference points cast to the sampling dtype, everything contiguous -- and save that in their place, so
+# that an eager backward casts and copies nothing a second time (the modules' reference points are float32 also beside a
+# 16-bit model, where the cast is real).  The original dtypes of the reference points, which their gradients take, are kept
+# either way.
+
+def _setup_prep(ctx, inputs, output, converted=None):
+    off_c, off_t, logit_c, logit_t, ref_c, ref_t, shapes, loc32 = inputs
+    ctx.loc32 = loc32
+    ctx.ref_dtypes = (_dtype_of(ref_c), _dtype_of(ref_t))
+    if converted is not None:
+        ref_c, ref_t, off_c, off_t = converted
+    ctx.save_for_backward(output[2], output[3], off_c, off_t, ref_c, ref_t, shapes)
+
+
+def _backward_prep(run, ctx, gloc_c, gloc_t, gaw_c, gaw_t):
+    """The autograd formula of the pre-op pass; ``run`` is :func:`_prep_backward` or the op ``prep_backward``."""
+    aw_c, aw_t, off_c, off_t, ref_c, ref_t, shapes = ctx.saved_tensors
+    w = off_t is not None
+    nc, nt = ctx.needs_input_grad[4], w and ref_t is not None and ctx.needs_input_grad[5]
+    goff_c, goff_t, glogit_c, glogit_t, gref_c, gref_t = run(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, off_c, off_t, ref_c,
+                                                             ref_t, shapes, ctx.loc32, nc, nt)
+    return (goff_c, goff_t if w else None, glogit_c, glogit_t if w else None,
+            gref_c.to(ctx.ref_dtypes[0]) if nc else None, gref_t.to(ctx.ref_dtypes[1]) if nt else None, None, None)
+
+
 class MSDeformPrepFunction(Function):
     """Joint softmax + sampling-location arithmetic of the (temporal) modules as one fused pass each way
     (include/msda.h msda_prep_forward/backward).
@@ -538,34 +581,18 @@ class MSDeformPrepFunction(Function):
 
     @staticmethod
     def forward(ctx, off_c, off_t, logit_c, logit_t, ref_c, ref_t, shapes, loc32=False):
-        ctx.ref_dtypes = (_dtype_of(ref_c), _dtype_of(ref_t))
+        inputs = (off_c, off_t, logit_c, logit_t, ref_c, ref_t, shapes, loc32)
         if torch.compiler.is_compiling():
-            ctx.loc32 = loc32
-            loc_c, loc_t, aw_c, aw_t = _ops().prep_forward(off_c, off_t, logit_c, logit_t, ref_c, ref_t, shapes, loc32)
-            if off_t is None:
-                loc_t = aw_t = None
-            ctx.save_for_backward(aw_c, aw_t, ref_c, ref_t, shapes, off_c, off_t)
-            return loc_c, loc_t, aw_c, aw_t
-        (loc_c, loc_t, aw_c, aw_t), (ref_c, ref_t, off_c, off_t) = _prep_forward(off_c, off_t, logit_c, logit_t,
-                                                                                   ref_c, ref_t, shapes, loc32)
-        ctx.save_for_backward(aw_c, aw_t, ref_c, ref_t, shapes, off_c, off_t)
-        return loc_c, loc_t, aw_c, aw_t
+            output, converted = _ops().prep_forward(*inputs), None
+        else:
+            output, converted = _prep_forward(*inputs)
+        _setup_prep(ctx, inputs, output, converted)
+        return _temporal_or_none(output, off_t is not None)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, gloc_c, gloc_t, gaw_c, gaw_t):
-        if torch.compiler.is_compiling():
-            aw_c, aw_t, ref_c, ref_t, shapes, off_c, off_t = ctx.saved_tensors
-            goff_c, goff_t, glogit_c, glogit_t, gref_c, gref_t = _ops().prep_backward(
-                gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, off_c, off_t, ref_c, ref_t, shapes, ctx.loc32,
-                ctx.needs_input_grad[4], ctx.needs_input_grad[5])
-            if off_t is None:
-                goff_t = glogit_t = None
-            return (goff_c, goff_t, glogit_c, glogit_t, gref_c if ctx.needs_input_grad[4] else None,
-                    gref_t if (off_t is not None and ctx.needs_input_grad[5]) else None, None, None)
-        aw_c, aw_t, ref_c, ref_t, shapes, off_c, off_t = ctx.saved_tensors
-        return _prep_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, ref_c, ref_t, shapes, off_c, off_t,
-                              ctx.ref_dtypes, ctx.needs_input_grad[4], ctx.needs_input_grad[5]) + (None, None)
+    def backward(ctx, *grads):
+        return _backward_prep(_ops().prep_backward if torch.compiler.is_compiling() else _prep_backward, ctx, *grads)
 
 
 def _prep_fused_cols(M, L, W, Pc, Pt):
@@ -598,10 +625,20 @@ def _prep_fused_forward(y, ref_c, ref_t, shapes, M, L, W, Pc, Pt, loc32=False):
     return (loc_c, loc_t, aw_c, aw_t), (ref_c, ref_t, y)
 
 
-def _prep_fused_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, ref_c, ref_t, shapes, y, M, L, W, Pc, Pt,
-                         ref_dtypes, need_ref_c, need_ref_t):
-    """Host side of :class:`MSDeformPrepFusedFunction`'s backward: (gy, gref_c, gref_t)."""
+def _prep_fused_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, y, ref_c, ref_t, shapes, M, L, W, Pc, Pt, loc32=False,
+                         need_ref_c=True, need_ref_t=True):
+    """Host side of :class:`MSDeformPrepFusedFunction`'s backward, with the arguments of the op ``prep_fused_backward``: (gy,
+    gref_c, gref_t), a reference-point gradient that does not exist or is not asked for None.  ``y`` / ``ref_*`` as the forward
+    was given them or as :func:`_prep_fused_forward` returned them, as in :func:`_prep_backward`."""
     R = y.shape[0]
+    if y.stride(1) != 1:
+        y = y.contiguous()
+    if not W:
+        gloc_t = gaw_t = aw_t = None
+    aw_c, aw_t = aw_c.contiguous(), None if aw_t is None else aw_t.contiguous()
+    ref_dtypes = (ref_c.dtype, _dtype_of(ref_t))
+    ref_c, ref_t = _check_prep_inputs(y, (("reference_points", ref_c), ("temporal reference_points", ref_t if W else None)),
+                                      shapes, aw_c.dtype)
     cols = _prep_fused_cols(M, L, W, Pc, Pt)
     gloc_c = torch.zeros_like(aw_c).unsqueeze(-1).repeat(1, 1, 1, 1, 2) if gloc_c is None else gloc_c.contiguous()
     gaw_c = torch.zeros_like(aw_c) if gaw_c is None else gaw_c.contiguous()
@@ -617,6 +654,25 @@ def _prep_fused_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, ref_c, ref_t,
     return gy, gref_c, gref_t
 
 
+def _setup_prep_fused(ctx, inputs, output, converted=None):
+    y, ref_c, ref_t, shapes, M, L, W, Pc, Pt, loc32 = inputs
+    ctx.dims = (M, L, W, Pc, Pt, loc32)
+    ctx.ref_dtypes = (_dtype_of(ref_c), _dtype_of(ref_t))
+    if converted is not None:       # (the eager Function's: see _setup_prep)
+        ref_c, ref_t, y = converted
+    ctx.save_for_backward(output[2], output[3], y, ref_c, ref_t, shapes)
+
+
+def _backward_prep_fused(run, ctx, gloc_c, gloc_t, gaw_c, gaw_t):
+    """The autograd formula of the pre-op pass on one matrix; ``run`` is :func:`_prep_fused_backward` or the op
+    ``prep_fused_backward``."""
+    aw_c, aw_t, y, ref_c, ref_t, shapes = ctx.saved_tensors
+    M, L, W, Pc, Pt, loc32 = ctx.dims
+    nc, nt = ctx.needs_input_grad[1], bool(W) and ref_t is not None and ctx.needs_input_grad[2]
+    gy, gref_c, gref_t = run(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, y, ref_c, ref_t, shapes, M, L, W, Pc, Pt, loc32, nc, nt)
+    return (gy, gref_c.to(ctx.ref_dtypes[0]) if nc else None, gref_t.to(ctx.ref_dtypes[1]) if nt else None) + (None,) * 7
+
+
 class MSDeformPrepFusedFunction(Function):
     """:class:`MSDeformPrepFunction` reading the offsets and logits as column slices of ONE matrix
     ``y [R, M*L*Pc*2 + M*W*L*Pt*2 + M*L*Pc + M*W*L*Pt]`` -- the output of the module's four query-side Linears
@@ -628,34 +684,16 @@ class MSDeformPrepFusedFunction(Function):
 
     @staticmethod
     def forward(ctx, y, ref_c, ref_t, shapes, M, L, W, Pc, Pt, loc32=False):
-        ctx.ref_dtypes = (_dtype_of(ref_c), _dtype_of(ref_t))
-        ctx.dims = (M, L, W, Pc, Pt)
+        inputs = (y, ref_c, ref_t if W else None, shapes, M, L, W, Pc, Pt, loc32)
         if torch.compiler.is_compiling():
-            ctx.loc32 = loc32
-            ref_t = ref_t if W else None
-            loc_c, loc_t, aw_c, aw_t = _ops().prep_fused_forward(y, ref_c, ref_t, shapes, M, L, W, Pc, Pt, loc32)
-            if not W:
-                loc_t = aw_t = None
-            ctx.save_for_backward(aw_c, aw_t, ref_c, ref_t, shapes, y)
-            return loc_c, loc_t, aw_c, aw_t
-        (loc_c, loc_t, aw_c, aw_t), (ref_c, ref_t, y) = _prep_fused_forward(y, ref_c, ref_t, shapes, M, L, W, Pc, Pt,
-                                                                            loc32)
-        ctx.save_for_backward(aw_c, aw_t, ref_c, ref_t, shapes, y)
-        return loc_c, loc_t, aw_c, aw_t
+            output, converted = _ops().prep_fused_forward(*inputs), None
+        else:
+            output, converted = _prep_fused_forward(*inputs)
+        _setup_prep_fused(ctx, inputs, output, converted)
+        return _temporal_or_none(output, bool(W))
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, gloc_c, gloc_t, gaw_c, gaw_t):
-        M, L, W, Pc, Pt = ctx.dims
-        if torch.compiler.is_compiling():
-            aw_c, aw_t, ref_c, ref_t, shapes, y = ctx.saved_tensors
-            gy, gref_c, gref_t = _ops().prep_fused_backward(
-                gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, y, ref_c, ref_t, shapes, M, L, W, Pc, Pt, ctx.loc32,
-                ctx.needs_input_grad[1], bool(W) and ctx.needs_input_grad[2])
-            return (gy, gref_c if ctx.needs_input_grad[1] else None, gref_t if (W and ctx.needs_input_grad[2]) else None,
-                    None, None, None, None, None, None, None)
-        aw_c, aw_t, ref_c, ref_t, shapes, y = ctx.saved_tensors
-        gy, gref_c, gref_t = _prep_fused_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, ref_c, ref_t, shapes, y,
-                                                  M, L, W, Pc, Pt, ctx.ref_dtypes, ctx.needs_input_grad[1],
-                                                  ctx.needs_input_grad[2])
-        return gy, gref_c, gref_t, None, None, None, None, None, None, None
+    def backward(ctx, *grads):
+        run = _ops().prep_fused_backward if torch.compiler.is_compiling() else _prep_fused_backward
+        return _backward_prep_fused(run, ctx, *grads)

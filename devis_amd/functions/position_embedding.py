@@ -15,7 +15,7 @@ import math
 import torch
 
 from .. import _native, _posembed
-from ._common import _check_device, _require
+from ._common import _check_device, _require, eager_backward
 
 OUT_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 ROUND_DTYPES = (torch.bfloat16, torch.float16)
@@ -172,29 +172,42 @@ def _encoder_backward(grad, heights, widths, want_level, want_temporal):
     return grad_level, grad_temporal
 
 
+def setup_context(ctx, inputs, output):
+    masks, level_embed, temporal_embed = inputs[:3]
+    ctx.heights, ctx.widths = [m.shape[1] for m in masks], [m.shape[2] for m in masks]
+    ctx.dtypes = (level_embed.dtype, None if temporal_embed is None else temporal_embed.dtype)
+    ctx.mark_non_differentiable(output[1], output[2])
+
+
+def backward(run, ctx, grad_pos, grad_mask, grad_ratios, embeds_at=1):
+    """The autograd formula, for the op's argument order; ``run`` is :func:`_encoder_backward` or the backward op.
+    ``embeds_at``: where ``level_embed`` sits among the arguments, ``temporal_embed`` following it (1 for the op)."""
+    needs = ctx.needs_input_grad
+    want_level, want_temporal = needs[embeds_at], needs[embeds_at + 1] and ctx.dtypes[1] is not None
+    grads = [[None] * len(n) if isinstance(n, list) else None for n in needs]      # (the op's list of masks: a list of None)
+    if want_level or want_temporal:
+        grad_level, grad_temporal = run(grad_pos, ctx.heights, ctx.widths, want_level, want_temporal)
+        grads[embeds_at] = grad_level.to(ctx.dtypes[0]) if want_level else None
+        grads[embeds_at + 1] = grad_temporal.to(ctx.dtypes[1]) if want_temporal else None
+    return tuple(grads)
+
+
 class EncoderPositionEmbeddingFunction(torch.autograd.Function):
     """``encoder_position_embedding`` for eager code: ``apply(level_embed, temporal_embed or None, num_pos_feats, temperature,
     normalize, scale, round_dtype, out_dtype, *masks)`` -> (pos, mask_flatten, valid_ratios).  Only ``pos`` is
     differentiable, and only with respect to the two embeddings; the backward computes the gradients autograd asks for, and
     launches nothing when it asks for none."""
 
-    @staticmethod
-    def forward(ctx, level_embed, temporal_embed, num_pos_feats, temperature, normalize, scale, round_dtype, out_dtype, *masks):
-        pos, mask_flatten, valid_ratios = _encoder(list(masks), level_embed, temporal_embed, num_pos_feats, temperature,
-                                                   normalize, scale, round_dtype, out_dtype)
-        ctx.sizes = [(m.shape[1], m.shape[2]) for m in masks]
-        ctx.dtypes = (level_embed.dtype, None if temporal_embed is None else temporal_embed.dtype)
-        ctx.mark_non_differentiable(mask_flatten, valid_ratios)
-        return pos, mask_flatten, valid_ratios
+    # The index adapter: ``apply`` takes the masks last and one by one, since a Function does not see tensors inside a list,
+    # while the formula is written for the op's arguments (``masks`` as a list, first).  forward and setup_context move them to
+    # the front; the backward is told that the embeddings sit at argument 0 here, not 1.
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_pos, grad_mask, grad_ratios):
-        want_level, want_temporal = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and ctx.dtypes[1] is not None
-        nothing = (None,) * (8 + len(ctx.sizes))
-        if not (want_level or want_temporal):
-            return nothing
-        grad_level, grad_temporal = _encoder_backward(grad_pos, [h for h, _ in ctx.sizes], [w for _, w in ctx.sizes],
-                                                      want_level, want_temporal)
-        return (grad_level.to(ctx.dtypes[0]) if want_level else None,
-                grad_temporal.to(ctx.dtypes[1]) if want_temporal else None) + nothing[2:]
+    def forward(*args):
+        return _encoder(list(args[8:]), *args[:8])
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        setup_context(ctx, (inputs[8:],) + inputs[:8], output)
+
+    backward = eager_backward(backward, _encoder_backward, embeds_at=0)

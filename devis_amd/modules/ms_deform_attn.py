@@ -207,12 +207,10 @@ class MSDeformAttn(_FusedParamsCache, nn.Module):
             weights = weights.view(N, Len_q, M, L, P)
             locations = _locations(reference_points[:, :, None, :, None, :], offsets,
                                    _normalizer(input_spatial_shapes), P)
-        if compiling:
-            output = _ops.ms_deform_attn_forward(value, input_spatial_shapes, input_level_start_index, locations.contiguous(),
-                                                 weights.contiguous(), self.im2col_step, input_padding_mask, True)
-        else:
-            output = MSDeformAttnFunction.apply(value, input_spatial_shapes, input_level_start_index, locations.contiguous(),
-                                                weights.contiguous(), self.im2col_step, input_padding_mask)
+        # the last argument (check_spatial_size): the operator's host code makes the assert of ref :96 as well -- under
+        # torch.compile / export when the custom op runs; in eager a second time, from the same cached host copy
+        output = MSDeformAttnFunction.apply(value, input_spatial_shapes, input_level_start_index, locations.contiguous(),
+                                            weights.contiguous(), self.im2col_step, input_padding_mask, True)
         output = self.output_proj(output)
         _flush_offset_checks(output)
         return output, None

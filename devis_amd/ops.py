@@ -1,9 +1,17 @@
 """The operator as ``torch.library`` custom ops (namespace ``devis_amd``), for ``torch.compile`` and ``torch.export``.
 
-Eager attention code never dispatches through these (the deformable convolution, which has no other path, always does): the autograd Functions of :mod:`devis_amd.functions` and the modules call the
-host code directly and switch to the ops only while ``torch.compiler.is_compiling()`` (Dynamo tracing, or export).  To the
-compiler each op is one opaque node whose implementation is that same host code -- the same checks, the same kernels
-through the C ABI, the same numbers -- and whose fake implementation gives shapes and dtypes only:
+This module holds the op definitions, their fake implementations and the public wrappers.  Eager code never dispatches
+through the ops (the deformable convolution, which has no other path, always does): the wrappers here call the autograd
+Functions of :mod:`devis_amd.functions` and switch to the ops only while ``torch.compiler.is_compiling()`` (Dynamo tracing, or
+export); the modules always call the four attention Functions, each of which picks the op or the host function once per
+direction.  To the compiler each op is one opaque node whose implementation is that same host code -- the same checks, the same
+kernels through the C ABI, the same numbers -- and whose fake implementation gives shapes and dtypes only.
+
+An operator's autograd formula is written once, next to its host code in ``devis_amd/functions/<op>.py``: a
+``setup_context(ctx, inputs, output)`` and a ``backward(run, ctx, *grads)`` whose ``run`` computes the gradients.  The eager
+Function binds ``run`` to the host function; ``register_autograd`` here binds it to the backward op (``op_runner``: the
+0-element tensors that stand for gradients not computed become None again).  Nothing in this module says what is saved or
+where a gradient goes -- except for the deformable convolution, whose only formula is here.  The ops:
 
 =============================  ==========================================================================================
 ``ms_deform_attn_forward``     ``MSDeformAttnFunction`` forward (the im2col chunk loop), + the module's ``sum(H*W) == S``
@@ -53,14 +61,15 @@ through the C ABI, the same numbers -- and whose fake implementation gives shape
 
 Everything that reads the host or keeps Python state -- the ``spatial_shapes`` host hint, the frame-table cache, the
 deferred verdicts of the temporal-offset range checks -- runs inside the implementations, at run time, never in a traced
-graph.  The implementations look ``_native`` and ``ms_deform_attn_func._check_inputs`` up at call time.  The forward ops
-carry their autograd formula (the backward op); a second derivative raises, as ``once_differentiable`` does in eager.
+graph.  The implementations look ``_native`` and ``ms_deform_attn_func._check_inputs`` up at call time.  The backward ops
+carry no formula of their own: a second derivative raises, as ``once_differentiable`` does in eager.
 Every op is tagged ``needs_fixed_stride_order``: Inductor hands over the strides eager would (e.g. the padded rows of
 ``value``) instead of contiguous copies.
 
 When the package is imported a second time under another name (DeVIS's ``src.models.ops``), that copy registers its ops
 under a namespace of its own (``devis_amd_src_models_ops``), bound to its own ``_native``.
 """
+import functools
 import re
 from typing import List, Optional
 
@@ -80,6 +89,7 @@ from .functions import mask_losses as _L
 from .functions import mask_rle as _R
 from .functions import ms_deform_attn_func as _F
 from .functions import position_embedding as _P
+from .functions._common import fill_slots, none_slots, op_runner
 
 
 def _namespace():
@@ -111,11 +121,8 @@ def ms_deform_attn_forward(value: Tensor, spatial_shapes: Tensor, level_start_in
                            check_spatial_size: bool = False) -> Tensor:
     """``MSDeformAttnFunction.forward``.  ``check_spatial_size``: assert ``sum(H*W) == value.shape[1]`` as
     ``MSDeformAttn.forward`` does (ref ms_deform_attn.py:96), from the cached host copy of ``spatial_shapes``."""
-    if check_spatial_size:
-        hint = _native.shapes_hint(spatial_shapes) if spatial_shapes.is_cuda else spatial_shapes.reshape(-1).tolist()
-        if hint is not None:
-            assert sum(int(hint[2 * l]) * int(hint[2 * l + 1]) for l in range(len(hint) // 2)) == value.shape[1]
-    return _F._forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step, padding_mask)
+    return _F._forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step, padding_mask,
+                       check_spatial_size)
 
 
 @ms_deform_attn_forward.register_fake
@@ -158,7 +165,7 @@ def ms_deform_attn_backward_grads(value: Tensor, spatial_shapes: Tensor, level_s
                       ("sampling_loc", sampling_loc), ("attn_weight", attn_weight)])
     out = _F._backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step,
                        padding_mask, grads)
-    return _fill_slots(out, _fake_backward_grads(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
+    return fill_slots(out, _fake_backward_grads(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
                                                  grad_output, im2col_step, grads, padding_mask))
 
 
@@ -172,35 +179,15 @@ def _fake_backward_grads(value, spatial_shapes, level_start_index, sampling_loc,
             _empty(attn_weight, attn_weight.shape if s else (0,)))
 
 
-def _fill_slots(outputs, fakes):
-    """A custom op returns tensors: the None of a group that was not computed becomes its 0-element stand-in."""
-    return tuple(fake if t is None else t for t, fake in zip(outputs, fakes))
-
-
-def none_slots(outputs):
-    """Inverse of _fill_slots for the autograd formulas: 0-element gradient tensors -> None."""
-    return tuple(_none_slot(t) for t in outputs)
-
-
-def _setup_forward(ctx, inputs, output):
-    value, shapes, lsi, loc, aw, im2col_step, padding_mask = inputs[:7]
-    ctx.im2col_step = im2col_step
-    ctx.save_for_backward(value, shapes, lsi, loc, aw, padding_mask)
-
-
-def _backward_forward(ctx, grad_output):
-    value, shapes, lsi, loc, aw, padding_mask = ctx.saved_tensors
-    needs = ctx.needs_input_grad
-    grads = _F._grads_mask(needs[0], needs[3], needs[4])
+def run_ms_deform_attn_backward(value, shapes, lsi, loc, aw, grad_output, im2col_step, padding_mask, grads):
+    """The two backward ops behind the signature of ``_F._backward``: what the formula runs in a compiled graph."""
     if grads == _native.GRAD_ALL:
-        gv, gl, ga = ms_deform_attn_backward(value, shapes, lsi, loc, aw, grad_output, ctx.im2col_step, padding_mask)
-    else:
-        gv, gl, ga = none_slots(ms_deform_attn_backward_grads(value, shapes, lsi, loc, aw, grad_output, ctx.im2col_step,
-                                                              grads, padding_mask))
-    return gv, None, None, gl if needs[3] else None, ga if needs[4] else None, None, None, None
+        return ms_deform_attn_backward(value, shapes, lsi, loc, aw, grad_output, im2col_step, padding_mask)
+    return none_slots(ms_deform_attn_backward_grads(value, shapes, lsi, loc, aw, grad_output, im2col_step, grads, padding_mask))
 
 
-ms_deform_attn_forward.register_autograd(_backward_forward, setup_context=_setup_forward)
+ms_deform_attn_forward.register_autograd(functools.partial(_F._backward_attn, run_ms_deform_attn_backward),
+                                         setup_context=_F._setup_attn)
 
 
 # ---- MSDeformAttnTemporalFunction ----------------------------------------------------------------------------------
@@ -249,7 +236,7 @@ def temporal_backward_grads(value: Tensor, spatial_shapes: Tensor, level_start_i
                       ("aw_temp", aw_temp)])
     out = _F._temporal_backward(value, spatial_shapes, level_start_index, frame_table, loc_curr, aw_curr, loc_temp,
                                 aw_temp, grad_output, clips, grads)
-    return _fill_slots(out, _fake_temporal_backward_grads(value, spatial_shapes, level_start_index, frame_table, loc_curr,
+    return fill_slots(out, _fake_temporal_backward_grads(value, spatial_shapes, level_start_index, frame_table, loc_curr,
                                                           aw_curr, loc_temp, aw_temp, grad_output, clips, grads))
 
 
@@ -263,34 +250,20 @@ def _fake_temporal_backward_grads(value, spatial_shapes, level_start_index, fram
                                                                for t in (loc_curr, aw_curr, loc_temp, aw_temp))
 
 
-def _setup_temporal(ctx, inputs, output):
-    ctx.clips = inputs[8]
-    ctx.save_for_backward(*inputs[:8])
+def run_temporal_backward(*args):
+    """The two backward ops behind the signature of ``_F._temporal_backward`` (``grads`` last)."""
+    if args[-1] == _native.GRAD_ALL:
+        return temporal_backward(*args[:-1])
+    return none_slots(temporal_backward_grads(*args))
 
 
-def _backward_temporal(ctx, grad_output):
-    value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t = ctx.saved_tensors
-    needs = ctx.needs_input_grad
-    grads = _F._grads_mask(needs[0], *needs[4:8])
-    if grads == _native.GRAD_ALL:
-        gv, glc, gac, glt, gat = temporal_backward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_output, ctx.clips)
-    else:
-        gv, glc, gac, glt, gat = none_slots(temporal_backward_grads(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t,
-                                                                    grad_output, ctx.clips, grads))
-    sampling = [g if need else None for g, need in zip((glc, gac, glt, gat), needs[4:8])]
-    return (gv, None, None, None, *sampling, None)
-
-
-temporal_forward.register_autograd(_backward_temporal, setup_context=_setup_temporal)
+temporal_forward.register_autograd(functools.partial(_F._backward_temporal, run_temporal_backward),
+                                   setup_context=_F._setup_temporal)
 
 
 # ---- MSDeformPrepFunction ------------------------------------------------------------------------------------------
 # Outputs that do not exist without a temporal part (loc_t, aw_t and their gradients) are tensors with 0 slots here:
 # a custom op returns tensors, not None.
-
-def _none_slot(t):
-    return t if t is not None and t.numel() else None
-
 
 def _prep_dims(off_c, off_t):
     R, M, L, Pc, _ = off_c.shape
@@ -328,19 +301,8 @@ def prep_backward(gloc_c: Optional[Tensor], gloc_t: Optional[Tensor], gaw_c: Opt
     """``MSDeformPrepFunction.backward`` from the forward's INPUTS (``off_*``, ``ref_*`` as given) and ``aw_*`` outputs:
     (grad_off_c, grad_off_t, grad_logit_c, grad_logit_t, grad_ref_c, grad_ref_t); a reference-point gradient that is
     not asked for (``need_ref_*``) comes back with 0 elements."""
-    off_t, aw_t = _none_slot(off_t), _none_slot(aw_t)
-    aw_c, aw_t = aw_c.contiguous(), None if aw_t is None else aw_t.contiguous()
-    ref_dtypes = (ref_c.dtype, None if ref_t is None else ref_t.dtype)
-    W = _prep_dims(off_c, off_t)[3]
-    sdt = aw_c.dtype
-    ref_c2, ref_t2 = _F._check_prep_inputs(off_c, (("reference_points", ref_c),
-                                                   ("temporal reference_points", ref_t if W else None)), spatial_shapes, sdt)
-    g = _F._prep_backward(_none_slot(gloc_c), _none_slot(gloc_t) if W else None, _none_slot(gaw_c),
-                          _none_slot(gaw_t) if W else None, aw_c, aw_t, ref_c2, ref_t2, spatial_shapes, off_c.contiguous(),
-                          None if off_t is None else off_t.contiguous(), ref_dtypes, need_ref_c, need_ref_t)
-    fake = _fake_prep_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, off_c, off_t, ref_c, ref_t, spatial_shapes,
-                               loc32, need_ref_c, need_ref_t)
-    return tuple(f if x is None else x for x, f in zip(g, fake))
+    args = (gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, off_c, off_t, ref_c, ref_t, spatial_shapes, loc32, need_ref_c, need_ref_t)
+    return fill_slots(_F._prep_backward(*args), _fake_prep_backward(*args))
 
 
 @prep_backward.register_fake
@@ -353,23 +315,7 @@ def _fake_prep_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, off_c, off_t, 
             _empty(ref_c if ref_t is None else ref_t, (R, W * L, d) if (W and need_ref_t) else (0,)))
 
 
-def _setup_prep(ctx, inputs, output):
-    off_c, off_t, logit_c, logit_t, ref_c, ref_t, shapes, loc32 = inputs
-    ctx.loc32 = loc32
-    ctx.save_for_backward(output[2], output[3], off_c, off_t, ref_c, ref_t, shapes)
-
-
-def _backward_prep(ctx, gloc_c, gloc_t, gaw_c, gaw_t):
-    aw_c, aw_t, off_c, off_t, ref_c, ref_t, shapes = ctx.saved_tensors
-    nc, nt = ctx.needs_input_grad[4], ctx.needs_input_grad[5] and ref_t is not None
-    goff_c, goff_t, glogit_c, glogit_t, gref_c, gref_t = prep_backward(
-        gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, off_c, off_t, ref_c, ref_t, shapes, ctx.loc32, nc, nt)
-    w = off_t is not None
-    return (goff_c, goff_t if w else None, glogit_c, glogit_t if w else None, gref_c if nc else None,
-            gref_t if (w and nt) else None, None, None)
-
-
-prep_forward.register_autograd(_backward_prep, setup_context=_setup_prep)
+prep_forward.register_autograd(functools.partial(_F._backward_prep, prep_backward), setup_context=_F._setup_prep)
 
 
 # ---- MSDeformPrepFusedFunction -------------------------------------------------------------------------------------
@@ -403,17 +349,9 @@ def prep_fused_backward(gloc_c: Optional[Tensor], gloc_t: Optional[Tensor], gaw_
                         ) -> tuple[Tensor, Tensor, Tensor]:
     """``MSDeformPrepFusedFunction.backward`` from the forward's inputs and ``aw_*`` outputs: (grad_y, grad_ref_c,
     grad_ref_t); a reference-point gradient that is not asked for comes back with 0 elements."""
-    if y.stride(1) != 1:
-        y = y.contiguous()
-    aw_c, aw_t = aw_c.contiguous(), None if aw_t is None else aw_t.contiguous()
-    ref_dtypes = (ref_c.dtype, None if ref_t is None else ref_t.dtype)
-    ref_c2, ref_t2 = _F._check_prep_inputs(y, (("reference_points", ref_c), ("temporal reference_points", ref_t if W else None)),
-                                           spatial_shapes, aw_c.dtype)
-    g = _F._prep_fused_backward(gloc_c, gloc_t if W else None, gaw_c, gaw_t if W else None, aw_c, aw_t if W else None,
-                                ref_c2, ref_t2, spatial_shapes, y, M, L, W, Pc, Pt, ref_dtypes, need_ref_c, need_ref_t)
-    fake = _fake_prep_fused_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, y, ref_c, ref_t, spatial_shapes, M, L, W,
-                                     Pc, Pt, loc32, need_ref_c, need_ref_t)
-    return tuple(f if x is None else x for x, f in zip(g, fake))
+    args = (gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, y, ref_c, ref_t, spatial_shapes, M, L, W, Pc, Pt, loc32, need_ref_c,
+            need_ref_t)
+    return fill_slots(_F._prep_fused_backward(*args), _fake_prep_fused_backward(*args))
 
 
 @prep_fused_backward.register_fake
@@ -425,22 +363,8 @@ def _fake_prep_fused_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, y, ref_c
             _empty(ref_c if ref_t is None else ref_t, (R, W * L, d) if (W and need_ref_t) else (0,)))
 
 
-def _setup_prep_fused(ctx, inputs, output):
-    y, ref_c, ref_t, shapes, M, L, W, Pc, Pt, loc32 = inputs
-    ctx.dims = (M, L, W, Pc, Pt, loc32)
-    ctx.save_for_backward(output[2], output[3], y, ref_c, ref_t, shapes)
-
-
-def _backward_prep_fused(ctx, gloc_c, gloc_t, gaw_c, gaw_t):
-    aw_c, aw_t, y, ref_c, ref_t, shapes = ctx.saved_tensors
-    M, L, W, Pc, Pt, loc32 = ctx.dims
-    nc, nt = ctx.needs_input_grad[1], bool(W) and ref_t is not None and ctx.needs_input_grad[2]
-    gy, gref_c, gref_t = prep_fused_backward(gloc_c, gloc_t, gaw_c, gaw_t, aw_c, aw_t, y, ref_c, ref_t, shapes,
-                                             M, L, W, Pc, Pt, loc32, nc, nt)
-    return gy, gref_c if nc else None, gref_t if nt else None, None, None, None, None, None, None, None
-
-
-prep_fused_forward.register_autograd(_backward_prep_fused, setup_context=_setup_prep_fused)
+prep_fused_forward.register_autograd(functools.partial(_F._backward_prep_fused, prep_fused_backward),
+                                     setup_context=_F._setup_prep_fused)
 
 
 # ---- frame table ---------------------------------------------------------------------------------------------------
@@ -483,7 +407,7 @@ def deform_conv2d_backward(grad_out: Tensor, input: Tensor, offset: Tensor, weig
     """(grad_input, grad_offset, grad_mask, grad_weight, grad_bias) for the gradients in ``grads`` (``NEED_*`` of
     devis_amd/functions/deform_conv.py); the others are 0-element tensors."""
     out = _D._backward(grad_out, input, offset, weight, mask, stride, padding, dilation, grads)
-    return _fill_slots(out, _fake_deform_conv2d_backward(grad_out, input, offset, weight, mask, stride, padding, dilation, grads))
+    return fill_slots(out, _fake_deform_conv2d_backward(grad_out, input, offset, weight, mask, stride, padding, dilation, grads))
 
 
 @deform_conv2d_backward.register_fake
@@ -581,7 +505,7 @@ def attention_maps_backward(grad_out: Tensor, q: Tensor, k: Tensor, out: Tensor,
     """(grad_q, grad_k) for the gradients in ``grads`` (``NEED_*`` of devis_amd/functions/attention_maps.py); the other
     is a 0-element tensor."""
     res = _A._backward(grad_out, q, k, out, num_heads, scale, grads)
-    return _fill_slots(res, _fake_attention_maps_backward(grad_out, q, k, out, num_heads, scale, grads))
+    return fill_slots(res, _fake_attention_maps_backward(grad_out, q, k, out, num_heads, scale, grads))
 
 
 @attention_maps_backward.register_fake
@@ -590,20 +514,8 @@ def _fake_attention_maps_backward(grad_out, q, k, out, num_heads, scale, grads):
     return (_empty(q, q.shape if grads & _A.NEED_Q else (0,)), _empty(k, k.shape if grads & _A.NEED_K else (0,)))
 
 
-def _setup_attention_maps(ctx, inputs, output):
-    q, k, mask, num_heads, scale = inputs[:5]
-    ctx.num_heads, ctx.scale = num_heads, scale
-    ctx.save_for_backward(q, k, output)
-
-
-def _backward_attention_maps(ctx, grad_out):
-    q, k, out = ctx.saved_tensors
-    grads = _A.grads_mask(ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-    gq, gk = none_slots(attention_maps_backward(grad_out, q, k, out, ctx.num_heads, ctx.scale, grads))
-    return gq, gk, None, None, None, None
-
-
-attention_maps_op.register_autograd(_backward_attention_maps, setup_context=_setup_attention_maps)
+attention_maps_op.register_autograd(functools.partial(_A.backward, op_runner(attention_maps_backward)),
+                                    setup_context=_A.setup_context)
 
 
 def attention_maps(q, k, mask=None, *, num_heads, scale=None, out_dtype=None):
@@ -644,7 +556,7 @@ def mask_head_stage_backward(grad_out: Tensor, x: Tensor, weight: Tensor, bias: 
     """(grad_x, grad_weight, grad_bias, grad_skip) for the gradients in ``grads`` (``NEED_*`` of
     devis_amd/functions/mask_head_stage.py); the others are 0-element tensors.  ``num_skip`` is F."""
     res = _S._backward(grad_out, x, weight, bias, mean, rstd, skip_index, num_groups, num_skip, grads)
-    return _fill_slots(res, _fake_mask_head_stage_backward(grad_out, x, weight, bias, mean, rstd, skip_index, num_groups,
+    return fill_slots(res, _fake_mask_head_stage_backward(grad_out, x, weight, bias, mean, rstd, skip_index, num_groups,
                                                            num_skip, grads))
 
 
@@ -657,25 +569,8 @@ def _fake_mask_head_stage_backward(grad_out, x, weight, bias, mean, rstd, skip_i
             _empty(x, (num_skip, C, H, W) if grads & _S.NEED_SKIP else (0,)))
 
 
-def _setup_mask_head_stage(ctx, inputs, output):
-    x, num_groups, weight, bias, eps, skip, skip_index, extra = inputs[:8]
-    ctx.num_groups = num_groups
-    ctx.num_skip = 0 if skip is None else skip.shape[0]
-    ctx.extra_dtype = None if extra is None else extra.dtype
-    ctx.save_for_backward(x, weight, bias, output[1], output[2], skip_index)
-
-
-def _backward_mask_head_stage(ctx, grad_out, grad_mean, grad_rstd):
-    x, weight, bias, mean, rstd, skip_index = ctx.saved_tensors
-    need = ctx.needs_input_grad
-    grads = _S.grads_mask(need[0], need[2], need[3], need[5], need[7])
-    gx, gw, gb, gs = none_slots(mask_head_stage_backward(grad_out, x, weight, bias, mean, rstd, skip_index, ctx.num_groups,
-                                                         ctx.num_skip, grads))
-    ge = _S.grad_extra_of(grad_out, x.shape[1], ctx.extra_dtype) if grads & _S.NEED_EXTRA else None
-    return gx, None, gw, gb, None, gs, None, ge, None
-
-
-mask_head_stage_op.register_autograd(_backward_mask_head_stage, setup_context=_setup_mask_head_stage)
+mask_head_stage_op.register_autograd(functools.partial(_S.backward, op_runner(mask_head_stage_backward)),
+                                     setup_context=_S.setup_context)
 
 
 def mask_head_stage(x, num_groups, weight, bias, eps=1e-5, *, skip=None, skip_index=None, extra=None, out_dtype=None):
@@ -693,7 +588,7 @@ def mask_head_stage(x, num_groups, weight, bias, eps=1e-5, *, skip=None, skip_in
     tensors only.  out and every gradient are bitwise reproducible."""
     if torch.compiler.is_compiling():
         return mask_head_stage_op(x, num_groups, weight, bias, float(eps), skip, skip_index, extra, out_dtype)[0]
-    return _S.MaskHeadStageFunction.apply(x, num_groups, weight, bias, float(eps), skip, skip_index, extra, out_dtype)
+    return _S.MaskHeadStageFunction.apply(x, num_groups, weight, bias, float(eps), skip, skip_index, extra, out_dtype)[0]
 
 
 # ---- the mask loss (include/maskloss.h) --------------------------------------------------------------------------------
@@ -724,20 +619,7 @@ def _(grad_focal, grad_dice, src, target, sums, alpha, gamma):
     return _empty(src, src.shape)
 
 
-def _setup_mask_loss_terms(ctx, inputs, output):
-    src, target, alpha, gamma = inputs
-    ctx.alpha, ctx.gamma = alpha, gamma
-    ctx.save_for_backward(src, target, output[2])
-
-
-def _backward_mask_loss_terms(ctx, grad_focal, grad_dice, grad_sums):
-    if not ctx.needs_input_grad[0]:
-        return None, None, None, None
-    src, target, sums = ctx.saved_tensors
-    return mask_loss_terms_backward(grad_focal, grad_dice, src, target, sums, ctx.alpha, ctx.gamma), None, None, None
-
-
-mask_loss_terms_op.register_autograd(_backward_mask_loss_terms, setup_context=_setup_mask_loss_terms)
+mask_loss_terms_op.register_autograd(functools.partial(_L.backward, mask_loss_terms_backward), setup_context=_L.setup_context)
 
 
 def mask_loss_terms(src_masks, target_masks, alpha=0.25, gamma=2.0):
@@ -764,7 +646,7 @@ def mask_loss_terms(src_masks, target_masks, alpha=0.25, gamma=2.0):
                 "mask_loss_terms: target_masks has no gradient (detach it)")
     if torch.compiler.is_compiling():
         return mask_loss_terms_op(src_masks, target_masks, float(alpha), gamma)[:2]
-    return _L.MaskLossTermsFunction.apply(src_masks, target_masks, float(alpha), gamma)
+    return _L.MaskLossTermsFunction.apply(src_masks, target_masks, float(alpha), gamma)[:2]
 
 
 def mask_losses(src_masks, target_masks, num_boxes, alpha=0.25, gamma=2.0):
@@ -1032,18 +914,7 @@ def _(grad_l1, grad_giou, src, target):
     return _empty(src, src.shape)
 
 
-def _setup_box_loss_terms(ctx, inputs, output):
-    ctx.save_for_backward(*inputs)
-
-
-def _backward_box_loss_terms(ctx, grad_l1, grad_giou):
-    if not ctx.needs_input_grad[0]:
-        return None, None
-    src, target = ctx.saved_tensors
-    return box_loss_terms_backward(grad_l1, grad_giou, src, target), None
-
-
-box_loss_terms_op.register_autograd(_backward_box_loss_terms, setup_context=_setup_box_loss_terms)
+box_loss_terms_op.register_autograd(functools.partial(_X.backward, box_loss_terms_backward), setup_context=_X.setup_context)
 
 
 def box_loss_terms(src_boxes, target_boxes):
@@ -1134,19 +1005,7 @@ def _(grad_sum, logits, target_classes, alpha):
     return _empty(logits, logits.shape)
 
 
-def _setup_label_loss_terms(ctx, inputs, output):
-    ctx.alpha = inputs[4]
-    ctx.save_for_backward(inputs[0], output[2])
-
-
-def _backward_label_loss_terms(ctx, grad_sum, grad_counts, grad_classes):
-    if not ctx.needs_input_grad[0]:
-        return None, None, None, None, None
-    logits, target_classes = ctx.saved_tensors
-    return label_loss_terms_backward(grad_sum, logits, target_classes, ctx.alpha), None, None, None, None
-
-
-label_loss_terms_op.register_autograd(_backward_label_loss_terms, setup_context=_setup_label_loss_terms)
+label_loss_terms_op.register_autograd(functools.partial(_Y.backward, label_loss_terms_backward), setup_context=_Y.setup_context)
 
 
 def label_loss_terms(logits, rows, labels, valid=None, *, alpha=0.25):
@@ -1254,24 +1113,8 @@ def _(grad_pos, heights, widths, want_level, want_temporal):
             _empty(grad_pos, (N, C) if want_temporal else (0,), torch.float32))
 
 
-def _setup_encoder_position_embedding(ctx, inputs, output):
-    masks, level_embed, temporal_embed = inputs[:3]
-    ctx.heights, ctx.widths = [m.shape[1] for m in masks], [m.shape[2] for m in masks]
-    ctx.dtypes = (level_embed.dtype, None if temporal_embed is None else temporal_embed.dtype)
-
-
-def _backward_encoder_position_embedding(ctx, grad_pos, grad_mask, grad_ratios):
-    want_level, want_temporal = ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.dtypes[1] is not None
-    nothing = (None,) * 9
-    if not (want_level or want_temporal):
-        return nothing
-    grad_level, grad_temporal = encoder_position_embedding_backward(grad_pos, ctx.heights, ctx.widths, want_level, want_temporal)
-    return (None, grad_level.to(ctx.dtypes[0]) if want_level else None,
-            grad_temporal.to(ctx.dtypes[1]) if want_temporal else None) + nothing[3:]
-
-
-encoder_position_embedding_op.register_autograd(_backward_encoder_position_embedding,
-                                                setup_context=_setup_encoder_position_embedding)
+encoder_position_embedding_op.register_autograd(functools.partial(_P.backward, encoder_position_embedding_backward),
+                                                setup_context=_P.setup_context)
 
 
 def encoder_position_embedding(masks, level_embed, temporal_embed=None, *, num_pos_feats=None, temperature=10000,

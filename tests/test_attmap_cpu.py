@@ -212,9 +212,10 @@ def test_operator_raises_on_cpu_tensors_and_on_bad_shapes_before_any_launch():
     assert A.default_scale(q, 4) == 8 ** -0.5
 
 
-def test_needs_input_grad_maps_to_the_gradient_mask(monkeypatch):
+def test_needs_input_grad_maps_to_the_gradient_mask():
     from devis_amd import _attmap, ops
     from devis_amd.functions import attention_maps as A
+    from devis_amd.functions._common import op_runner
     assert (A.grads_mask(True, False), A.grads_mask(False, True), A.grads_mask(True, True)) == (1, 2, 3)
     assert (A.NEED_Q, A.NEED_K, A.NEED_ALL) == (_attmap.GRAD_Q, _attmap.GRAD_K, 3)
     seen = []
@@ -228,15 +229,16 @@ def test_needs_input_grad_maps_to_the_gradient_mask(monkeypatch):
         seen.append(("host", grads, num_heads, scale))
         return (torch.zeros_like(q) if grads & 1 else None, torch.zeros_like(k) if grads & 2 else None)
 
-    monkeypatch.setattr(ops, "attention_maps_backward", fake_op_backward)
-    monkeypatch.setattr(A, "_backward", fake_host_backward)
+    # the one formula, run the way the op's register_autograd runs it and the way the eager Function does
+    assert A.AttentionMapsFunction.setup_context is A.setup_context is ops.attention_maps_op._setup_context_fn
+    assert ops.attention_maps_op._backward_fn.func is A.backward
     for needs, want in (((True, True, False, False, False, False), 3), ((True, False, False, False, False, False), 1),
                         ((False, True, False, False, False, False), 2)):
         ctx = types.SimpleNamespace(saved_tensors=(q, k, out), needs_input_grad=needs, num_heads=4, scale=0.5)
-        res = ops._backward_attention_maps(ctx, out)
+        res = A.backward(op_runner(fake_op_backward), ctx, out)
         assert seen[-1] == ("op", want, 4, 0.5) and len(res) == 6 and res[2:] == (None,) * 4
         assert (res[0] is not None, res[1] is not None) == needs[:2]
-        res = A.AttentionMapsFunction.backward(ctx, out)
+        res = A.backward(fake_host_backward, ctx, out)
         assert seen[-1] == ("host", want, 4, 0.5) and len(res) == 6 and res[2:] == (None,) * 4
         assert (res[0] is not None, res[1] is not None) == needs[:2]
 

@@ -226,6 +226,20 @@ def test_opcheck_frame_table():
     assert ops.frame_table(offs, 3, torch.device("cpu")).tolist() == [[1, 2], [0, 2], [0, 1]]
 
 
+def test_every_op_keeps_its_recorded_schema():
+    """The ops of the namespace and their schemas are an outward contract (saved graphs and exported programs name them):
+    tests/golden/op_schemas.json is the list, recorded before the autograd formulas moved next to the host code."""
+    import json
+    from devis_amd import ops
+    with open(os.path.join(ROOT, "tests", "golden", "op_schemas.json")) as f:
+        want = json.load(f)
+    prefix = ops.NAMESPACE + "::"
+    names = sorted({n.split(".")[0] for n in torch._C._dispatch_get_all_op_names() if n.startswith(prefix)})
+    got = [str(getattr(getattr(torch.ops, ops.NAMESPACE), n[len(prefix):]).default._schema).replace(prefix, "devis_amd::", 1)
+           for n in names]
+    assert len(want) == 34 and got == want
+
+
 # ---- 2. the Function under torch.compile ----------------------------------------------------------------------------
 
 @pytest.mark.parametrize("step", [1, 64])

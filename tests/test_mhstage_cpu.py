@@ -245,9 +245,10 @@ def test_operator_raises_on_cpu_tensors_and_on_bad_shapes_before_any_launch():
             call()
 
 
-def test_needs_input_grad_maps_to_the_gradient_mask(monkeypatch):
+def test_needs_input_grad_maps_to_the_gradient_mask():
     from devis_amd import _mhstage, ops
     from devis_amd.functions import mask_head_stage as S
+    from devis_amd.functions._common import op_runner
     assert S.grads_mask(True, False, False, False, False) == _mhstage.GRAD_X == S.NEED_X
     assert S.grads_mask(False, True, True, False, False) == _mhstage.GRAD_WEIGHT | _mhstage.GRAD_BIAS
     assert S.grads_mask(True, True, True, True, True) == S.NEED_ALL == 31 and _mhstage.GRAD_ALL == 15
@@ -263,16 +264,16 @@ def test_needs_input_grad_maps_to_the_gradient_mask(monkeypatch):
         seen.append(("host", grads, num_groups, num_skip))
         return tuple(torch.zeros(1) if grads & bit else None for bit in (1, 2, 4, 8))
 
-    monkeypatch.setattr(ops, "mask_head_stage_backward", fake_op_backward)
-    monkeypatch.setattr(S, "_backward", fake_host_backward)
+    # the one formula, run the way the op's register_autograd runs it and the way the eager Function does
+    assert S.MaskHeadStageFunction.setup_context is S.setup_context is ops.mask_head_stage_op._setup_context_fn
+    assert ops.mask_head_stage_op._backward_fn.func is S.backward
     T, N_ = True, False
     for needs, want in (((T, N_, T, T, N_, T, N_, T, N_), 31), ((T, N_, N_, N_, N_, N_, N_, N_, N_), 1),
                         ((N_, N_, T, T, N_, N_, N_, N_, N_), 6), ((N_, N_, N_, N_, N_, T, N_, T, N_), 24)):
         ctx = types.SimpleNamespace(saved_tensors=(x, w, b, stats, stats, None), needs_input_grad=needs, num_groups=8,
                                     num_skip=2, extra_dtype=torch.float32)
-        for call, who in ((lambda: ops._backward_mask_head_stage(ctx, go, None, None), "op"),      # noqa: B023
-                          (lambda: S.MaskHeadStageFunction.backward(ctx, go), "host")):      # noqa: B023
-            res = call()
+        for run, who in ((op_runner(fake_op_backward), "op"), (fake_host_backward, "host")):
+            res = S.backward(run, ctx, go, None, None)
             assert seen[-1] == (who, want, 8, 2) and len(res) == 9
             assert tuple(r is not None for r in res) == needs
             if needs[7]:

@@ -311,7 +311,7 @@ def test_operators_raise_on_cpu_tensors_and_on_bad_arguments_before_any_launch(m
         devis_amd.encoder_position_embedding(masks, level, torch.zeros(2, 16))
 
 
-def test_only_the_requested_gradient_is_computed(monkeypatch):
+def test_only_the_requested_gradient_is_computed():
     from devis_amd import ops
     from devis_amd.functions import position_embedding as P
     seen = []
@@ -320,16 +320,23 @@ def test_only_the_requested_gradient_is_computed(monkeypatch):
         seen.append((list(heights), list(widths), want_level, want_temporal))
         return torch.zeros(3, 16) if want_level else torch.zeros(0), torch.zeros(3, 16) if want_temporal else torch.zeros(0)
 
-    monkeypatch.setattr(P, "_encoder_backward", fake)
-    monkeypatch.setattr(ops, "encoder_position_embedding_backward", fake)
+    # the one formula, for the eager Function's argument order (the embeddings first, the masks last and one by one) and for
+    # the op's (the masks first, as a list)
+    assert ops.encoder_position_embedding_op._setup_context_fn is P.setup_context
+    assert ops.encoder_position_embedding_op._backward_fn.func is P.backward
     g = torch.ones(3, 51, 16)
     for level, temporal, has_temporal in ((True, True, True), (True, False, True), (False, True, True), (False, False, True), (True, True, False)):
         dtypes = (F32, torch.float16 if has_temporal else None)
-        eager = types.SimpleNamespace(sizes=SIZES, dtypes=dtypes, needs_input_grad=(level, temporal) + (False,) * 9)
+        eager = types.SimpleNamespace(mark_non_differentiable=lambda *t: None)
+        P.EncoderPositionEmbeddingFunction.setup_context(
+            eager, (torch.zeros(3, 16), torch.zeros(3, 16, dtype=torch.float16) if has_temporal else None) + (None,) * 6 +
+            tuple(torch.zeros((3,) + s, dtype=torch.bool) for s in SIZES), (None, None, None))
+        assert (eager.heights, eager.widths, eager.dtypes) == ([5, 3, 2], [7, 4, 2], dtypes)
+        eager.needs_input_grad = (level, temporal) + (False,) * 9
         op = types.SimpleNamespace(heights=[5, 3, 2], widths=[7, 4, 2], dtypes=dtypes, needs_input_grad=(False, level, temporal) + (False,) * 6)
         before = len(seen)
-        a = P.EncoderPositionEmbeddingFunction.backward(eager, g, None, None)
-        b = ops._backward_encoder_position_embedding(op, g, None, None)
+        a = P.backward(fake, eager, g, None, None, embeds_at=0)
+        b = P.backward(fake, op, g, None, None)
         assert len(a) == 11 and len(b) == 9 and b[0] is None
         want_t = temporal and has_temporal
         for gl, gt in ((a[0], a[1]), (b[1], b[2])):
@@ -337,6 +344,27 @@ def test_only_the_requested_gradient_is_computed(monkeypatch):
             assert gt is None or gt.dtype == torch.float16                       # in the embedding's dtype
         assert all(r is None for r in a[2:] + b[3:])
         assert seen[before:] == ([([5, 3, 2], [7, 4, 2], level, want_t)] * 2 if level or want_t else [])
+
+
+def test_the_formula_runs_under_torchs_autograd_for_the_function_and_for_the_op(monkeypatch):
+    """Both registrations of the one formula through torch's own machinery, with the kernel launches stubbed out: the
+    Function's masks are separate arguments, the op's are a list, whose gradient slot has to be a list of None."""
+    from devis_amd import _posembed, ops
+    from devis_amd.functions import position_embedding as P
+    monkeypatch.setattr(P, "_check_device", lambda *a: None)
+    monkeypatch.setattr(_posembed, "workspace_bytes", lambda *a: 16)
+    for name in ("counts", "write_flat", "backward"):
+        monkeypatch.setattr(_posembed, name, lambda *a, **k: None)
+    masks = [torch.zeros((3,) + s, dtype=torch.bool) for s in SIZES]
+    rest = (None, 10000.0, True, None, None, None)
+    for call in (lambda lv, tp: P.EncoderPositionEmbeddingFunction.apply(lv, tp, *rest, *masks),
+                 lambda lv, tp: ops.encoder_position_embedding_op(masks, lv, tp, *rest)):
+        level = torch.zeros(3, 16, requires_grad=True)
+        temporal = torch.zeros(3, 16, dtype=torch.float64, requires_grad=True)
+        pos, mask_flatten, valid_ratios = call(level, temporal)
+        assert pos.requires_grad and not mask_flatten.requires_grad and not valid_ratios.requires_grad
+        grad_level, grad_temporal = torch.autograd.grad(pos.sum(), [level, temporal])
+        assert (grad_level.dtype, grad_temporal.dtype) == (F32, torch.float64)
 
 
 # ---- modules and patches -----------------------------------------------------------------------------------------------------
