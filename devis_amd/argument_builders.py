@@ -717,3 +717,22 @@ def unpatch_position_encoding(position_encoding_module, deformable_transformer_m
                 delattr(cls, name)
         else:
             setattr(cls, name, previous[key])
+
+
+def patch_transformer_layers(deformable_transformer_module):
+    """Opt-in: make ``forward`` and ``forward_ffn`` of the reference's ``DeformableTransformerEncoderLayer`` and
+    ``DeformableTransformerDecoderLayer`` (``src.models.deformable_transformer``; the DeVIS subclasses inherit both) run every
+    ``x = norm(x + dropout(y))`` as one :func:`devis_amd.add_layer_norm` call and the FFN as
+    ``linear2(relu_dropout(linear1(x)))`` (:mod:`devis_amd.modules.transformer_layers`, which lists when the replaced methods run
+    instead: while compiling, on the CPU, with another activation than relu, ...).  Takes effect at once, also for layers that
+    already exist (the methods are looked up on the class); no module is replaced, so state dicts are untouched.  Independent of
+    every other patch, in either order: :func:`patch_transformer` touches other classes.  Returns what was replaced (to undo the
+    patch; :func:`unpatch_transformer_layers`)."""
+    from .modules import transformer_layers
+    return transformer_layers.patch(deformable_transformer_module)
+
+
+def unpatch_transformer_layers(deformable_transformer_module, previous):
+    """Undo :func:`patch_transformer_layers` (tests)."""
+    from .modules import transformer_layers
+    transformer_layers.unpatch(deformable_transformer_module, previous)
