@@ -736,3 +736,22 @@ def unpatch_transformer_layers(deformable_transformer_module, previous):
     """Undo :func:`patch_transformer_layers` (tests)."""
     from .modules import transformer_layers
     transformer_layers.unpatch(deformable_transformer_module, previous)
+
+
+def patch_self_attention(root_module, *, discard_weights=True):
+    """Opt-in: every module under ``root_module`` whose type is exactly ``nn.MultiheadAttention`` -- the ``self_attn`` of the
+    reference's ``DeformableTransformerDecoderLayer`` -- becomes a :class:`devis_amd.modules.FusedMultiheadAttention` by setting
+    its ``__class__`` (:mod:`devis_amd.modules.self_attention`, which lists when the stock forward runs instead: while compiling,
+    on the CPU, with a mask, ...).  No module is replaced: state dicts are untouched and ``copy.deepcopy`` keeps the class;
+    subclasses of ``nn.MultiheadAttention`` are left alone.  ``discard_weights=True`` is a stated deviation: a fused call with
+    ``need_weights=True`` returns ``None`` where torch returns the head-averaged weights (the reference throws them away); with
+    ``discard_weights=False`` such calls run the stock forward.  Independent of :func:`patch_transformer_layers`, in either
+    order.  Returns what :func:`unpatch_self_attention` needs."""
+    from .modules import self_attention
+    return self_attention.patch(root_module, discard_weights)
+
+
+def unpatch_self_attention(previous):
+    """Undo :func:`patch_self_attention`."""
+    from .modules import self_attention
+    self_attention.unpatch(previous)

@@ -3,6 +3,7 @@
 // and holds it in registers; there is no LDS, no atomic and nothing is zeroed.  The dropout mask is Philox4x32-10 of (seed, row,
 // channel / 4), recomputed by the backward, and the seed is read on the device.
 #include "op_common.h"       // (fp contraction off)
+#include "philox.h"
 #include "addnorm.h"
 
 namespace addnorm {
@@ -20,24 +21,7 @@ constexpr int kSpan = 256;                  // channels one group of four per la
 
 thread_local Status err;     // addnorm_last_error()
 
-// ---- the mask (include/addnorm.h) ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2, unsigned c3,
-                                              unsigned (&out)[4])
-{
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
+// ---- the mask (include/addnorm.h; the generator is philox.h) ---------------------------------------------------------------
 // bit j: element (row, 4 * quad + j) is kept
 __device__ __forceinline__ unsigned keep_of(long long seed, long long row, unsigned quad, unsigned long long threshold)
 {

@@ -6,3 +6,4 @@ from .attention_maps import MultiScaleMHAttentionMap  # noqa: F401  (reference s
 from .mask_head import MaskHeadConv  # noqa: F401  (reference src/models/deformable_segmentation.py)
 from .position_encoding import (PositionEmbeddingSine,  # noqa: F401  (reference src/models/position_encoding.py)
                                 PositionEmbeddingSineWithLearnableTemporal)
+from .self_attention import FusedMultiheadAttention  # noqa: F401  (reference src/models/deformable_transformer.py: self_attn)
