@@ -4,9 +4,11 @@ allocates nor synchronises -- outputs are torch tensors of the caller.  A call r
 """
 import ctypes
 
+import torch
+
 from . import _binding, _native
 
-SELFATTN_ABI_VERSION = 1
+SELFATTN_ABI_VERSION = 2
 MAX_HEAD_DIM = 64                       # include/selfattn.h SELFATTN_MAX_HEAD_DIM
 # every symbol include/selfattn.h declares (tests check the library exports each of them)
 EXPORTED_SYMBOLS = ("selfattn_version", "selfattn_last_error", "selfattn_forward", "selfattn_backward")
@@ -27,7 +29,7 @@ class View(ctypes.Structure):
 def _prototypes(lib):
     shape_p, view_p = ctypes.POINTER(Shape), ctypes.POINTER(View)
     lib.selfattn_forward.restype = _ci
-    lib.selfattn_forward.argtypes = [_ci, _vp, view_p, _vp, view_p, _vp, view_p, _vp, _cd, shape_p, _vp, _vp, _vp]
+    lib.selfattn_forward.argtypes = [_ci, _vp, view_p, _vp, view_p, _vp, view_p, _vp, _cd, shape_p, _vp, _vp, _vp, _vp]
     lib.selfattn_backward.restype = _ci
     lib.selfattn_backward.argtypes = [_ci, _vp, view_p, _vp, view_p, _vp, view_p, _vp, _vp, _vp, _vp, _cd, shape_p, _vp, _vp,
                                       _vp, _vp]
@@ -42,19 +44,23 @@ def view_of(t):
     return View(t.stride(0), t.stride(1), t.stride(2))
 
 
-def forward(code, q, k, v, seed, p, shape, out, lse):
-    """selfattn_forward on the current stream: ``out`` [L, N, E] fully written, ``lse`` [N * H, L] when given.  ``q``, ``k`` and
-    ``v`` are passed with their strides.  Returns the number of launches."""
+def forward(code, q, k, v, seed, p, shape, out, lse, out_acc=None):
+    """selfattn_forward on the current stream: ``out`` [L, N, E] fully written, ``lse`` [N * H, L] and ``out_acc`` [L, N, E]
+    float32 -- ``out`` before its rounding -- when given.  ``q``, ``k`` and ``v`` are passed with their strides.  Returns the
+    number of launches."""
     with _native._on(q.device):
         rc = load().selfattn_forward(code, _native._p(q), ctypes.byref(view_of(q)), _native._p(k), ctypes.byref(view_of(k)),
                                      _native._p(v), ctypes.byref(view_of(v)), _native._p(seed), float(p), ctypes.byref(shape),
-                                     _native._p(out), _native._p(lse), _native._stream(q))
+                                     _native._p(out), _native._p(lse), _native._p(out_acc), _native._stream(q))
     return _check(rc, "selfattn_forward")
 
 
 def backward(code, q, k, v, out, grad_out, lse, seed, p, shape, grad_q, grad_k, grad_v):
-    """selfattn_backward on the current stream: the gradients that are given, fully written.  Returns the number of launches:
-    one for ``grad_q``, one for ``grad_k`` and / or ``grad_v``."""
+    """selfattn_backward on the current stream: the gradients that are given, fully written.  ``out`` is FLOAT32 whatever the
+    storage dtype: the forward's ``out_acc``, or its ``out`` for float32 operands.  Returns the number of launches: one for
+    ``grad_q``, one for ``grad_k`` and / or ``grad_v``."""
+    if out.dtype != torch.float32:
+        raise RuntimeError("selfattn_backward: out must be float32 (the forward's out_acc), got %s" % out.dtype)
     with _native._on(q.device):
         rc = load().selfattn_backward(code, _native._p(q), ctypes.byref(view_of(q)), _native._p(k), ctypes.byref(view_of(k)),
                                       _native._p(v), ctypes.byref(view_of(v)), _native._p(out), _native._p(grad_out),

@@ -136,7 +136,8 @@ template <typename T, int CT>
 __global__ __launch_bounds__(64) void forward_kernel(const T *__restrict__ q, const Strides qs, const T *__restrict__ k,
                                                      const Strides ks, const T *__restrict__ v, const Strides vs,
                                                      const long long *__restrict__ seed, T *__restrict__ out,
-                                                     float *__restrict__ lse, const Problem pb, const int N)
+                                                     float *__restrict__ lse, float *__restrict__ out_acc, const Problem pb,
+                                                     const int N)
 {
     constexpr int NQ = 4 * CT;
     const int lane = threadIdx.x, c = lane & 15, g = lane >> 4;
@@ -207,11 +208,13 @@ __global__ __launch_bounds__(64) void forward_kernel(const T *__restrict__ q, co
     if (i >= L) return;
     if (lse && g == 0) lse[row] = m + logf(total);
     const float inv = 1.0f / total;
-    T *dst = out + ((long long)i * N + nb) * ((long long)pb.H * D) + head;
+    const long long dense = ((long long)i * N + nb) * ((long long)pb.H * D) + head;
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
         const int d0 = ct * 16 + 4 * g;             // register r is channel d0 + r
-        if (d0 < D) store_quad(dst + d0, pb.vec != 0, o[ct], inv);
+        if (d0 >= D) continue;
+        store_quad(out + dense + d0, pb.vec != 0, o[ct], inv);
+        if (out_acc) store_quad(out_acc + dense + d0, pb.vec != 0, o[ct], inv);       // before the rounding to T: the backward's
     }
 }
 
@@ -221,7 +224,7 @@ __global__ __launch_bounds__(64) void forward_kernel(const T *__restrict__ q, co
 template <typename T, int CT>
 __global__ __launch_bounds__(64) void backward_q_kernel(const T *__restrict__ q, const Strides qs, const T *__restrict__ k,
                                                         const Strides ks, const T *__restrict__ v, const Strides vs,
-                                                        const T *__restrict__ out, const T *__restrict__ grad_out,
+                                                        const float *__restrict__ out, const T *__restrict__ grad_out,
                                                         const float *__restrict__ lse, const long long *__restrict__ seed,
                                                         T *__restrict__ grad_q, const Problem pb, const int N)
 {
@@ -238,7 +241,7 @@ __global__ __launch_bounds__(64) void backward_q_kernel(const T *__restrict__ q,
     float qf[NQ], dof[NQ], of[NQ];
     load_chunk<T, NQ>(q + i * qs.seq + nb * qs.batch + head + g * n, n, i < L, chunk_vec, qf);
     load_chunk<T, NQ>(grad_out + dense + g * n, n, i < L, chunk_vec, dof);
-    load_chunk<T, NQ>(out + dense + g * n, n, i < L, chunk_vec, of);
+    load_chunk<float, NQ>(out + dense + g * n, n, i < L, chunk_vec, of);
     const float delta = delta_of<NQ>(dof, of, n);
     const float lse_i = i < L ? lse[row] : 0.0f;
     f32x4 dq[CT];
@@ -301,7 +304,7 @@ __global__ __launch_bounds__(64) void backward_q_kernel(const T *__restrict__ q,
 template <typename T, int CT>
 __global__ __launch_bounds__(64) void backward_kv_kernel(const T *__restrict__ q, const Strides qs, const T *__restrict__ k,
                                                          const Strides ks, const T *__restrict__ v, const Strides vs,
-                                                         const T *__restrict__ out, const T *__restrict__ grad_out,
+                                                         const float *__restrict__ out, const T *__restrict__ grad_out,
                                                          const float *__restrict__ lse, const long long *__restrict__ seed,
                                                          T *__restrict__ grad_k, T *__restrict__ grad_v, const Problem pb,
                                                          const int N)
@@ -360,7 +363,7 @@ __global__ __launch_bounds__(64) void backward_kv_kernel(const T *__restrict__ q
         }
         if (want_k) {
             float of[NQ];
-            load_chunk<T, NQ>(out + dense + g * n, n, ic < L, chunk_vec, of);
+            load_chunk<float, NQ>(out + dense + g * n, n, ic < L, chunk_vec, of);
             const float delta_c = delta_of<NQ>(dof, of, n);             // of query i0 + c
             const f32x4 dpt = dot_tile<NQ>(dof, vf, n);
             float ds[4];
@@ -506,7 +509,7 @@ const char *selfattn_last_error(void) { return err.msg; }
 
 int selfattn_forward(int dtype, const void *q, const selfattn_view *q_view, const void *k, const selfattn_view *k_view,
                      const void *v, const selfattn_view *v_view, const long long *seed, double p, const selfattn_shape *shape,
-                     void *out, void *lse, void *stream)
+                     void *out, void *lse, void *out_acc, void *stream)
 {
     err.clear();
     if (check_dtype(dtype) != SELFATTN_OK || check_shape(shape) != SELFATTN_OK) return SELFATTN_ERR_ARGUMENT;
@@ -520,8 +523,8 @@ int selfattn_forward(int dtype, const void *q, const selfattn_view *q_view, cons
     if (!q || !k || !v || !out) return err.fail("null pointer: q, k, v and out are required");
     dim3 grid;
     if (grid_of(s.L, s, &grid) != SELFATTN_OK) return SELFATTN_ERR_ARGUMENT;
-    const bool vec = aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out) && quads(*q_view) && quads(*k_view) &&
-                     quads(*v_view);
+    const bool vec = aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out) && aligned16(out_acc) && quads(*q_view) &&
+                     quads(*k_view) && quads(*v_view);
     const Problem pb = problem_of(s, threshold, scale, vec);
     const long long *sd = p > 0.0 ? seed : nullptr;
     hipStream_t st = (hipStream_t)stream;
@@ -529,14 +532,15 @@ int selfattn_forward(int dtype, const void *q, const selfattn_view *q_view, cons
         typedef type_of<decltype(t)> T;
         constexpr int CT = decltype(tiles)::value;
         hipLaunchKernelGGL((forward_kernel<T, CT>), grid, dim3(64), 0, st, (const T *)q, strides_of(*q_view), (const T *)k,
-                           strides_of(*k_view), (const T *)v, strides_of(*v_view), sd, (T *)out, (float *)lse, pb, (int)s.N);
+                           strides_of(*k_view), (const T *)v, strides_of(*v_view), sd, (T *)out, (float *)lse, (float *)out_acc, pb,
+                           (int)s.N);
         return err.check_launch("selfattn_forward");
     });
     return rc == SELFATTN_OK ? 1 : rc;
 }
 
 int selfattn_backward(int dtype, const void *q, const selfattn_view *q_view, const void *k, const selfattn_view *k_view,
-                      const void *v, const selfattn_view *v_view, const void *out, const void *grad_out, const void *lse,
+                      const void *v, const selfattn_view *v_view, const void *out_acc, const void *grad_out, const void *lse,
                       const long long *seed, double p, const selfattn_shape *shape, void *grad_q, void *grad_k, void *grad_v,
                       void *stream)
 {
@@ -550,10 +554,11 @@ int selfattn_backward(int dtype, const void *q, const selfattn_view *q_view, con
     if (s.L == 0 || s.N == 0 || s.S == 0) return 0;
     if (check_view(q_view, "q") != SELFATTN_OK || check_view(k_view, "k") != SELFATTN_OK || check_view(v_view, "v") != SELFATTN_OK)
         return SELFATTN_ERR_ARGUMENT;
-    if (!q || !k || !v || !out || !grad_out || !lse) return err.fail("null pointer: q, k, v, out, grad_out and lse are required");
+    if (!q || !k || !v || !out_acc || !grad_out || !lse)
+        return err.fail("null pointer: q, k, v, out_acc, grad_out and lse are required");
     dim3 grid_q, grid_kv;
     if (grid_of(s.L, s, &grid_q) != SELFATTN_OK || grid_of(s.S, s, &grid_kv) != SELFATTN_OK) return SELFATTN_ERR_ARGUMENT;
-    const bool vec = aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out) && aligned16(grad_out) && aligned16(grad_q) &&
+    const bool vec = aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out_acc) && aligned16(grad_out) && aligned16(grad_q) &&
                      aligned16(grad_k) && aligned16(grad_v) && quads(*q_view) && quads(*k_view) && quads(*v_view);
     const Problem pb = problem_of(s, threshold, scale, vec);
     const long long *sd = p > 0.0 ? seed : nullptr;
@@ -564,13 +569,13 @@ int selfattn_backward(int dtype, const void *q, const selfattn_view *q_view, con
         constexpr int CT = decltype(tiles)::value;
         if (grad_q) {
             hipLaunchKernelGGL((backward_q_kernel<T, CT>), grid_q, dim3(64), 0, st, (const T *)q, strides_of(*q_view),
-                               (const T *)k, strides_of(*k_view), (const T *)v, strides_of(*v_view), (const T *)out,
+                               (const T *)k, strides_of(*k_view), (const T *)v, strides_of(*v_view), (const float *)out_acc,
                                (const T *)grad_out, (const float *)lse, sd, (T *)grad_q, pb, (int)s.N);
             ++launches;
         }
         if (grad_k || grad_v) {
             hipLaunchKernelGGL((backward_kv_kernel<T, CT>), grid_kv, dim3(64), 0, st, (const T *)q, strides_of(*q_view),
-                               (const T *)k, strides_of(*k_view), (const T *)v, strides_of(*v_view), (const T *)out,
+                               (const T *)k, strides_of(*k_view), (const T *)v, strides_of(*v_view), (const float *)out_acc,
                                (const T *)grad_out, (const float *)lse, sd, (T *)grad_k, (T *)grad_v, pb, (int)s.N);
             ++launches;
         }

@@ -5,7 +5,9 @@ backward.  Argument checks, the output tensors, the kernel launches and the auto
 
 ``q``, ``k`` and ``v`` are handed to the kernels as the views they are (any strides with a last stride of 1), so the two column
 halves of one ``[L, N, 2E]`` projection and ``batch_first`` tensors need no copy.  No probability matrix and no mask is stored:
-the Function saves the operands, ``out``, one float32 per row (``lse``) and the seed, and the backward recomputes the rest.
+the Function saves the operands, ``out`` in float32 (for 16-bit operands a copy the forward writes before it rounds: the
+backward's ``delta = sum(dO * O)`` cancels against ``dP`` and needs the unrounded rows), one float32 per row (``lse``) and the
+seed, and the backward recomputes the rest.
 
 The dropout mask is a function of ``(seed, n, h, i, j)`` (Philox4x32-10; the rule is in the header).  ``seed`` is an int64
 DEVICE tensor of one element that only the kernels read -- nothing here reads a device value on the host, and a HIP graph
@@ -71,7 +73,9 @@ def as_view(t):
 
 
 def _forward(q, k, v, seed, num_heads, p, want_lse=True):
-    """(out [L, N, E] in q's dtype, lse [N * H, L] float32 or None unless ``want_lse``)."""
+    """(out [L, N, E] in q's dtype, lse [N * H, L] float32, out_acc); the last two are what a backward needs and are None
+    unless ``want_lse``.  out_acc [L, N, E] float32 is ``out`` before its rounding to a 16-bit dtype, and None for float32
+    operands, whose ``out`` is that already."""
     p = check_p(OP, p, seed)
     L, S, N, E, H, D = check_shapes(q, k, v, num_heads)
     seed = seed if p > 0.0 else None
@@ -79,20 +83,22 @@ def _forward(q, k, v, seed, num_heads, p, want_lse=True):
     new = torch.empty if S else torch.zeros
     out = new((L, N, E), dtype=q.dtype, device=q.device)
     lse = torch.empty((N * H, L), dtype=torch.float32, device=q.device) if want_lse else None
+    acc = new((L, N, E), dtype=torch.float32, device=q.device) if want_lse and q.dtype in (torch.bfloat16, torch.float16) else None
     if L and N and S:
+        extra = () if acc is None else (acc,)            # (float32: the call the binding has always taken)
         _selfattn.forward(_native.dtype_code(q.dtype), as_view(q), as_view(k), as_view(v), seed, p,
-                          _selfattn.Shape(L, S, N, E, H), out, lse)
-    return out, lse
+                          _selfattn.Shape(L, S, N, E, H), out, lse, *extra)
+    return out, lse, acc
 
 
 def _backward(grad_out, q, k, v, out, lse, seed, num_heads, p, wants):
-    """(grad_q, grad_k, grad_v), dense and in their operand's dtype, None where ``wants`` is False.  One launch for grad_q, one
-    for grad_k and / or grad_v."""
+    """(grad_q, grad_k, grad_v), dense and in their operand's dtype, None where ``wants`` is False.  ``out`` is the forward's
+    result in float32: its out_acc for 16-bit operands.  One launch for grad_q, one for grad_k and / or grad_v."""
     _require(any(wants), "%s: no gradient is asked for" % OP)
     L, S, N, E, H, D = check_shapes(q, k, v, num_heads)
     seed = seed if p > 0.0 else None
     _check_device(OP, [("grad_out", grad_out), ("q", q), ("k", k), ("v", v), ("out", out), ("lse", lse), ("seed", seed)])
-    _require(grad_out.shape == out.shape and grad_out.dtype == out.dtype, "%s: the gradient of out must have its shape and dtype" % OP)
+    _require(grad_out.shape == out.shape and grad_out.dtype == q.dtype, "%s: the gradient of out must have its shape and dtype" % OP)
     empty = not (L and N and S)
     new = torch.zeros if empty else torch.empty
     grads = [new(t.shape, dtype=t.dtype, device=t.device) if want else None for t, want in zip((q, k, v), wants)]
@@ -104,13 +110,13 @@ def _backward(grad_out, q, k, v, out, lse, seed, num_heads, p, wants):
 
 def setup_context(ctx, inputs, output):
     q, k, v, seed, num_heads, p = inputs
-    out, lse = output
+    out, lse, acc = output
     ctx.p, ctx.num_heads = float(p), int(num_heads)
-    ctx.mark_non_differentiable(lse)
-    ctx.save_for_backward(q, k, v, out, lse, seed if ctx.p > 0.0 else None)
+    ctx.mark_non_differentiable(*(t for t in (lse, acc) if t is not None))
+    ctx.save_for_backward(q, k, v, out if acc is None else acc, lse, seed if ctx.p > 0.0 else None)
 
 
-def backward(run, ctx, grad_out, grad_lse):
+def backward(run, ctx, grad_out, grad_lse, grad_acc=None):
     """The autograd formula; ``run`` is :func:`_backward`."""
     wants = tuple(ctx.needs_input_grad[:3])
     if not any(wants):
@@ -120,9 +126,9 @@ def backward(run, ctx, grad_out, grad_lse):
 
 
 class MultiheadAttentionFunction(torch.autograd.Function):
-    """``multihead_attention`` for eager code: ``apply(q, k, v, seed or None, num_heads, p)`` -> (out, lse).  Saves the operand
-    views, out, lse and the seed -- no probabilities, no mask; only out is differentiable.  The backward computes the gradients
-    autograd asks for and launches nothing when it asks for none."""
+    """``multihead_attention`` for eager code: ``apply(q, k, v, seed or None, num_heads, p)`` -> (out, lse, out_acc or None).
+    Saves the operand views, out in float32 (out_acc for 16-bit operands), lse and the seed -- no probabilities, no mask; only
+    out is differentiable.  The backward computes the gradients autograd asks for and launches nothing when it asks for none."""
     @staticmethod
     def forward(q, k, v, seed, num_heads, p):
         return _forward(q, k, v, seed, num_heads, p)

@@ -7,8 +7,8 @@
  *         P   = softmax over the keys of S
  *         out = dropout_p(P) v_h                       [L, D]
  *
- * forward and backward.  No probability matrix and no mask is ever stored: the forward keeps one float per row (lse), the
- * backward recomputes P from it and the mask from the seed.
+ * forward and backward.  No probability matrix and no mask is ever stored: the forward keeps one float per row (lse) and,
+ * for 16-bit dtypes, out before its rounding (out_acc); the backward recomputes P from lse and the mask from the seed.
  *
  * Geometry: q [L, N, E], k and v [S, N, E], out [L, N, E]; H heads of D = E / H channels with D % 4 == 0 and
  * 4 <= D <= SELFATTN_MAX_HEAD_DIM.  q, k and v are VIEWS: each has a sequence stride and a batch stride in ELEMENTS
@@ -31,7 +31,8 @@
  *   The generator and the threshold are those of addnorm.h; the last counter word is 1 where addnorm.h has 0, so the two
  *   streams are disjoint under an equal seed.  p == 1 keeps nothing (no word reaches 2^32) and out is exactly 0.
  *
- * Backward.  With delta_i = sum_d(dO * O) of row i and keep / scale as above:
+ * Backward.  With delta_i = sum_d(dO * O) of row i -- O in float, out_acc: delta cancels against dP, and an O rounded to
+ * bfloat16 costs percents of grad_q and grad_k once the softmax is peaked -- and keep / scale as above:
  *     dP = keep * scale * (dO V^T)          dS = P o (dP - delta)            (the identity holds with dropout as well)
  *     dQ = dS K / sqrt(D)                   dK = dS^T Q / sqrt(D)            dV = dropout(P)^T dO
  *   At most two enqueued passes: one over query tiles that loops over the keys and writes grad_q, one over key tiles that
@@ -64,7 +65,7 @@
 extern "C" {
 #endif
 
-#define SELFATTN_ABI_VERSION 1
+#define SELFATTN_ABI_VERSION 2
 
 typedef enum selfattn_status { SELFATTN_OK = 0, SELFATTN_ERR_ARGUMENT = -1, SELFATTN_ERR_HIP = -2 } selfattn_status;
 
@@ -89,18 +90,20 @@ typedef struct selfattn_view {
 int selfattn_version(void);
 const char *selfattn_last_error(void);
 
-/* out [L, N, E], every element written, in one enqueued pass; lse [N * H, L] float when given (a backward will follow).
- * Returns 1.  L == 0 or N == 0: nothing to write, returns 0.  S == 0: returns 0 and writes nothing -- the result is zeros,
- * which the caller provides.  Neither dereferences anything. */
+/* out [L, N, E], every element written, in one enqueued pass; when given (a backward will follow), lse [N * H, L] float and
+ * out_acc [L, N, E] FLOAT, dense: out before its rounding to a 16-bit dtype (with SELFATTN_F32 out is that already and
+ * out_acc may stay NULL).  Returns 1.  L == 0 or N == 0: nothing to write, returns 0.  S == 0: returns 0 and writes nothing
+ * -- the result is zeros, which the caller provides.  Neither dereferences anything. */
 int selfattn_forward(int dtype, const void *q, const selfattn_view *q_view, const void *k, const selfattn_view *k_view,
                      const void *v, const selfattn_view *v_view, const long long *seed, double p, const selfattn_shape *shape,
-                     void *out, void *lse, void *stream);
+                     void *out, void *lse, void *out_acc, void *stream);
 
-/* The gradients that are given -- grad_q [L, N, E], grad_k and grad_v [S, N, E], dense --, every element written.  out and
- * grad_out are dense [L, N, E], lse is the forward's.  Returns the number of passes enqueued: 0 when no gradient is asked for
- * or the problem is empty (L, S or N is 0: the caller provides the zeros), else 1 or 2. */
+/* The gradients that are given -- grad_q [L, N, E], grad_k and grad_v [S, N, E], dense --, every element written.  out_acc
+ * [L, N, E] is FLOAT for every dtype -- the forward's out_acc, or its out with SELFATTN_F32 --, grad_out is dense [L, N, E] in
+ * the storage dtype, lse is the forward's.  Returns the number of passes enqueued: 0 when no gradient is asked for or the
+ * problem is empty (L, S or N is 0: the caller provides the zeros), else 1 or 2. */
 int selfattn_backward(int dtype, const void *q, const selfattn_view *q_view, const void *k, const selfattn_view *k_view,
-                      const void *v, const selfattn_view *v_view, const void *out, const void *grad_out, const void *lse,
+                      const void *v, const selfattn_view *v_view, const void *out_acc, const void *grad_out, const void *lse,
                       const long long *seed, double p, const selfattn_shape *shape, void *grad_q, void *grad_k, void *grad_v,
                       void *stream);
 

@@ -40,16 +40,19 @@ def install(monkeypatch, calls=None):
     def merge(t, like):          # [N, H, rows, D] -> like's [rows, N, E]
         return t.permute(2, 0, 1, 3).reshape(like.shape)
 
-    def forward(code, q, k, v, seed, p, shape, out, lse):
+    def forward(code, q, k, v, seed, p, shape, out, lse, out_acc=None):
         calls.append("forward")
         qh, kh, vh, prob, dropped, keep, inv = _parts(q, k, v, seed, p, shape)
         out.copy_(merge(dropped @ vh, out))
+        if out_acc is not None:              # before the rounding to a 16-bit dtype
+            out_acc.copy_(merge(dropped @ vh, out_acc))
         if lse is not None:
             lse.copy_(torch.logsumexp(qh @ kh.transpose(-1, -2) * inv, -1).reshape(lse.shape))
         return 1
 
     def backward(code, q, k, v, out, grad_out, lse, seed, p, shape, grad_q, grad_k, grad_v):
         calls.append(("backward", grad_q is not None, grad_k is not None, grad_v is not None))
+        assert out.dtype == _acc(q), "the backward takes out in the arithmetic type: the forward's out_acc for 16-bit operands"
         qh, kh, vh, prob, dropped, keep, inv = _parts(q, k, v, seed, p, shape)
         L, N, H = shape.L, shape.N, shape.H
         do = grad_out.to(qh.dtype).reshape(L, N, H, -1).permute(1, 2, 0, 3)

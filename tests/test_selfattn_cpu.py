@@ -3,6 +3,7 @@ ABI of include/selfattn.h (exports, version, argument errors -- no compute calls
 gradients are computed), the drop-in module and the patch with the binding replaced by the torch stand-in of
 tests/fake_selfattn.py, the patched decoder layer on the reference's fixtures, and the compiled path.  The kernels themselves
 are tests/test_selfattn_gpu.py."""
+import collections
 import copy
 import ctypes
 import json
@@ -20,6 +21,7 @@ import addnorm_oracle
 import fake_addnorm
 import fake_selfattn
 import layerglue_cases as LG
+import selfattn_cases as C
 import selfattn_oracle as O
 from conftest import ROOT
 
@@ -84,7 +86,7 @@ def test_library_exports_every_symbol_selfattn_h_declares_and_versions_agree():
     for name in declared:
         assert hasattr(raw, name), name
     lib = _selfattn.load()
-    assert lib.selfattn_version() == _selfattn.SELFATTN_ABI_VERSION == 1 == int(re.search(r"#define SELFATTN_ABI_VERSION (\d+)", header).group(1))
+    assert lib.selfattn_version() == _selfattn.SELFATTN_ABI_VERSION == 2 == int(re.search(r"#define SELFATTN_ABI_VERSION (\d+)", header).group(1))
     assert dict(re.findall(r"SELFATTN_(F32|F64|BF16|F16) = (\d)", header)) == {"F32": "0", "F64": "1", "BF16": "2", "F16": "3"}
     assert int(re.search(r"#define SELFATTN_MAX_HEAD_DIM (\d+)", header).group(1)) == _selfattn.MAX_HEAD_DIM == 64
     assert ctypes.sizeof(_selfattn.Shape) == 40 and ctypes.sizeof(_selfattn.View) == 24
@@ -105,8 +107,8 @@ def test_selfattn_argument_errors_without_gpu():
     err = lib.selfattn_last_error
     shape = lambda L=5, S=6, N=2, E=32, H=8: ctypes.byref(_selfattn.Shape(L, S, N, E, H))        # noqa: E731
     view = lambda seq=64, batch=32, channel=1: ctypes.byref(_selfattn.View(seq, batch, channel))   # noqa: E731
-    fwd = lambda dt=0, q=p, qv=view(), k=p, kv=view(), v=p, vv=view(), seed=p, pr=0.1, s=shape(), out=p, lse=p: lib.selfattn_forward(      # noqa: E731
-        dt, q, qv, k, kv, v, vv, seed, pr, s, out, lse, None)
+    fwd = lambda dt=0, q=p, qv=view(), k=p, kv=view(), v=p, vv=view(), seed=p, pr=0.1, s=shape(), out=p, lse=p, acc=None: lib.selfattn_forward(      # noqa: E731
+        dt, q, qv, k, kv, v, vv, seed, pr, s, out, lse, acc, None)
     bwd = lambda dt=0, q=p, qv=view(), k=p, kv=view(), v=p, vv=view(), out=p, go=p, lse=p, seed=p, pr=0.1, s=shape(), gq=p, gk=p, gv=p: lib.selfattn_backward(      # noqa: E731
         dt, q, qv, k, kv, v, vv, out, go, lse, seed, pr, s, gq, gk, gv, None)
     for call in (fwd, bwd):
@@ -505,6 +507,168 @@ def test_the_namespace_has_no_new_op():
     names = sorted({n.split(".")[0] for n in torch._C._dispatch_get_all_op_names() if n.startswith(prefix)})
     assert len(names) == len(want) == 34 and not any("attention" in n and "multihead" in n for n in names)
     assert not hasattr(ops, "multihead_attention") and "devis_amd.functions.self_attention" in sys.modules
+
+
+# ---- the kernel variants and the inputs of the GPU tests (tests/selfattn_cases.py) -----------------------------------------------
+
+def test_variant_of_restates_the_host_of_the_kernels():
+    source = open(os.path.join(ROOT, "devis_amd", "csrc", "selfattn.hip")).read()
+    # the three rules, where variant_of says they are: a change to either side fails here until the other follows
+    assert source.count("switch ((D + 15) / 16)") == 1 and re.findall(r"Tiles<(\d)>\(\)\);", source) == ["1", "2", "3", "4"]
+    assert source.count("const bool chunk_vec = pb.vec && (n & 3) == 0;") == 3 and source.count("D = pb.D, n = D >> 2;") == 3
+    assert "bool quads(const selfattn_view &v) { return v.seq % 4 == 0 && v.batch % 4 == 0; }" in source
+    assert "bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }" in source
+    assert len(re.findall(r"const bool vec = aligned16\(q\) && aligned16\(k\) && aligned16\(v\) && aligned16\(out", source)) == 2
+    assert [k for k in C.KERNELS if "void %s(" % k in source] == list(C.KERNELS)
+    for name in ("dispatch_kernel", "selfattn_forward", "selfattn_backward", "chunk_vec"):
+        assert name in C.variant_of.__doc__, name
+    for dtype in C.DTYPES:
+        assert [C.variant_of(D, dtype, True)[0] for D in range(4, 65, 4)] == [1] * 4 + [2] * 4 + [3] * 4 + [4] * 4
+        assert [D for D in range(4, 65, 4) if C.variant_of(D, dtype, True)[1]] == [16, 32, 48, 64]
+        assert not any(any(C.variant_of(D, dtype, False)[1:]) for D in range(4, 65, 4))
+    with pytest.raises(AssertionError):
+        C.variant_of(32, F64, True)
+
+
+@pytest.mark.parametrize("name", list(C.VIEWS))
+def test_views_hold_equal_values_and_state_whether_the_call_is_vec(name):
+    from devis_amd.functions import self_attention as A
+    assert list(C.VIEWS) == ["dense", "packed", "batch_first", "shifted", "padded_rows", "only_v_unaligned", "broadcast"]
+    view = C.VIEWS[name]
+    for dtype in C.DTYPES:
+        for L, S, N, H, D in ((5, 7, 2, 3, 4), (7, 5, 3, 1, 4), (1, 1, 1, 1, 4), (6, 6, 1, 2, 16), (3, 9, 4, 1, 20)):
+            dense = C.make_inputs(L, S, N, H, D, dtype)
+            got = view.build(*dense)
+            want = dense if name != "broadcast" else tuple(t[:, :1].expand_as(t) for t in dense[:3]) + dense[3:]
+            for a, b in zip(got, want):
+                assert a.shape == b.shape and a.dtype == dtype and torch.equal(a, b) and A.as_view(a) is a, (name, dtype)
+            assert C.aligned_and_quad_strided(*got) is view.vec(H * D, dtype), (name, dtype, L, S, N, H, D)
+            if name == "broadcast" and N > 1:
+                assert all(t.stride(1) == 0 for t in got[:3])
+    assert C.VIEWS["packed"].vec(4, torch.bfloat16) is False and C.VIEWS["packed"].vec(4, F32) is True
+
+
+def test_the_sweep_and_the_matrices_reach_every_compiled_variant():
+    """A condition on the generator and on the parameter lists, not a measurement."""
+    configs = [C.sweep_config(seed) for seed in C.SWEEP]
+    assert len(configs) == 96 and configs == [C.sweep_config(seed) for seed in C.SWEEP]
+    reached, views, vecs = collections.Counter(), collections.Counter(), set()
+    for c in configs:
+        assert 1 <= c.L <= 80 and 1 <= c.S <= 80 and 1 <= c.N <= 3 and 1 <= c.H <= 4 and c.D in range(4, 65, 4)
+        assert c.p in (0.0, 0.1, 0.5) and c.dtype in C.DTYPES and c.view in C.VIEWS and -(1 << 63) <= c.dropout_seed < 1 << 63
+        ct, chunk, vec = C.variant_of(c.D, c.dtype, C.VIEWS[c.view].vec(c.H * c.D, c.dtype))
+        reached[c.dtype, ct, c.D % 16 == 0] += 1
+        views[c.view] += 1
+        vecs.add((c.dtype, vec, chunk))
+    assert sorted(reached, key=str) == sorted(C.classes(), key=str) and len(reached) == 24 and min(reached.values()) >= 2, reached
+    assert sorted(views) == sorted(C.VIEWS) and min(views.values()) >= 5, views
+    for dtype in C.DTYPES:                   # per element; vector stores with per-element chunks; vector everything
+        assert {(vec, chunk) for d, vec, chunk in vecs if d is dtype} == {(False, False), (True, False), (True, True)}, dtype
+    assert {c.p for c in configs} == {0.0, 0.1, 0.5} and len({c.D for c in configs}) == 16
+    # the head-dimension matrices launch each of the 36 instantiations and compare it with the oracle
+    want = {(kernel, dtype, ct) for kernel in C.KERNELS for dtype in C.DTYPES for ct in (1, 2, 3, 4)}
+    assert C.oracle_matrix_variants() == want and len(want) == 36
+    # the view matrix compares both load paths of every (dtype, CT) bit for bit: "dense" is vec, "shifted" is not
+    both = {(dtype, C.variant_of(D, dtype, True)[0]) for D, dtype in C.VIEW_MATRIX}
+    assert both == {(dtype, ct) for dtype in C.DTYPES for ct in (1, 2, 3, 4)}
+    assert {C.variant_of(D, dtype, True)[1] for D, dtype in C.VIEW_MATRIX} == {True, False}
+    E = [C.VIEW_SHAPE[3] * D for D, _ in C.VIEW_MATRIX]
+    assert all(C.VIEWS["dense"].vec(e, F32) for e in E) and not any(C.VIEWS["shifted"].vec(e, F32) for e in E)
+    # the lists are what the issue sets
+    assert len(C.MATRIX_F32) == 32 and len(C.MATRIX_16) == 36 and len(C.PLANTED) == 48 and len(C.LOPSIDED) == 8
+
+
+@pytest.mark.parametrize("dtype", C.DTYPES)
+def test_the_backward_takes_out_in_float32_before_its_rounding(monkeypatch, dtype):
+    """delta = sum(dO * O) cancels against dP in dS = P (dP - delta): with O rounded to bfloat16 a peaked softmax left grad_q and
+    grad_k off by up to 10 % of their maximum.  The forward writes a float32 copy for the backward of 16-bit operands."""
+    from devis_amd import _selfattn
+    from devis_amd.functions import self_attention as A
+    fake_selfattn.install(monkeypatch)
+    counts, double = [], _selfattn.forward
+    monkeypatch.setattr(_selfattn, "forward", lambda *a: counts.append(len(a)) or double(*a))
+    q, k, v, go = (t.requires_grad_(True) for t in C.make_inputs(5, 7, 2, 2, 8, dtype))
+    out, lse, acc = A.MultiheadAttentionFunction.apply(q, k, v, None, 2, 0.0)
+    assert counts == [9 if dtype == F32 else 10]          # float32: the call as it was before out_acc, for older doubles
+    saved = out.grad_fn.saved_tensors
+    assert out.dtype == dtype and saved[3].dtype == F32 and lse.dtype == F32 and not lse.requires_grad
+    if dtype == F32:
+        assert acc is None and saved[3].data_ptr() == out.data_ptr()
+    else:
+        assert saved[3].data_ptr() == acc.data_ptr() and not acc.requires_grad and torch.equal(acc.to(dtype), out)
+        assert not torch.equal(acc, out.float())
+    with torch.no_grad():
+        assert A._forward(q, k, v, None, 2, 0.0, want_lse=False)[1:] == (None, None)
+    monkeypatch.undo()
+    if dtype != F32:                            # the binding refuses the rounded out before any call
+        with pytest.raises(RuntimeError, match="must be float32"):
+            _selfattn.backward(2, q, k, v, out.detach(), go, lse, None, 0.0, _selfattn.Shape(5, 7, 2, 16, 2), None, None, None)
+
+
+def double_shares(operands, H, D, dtype, p, seed, cancelling=()):
+    """{tensor: max|double - oracle| as a share of max|oracle|} of the CPU double (tests/fake_selfattn.py, installed by the
+    caller) on ``operands``; for the tensors in ``cancelling`` and beside an all-zero oracle the share is of the cancelling
+    terms, as in tests/test_selfattn_gpu.py::compare."""
+    dense = [t.contiguous() for t in operands]
+    L, N, S = dense[0].shape[0], dense[0].shape[1], dense[1].shape[0]
+    keep = None if not p else O.keep_mask(seed, N, H, L, S, p)
+    want = O.attention_grads(*dense[:3], H, dense[3], keep, O.scale_of(p))
+    got = C.run(*operands, H, p, None if not p else torch.tensor([seed], dtype=torch.int64))
+    shares = {}
+    for name, a, b in zip(C.NAMES, got, want):
+        assert a.dtype == dtype and a.shape == b.shape and bool(a.isfinite().all()), name
+        ref = float(b.abs().max())
+        if name in cancelling or ref == 0.0:
+            ref = C.cancelling_terms(*dense, D, p)
+        shares[name] = float((a.double() - b).abs().max()) / ref
+    return shares
+
+
+def double_cases(group):
+    """(what, operands, H, D, dtype, p, seed, cancelling) of every case of a group of GPU tests."""
+    if group == "sweep":
+        for seed in C.SWEEP:
+            c = C.sweep_config(seed)
+            operands = C.VIEWS[c.view].build(*C.make_inputs(c.L, c.S, c.N, c.H, c.D, c.dtype, seed=seed))
+            yield str(c), operands, c.H, c.D, c.dtype, c.p, c.dropout_seed, ()
+    elif group == "float32 matrix":
+        for L, S, N, H, D in C.MATRIX_F32:
+            yield str((L, S, D)), C.make_inputs(L, S, N, H, D), H, D, F32, 0.0, None, ()
+    elif group == "16-bit matrix":
+        for L, S, N, H, D, dtype, p in C.MATRIX_16:
+            yield str((D, dtype, p)), C.make_inputs(L, S, N, H, D, dtype), H, D, dtype, p, C.DROPOUT_SEED, ()
+    elif group == "views":
+        L, S, N, H = C.VIEW_SHAPE
+        for D, dtype in C.VIEW_MATRIX:
+            yield str((D, dtype)), C.make_inputs(L, S, N, H, D, dtype), H, D, dtype, 0.5, C.DROPOUT_SEED, ()
+    elif group == "planted maxima":
+        L, N, H, D = C.PLANTED_SHAPE
+        for S, dtype, p, last, boost in C.PLANTED:
+            operands = C.planted_inputs(L, S, N, H, D, dtype, S - 1 if last else 0, boost)
+            yield str((S, dtype, p, last, boost)), operands, H, D, dtype, p, C.DROPOUT_SEED, ("grad_q", "grad_k") if boost > 9 else ()
+    elif group == "lopsided":
+        for L, S, N, H, D, p in C.LOPSIDED:
+            yield str((L, S, p)), C.make_inputs(L, S, N, H, D), H, D, F32, p, C.DROPOUT_SEED, ()
+
+
+@pytest.mark.parametrize("group", ["sweep", "float32 matrix", "16-bit matrix", "views", "planted maxima", "lopsided"])
+def test_the_inputs_leave_a_correct_implementation_inside_half_of_each_bar(monkeypatch, group):
+    """Every input the GPU tests feed the kernels, through the CPU double -- float32 arithmetic on the rounded operands, results
+    rounded once -- against the float64 oracle: at most HALF of the bar of tests/test_selfattn_gpu.py for each tensor, so that a
+    kernel that misses a bar there is wrong and not unlucky.  Worst shares of max|want| as printed below, float32 / bfloat16 /
+    float16: sweep 7.2e-7 / 3.7e-3 / 4.5e-4; the matrices 6.6e-7 / 3.5e-3 / 4.6e-4; views 4.1e-7 / 3.2e-3 / 3.9e-4; planted maxima
+    9.2e-6 / 3.1e-3 / 3.9e-4; lopsided 6.5e-7 -- 37 % of a bar at most, so the generator needed no restriction.  (With the
+    backward reading the rounded out, as it did, the planted maxima gave 9.5e-2 in bfloat16 and 1.0e-2 in float16.)"""
+    from test_attmap_gpu import TOL
+    fake_selfattn.install(monkeypatch)
+    worst = {}
+    for what, operands, H, D, dtype, p, seed, cancelling in double_cases(group):
+        for name, share in double_shares(operands, H, D, dtype, p, seed, cancelling).items():
+            if share > worst.get(dtype, (0.0,))[0]:
+                worst[dtype] = (share, name, what)
+            assert share <= 0.5 * TOL[dtype], (what, name, share)
+    for dtype, (share, name, what) in worst.items():
+        print("%s %s: the double's worst error %.2e of max |want| (%s of %s), bar %.0e" % (group, dtype, share, name, what, TOL[dtype]))
 
 
 # ---- documents ---------------------------------------------------------------------------------------------------------------

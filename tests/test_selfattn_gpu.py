@@ -13,6 +13,7 @@ import torch
 from torch import nn
 
 import layerglue_cases as LG
+import selfattn_cases as C
 import selfattn_oracle as O
 import stale_memory
 from test_attmap_gpu import TOL, assert_close
@@ -22,29 +23,32 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F32, BF16, F16 = torch.float32, torch.bfloat16, torch.float16
 SIZES = [(1, 1), (16, 16), (17, 15), (33, 70), (300, 300)]                 # (L, S): every tile edge, and the reference's
-HEADS = [(1, 8, 32), (3, 1, 4), (2, 8, 4), (2, 3, 20), (1, 2, 64)]          # (N, H, D): every D class, the reference's first
+HEADS = [(1, 8, 32), (3, 1, 4), (2, 8, 4), (2, 3, 20), (1, 2, 64)]          # (N, H, D): CT = 2, 1, 1, 2, 4 (CT = 3 and every other
+#                                                                            D: the matrices below), the reference's first
 
 
-def make_inputs(L, S, N, H, D, dtype=F32, gain=1.0, seed=0):
-    """q ~ gain * randn, k, v and grad_out ~ randn, rounded once to ``dtype``, on the CPU."""
-    g = torch.Generator().manual_seed(seed)
-    q = (gain * torch.randn(L, N, H * D, generator=g, dtype=torch.float64)).to(dtype)
-    k, v = (torch.randn(S, N, H * D, generator=g, dtype=torch.float64).to(dtype) for _ in range(2))
-    return q, k, v, torch.randn(L, N, H * D, generator=g, dtype=torch.float64).to(dtype)
+make_inputs, run = C.make_inputs, C.run
 
 
 def seed_tensor(value):
     return torch.tensor([value], dtype=torch.int64, device=DEV)
 
 
-def run(q, k, v, grad_out, H, p=0.0, seed=None, wants=(True, True, True)):
-    """(out, grad_q, grad_k, grad_v) of the operator on the GPU tensors given; a gradient that is not wanted is None."""
-    import devis_amd
-    leaves = [t.detach().requires_grad_(want) for t, want in zip((q, k, v), wants)]
-    out = devis_amd.multihead_attention(*leaves, H, p=p, seed=seed)
-    asked = [t for t in leaves if t.requires_grad]
-    grads = iter(torch.autograd.grad(out, asked, grad_out)) if asked else iter(())
-    return (out.detach(),) + tuple(next(grads) if want else None for want in wants)
+def compare(got, want, operands, D, dtype, p=0.0, what="", cancelling=()):
+    """``got`` against the oracle's ``want`` at the bars.  Beside an all-zero oracle, and for the tensors named in
+    ``cancelling``, the bar is tol times the size of the terms that cancel."""
+    q, k, v, go = operands
+    for name, a, b in zip(C.NAMES, got, want):
+        assert a.dtype == dtype and a.shape == b.shape and a.is_contiguous()
+        if name in cancelling or float(b.abs().max()) == 0.0:
+            # S == 1 (grad_q and grad_k are dS = P (dP - delta) times k or q, and dP == delta in exact arithmetic), one-hot rows
+            # (the same, up to what underflows) or p == 1 (everything is dropped): tests/selfattn_cases.py::cancelling_terms
+            terms = C.cancelling_terms(q, k, v, go, D, p)
+            err = float((a.double().cpu() - b).abs().max())
+            print("%s %s: max error %.3e beside an oracle of max %.3e, cancelling terms %.3e" % (what, name, err, float(b.abs().max()), terms))
+            assert bool(a.isfinite().all()) and err <= TOL[dtype] * terms, (what, name, err)
+        else:
+            assert_close(a, b, TOL[dtype], "%s %s" % (what, name))
 
 
 def check(L, S, N, H, D, dtype=F32, gain=1.0, p=0.0, seed=None, what=""):
@@ -52,18 +56,7 @@ def check(L, S, N, H, D, dtype=F32, gain=1.0, p=0.0, seed=None, what=""):
     keep = None if not p else O.keep_mask(seed, N, H, L, S, p)
     want = O.attention_grads(q, k, v, H, go, keep, O.scale_of(p))
     got = run(*(t.to(DEV) for t in (q, k, v, go)), H, p, None if not p else seed_tensor(seed))
-    for name, a, b in zip(("out", "grad_q", "grad_k", "grad_v"), got, want):
-        assert a.dtype == dtype and a.shape == b.shape and a.is_contiguous()
-        if float(b.abs().max()) == 0.0:
-            # S == 1 (grad_q and grad_k are dS = P (dP - delta) times k or q, and dP == delta in exact arithmetic) or p == 1
-            # (everything is dropped).  The bar is tol times the size of the terms that cancel: dP and delta are sums of D
-            # products of grad_out and v, times the largest q or k; with p == 1 those terms are exactly 0.
-            terms = float(go.abs().max() * v.abs().max()) * D * float(max(q.abs().max(), k.abs().max())) if p < 1.0 else 0.0
-            err = float(a.double().abs().max())
-            print("%s %s: max |got| %.3e beside an all-zero oracle, cancelling terms %.3e" % (what, name, err, terms))
-            assert err <= TOL[dtype] * terms, (name, err)
-        else:
-            assert_close(a, b, TOL[dtype], "%s %s" % (what, name))
+    compare(got, want, (q, k, v, go), D, dtype, p, what)
 
 
 def same_bits(a, b):
@@ -86,6 +79,56 @@ def test_16_bit_operands_match_the_oracle(L, S, N, H, D, dtype):
 
 def test_large_logits_stay_within_the_bound():
     check(70, 70, 1, 2, 32, gain=30.0, what="queries x 30")
+
+
+# ---- every compiled variant (tests/selfattn_cases.py lists them; tests/test_selfattn_cpu.py asserts that these lists launch all
+# 36 and that a correct implementation stays within half of each bar on them) ----------------------------------------------------
+
+def check_operands(operands, H, D, dtype, p=0.0, seed=None, what="", cancelling=()):
+    """The operator on ``operands`` (GPU tensors, passed as the views they are) against the oracle on their values."""
+    dense = [t.contiguous().cpu() for t in operands]
+    L, N, S = dense[0].shape[0], dense[0].shape[1], dense[1].shape[0]
+    keep = None if not p else O.keep_mask(seed, N, H, L, S, p)
+    want = O.attention_grads(*dense[:3], H, dense[3], keep, O.scale_of(p))
+    got = run(*operands, H, p, None if not p else seed_tensor(seed))
+    compare(got, want, dense, D, dtype, p, what, cancelling)
+
+
+@pytest.mark.parametrize("L,S,N,H,D", C.MATRIX_F32)
+def test_every_head_dimension_matches_the_oracle_in_float32(L, S, N, H, D):
+    """N, H = 2, 3: the head offset h * D is no multiple of 16 for most D."""
+    check(L, S, N, H, D, what="L %d S %d D %d" % (L, S, D))
+
+
+@pytest.mark.parametrize("L,S,N,H,D,dtype,p", C.MATRIX_16)
+def test_every_tile_count_matches_the_oracle_in_16_bit_with_and_without_dropout(L, S, N, H, D, dtype, p):
+    check(L, S, N, H, D, dtype, p=p, seed=C.DROPOUT_SEED, what="%s D %d p %s" % (dtype, D, p))
+
+
+@pytest.mark.parametrize("S,dtype,p,last,boost", C.PLANTED)
+def test_planted_row_maxima_in_the_first_and_in_the_last_partly_masked_tile(S, dtype, p, last, boost):
+    """Key 0 or S - 1 (the last tile holds 1 key of 16) gains ``boost`` on every logit.  At 9 the softmax is peaked and every
+    tensor meets its bar.  At 60 every later (or earlier) exp underflows against it and rows are one-hot: grad_q and grad_k are
+    pure cancellation -- of the order 1e-23 in the float64 oracle, and float32 torch is off by 100 % of that -- so they are
+    held to the bound on cancelling terms and out and grad_v to their bars.  While the backward took delta from the rounded
+    out, boost 9 left grad_q off by 1.5 % to 3.5 % of max|want| in every bfloat16 case and grad_k by 1.0 % in one float16 case
+    ("What is saved")."""
+    L, N, H, D = C.PLANTED_SHAPE
+    operands = C.planted_inputs(L, S, N, H, D, dtype, S - 1 if last else 0, boost)
+    check_operands([t.to(DEV) for t in operands], H, D, dtype, p, C.DROPOUT_SEED, "S %d %s p %s key %s boost %d" % (
+        S, dtype, p, "S - 1" if last else "0", boost), cancelling=("grad_q", "grad_k") if boost > 9 else ())
+
+
+@pytest.mark.parametrize("L,S,N,H,D,p", C.LOPSIDED)
+def test_lopsided_sizes_match_the_oracle(L, S, N, H, D, p):
+    check(L, S, N, H, D, p=p, seed=C.DROPOUT_SEED, what="L %d S %d p %s" % (L, S, p))
+
+
+@pytest.mark.parametrize("seed", C.SWEEP)
+def test_sweep_through_views_matches_the_oracle(seed):
+    c = C.sweep_config(seed)
+    dense = [t.to(DEV) for t in make_inputs(c.L, c.S, c.N, c.H, c.D, c.dtype, seed=seed)]
+    check_operands(C.VIEWS[c.view].build(*dense), c.H, c.D, c.dtype, c.p, c.dropout_seed, str(c))
 
 
 # ---- views -------------------------------------------------------------------------------------------------------------------
@@ -122,6 +165,27 @@ def test_views_give_the_bits_of_dense_aligned_copies():
     want = run(hq, hk, hv, hgo, H)
     got = run(shifted(hq), shifted(hk), shifted(hv), shifted(hgo), H)
     assert all(same_bits(a, b) for a, b in zip(got, want)) and shifted(hq).data_ptr() % 16 == 2
+
+
+@pytest.mark.parametrize("D,dtype", C.VIEW_MATRIX)
+def test_every_view_gives_the_bits_of_the_dense_call_at_every_variant(D, dtype):
+    """What the test above promises at D = 32, for every CT, with and without the vector chunk path, in every storage type and
+    with dropout: the per-element path ("shifted", "padded_rows", "only_v_unaligned", and "packed" where the k half is not
+    16-byte aligned) and the 8 / 16-byte one give the same bits.  "broadcast" -- batch strides of 0 -- changes the values and
+    is compared with the call on dense copies of its operands."""
+    L, S, N, H = C.VIEW_SHAPE
+    dense = C.VIEWS["dense"].build(*(t.to(DEV) for t in make_inputs(L, S, N, H, D, dtype)))
+    assert C.aligned_and_quad_strided(*dense)
+    seed = seed_tensor(C.DROPOUT_SEED)
+    want = run(*dense, H, 0.5, seed)
+    for name, view in C.VIEWS.items():
+        operands = view.build(*dense)
+        assert C.aligned_and_quad_strided(*operands) is view.vec(H * D, dtype), name
+        ref = want if name != "broadcast" else run(*(t.contiguous() for t in operands), H, 0.5, seed)
+        got = run(*operands, H, 0.5, seed)
+        for what, a, b in zip(C.NAMES, got, ref):
+            assert same_bits(a, b), (name, what)
+    assert not all(same_bits(a, b) for a, b in zip(ref, want))                    # (the broadcast operands are other values)
 
 
 def test_guard_zones_stay_untouched_and_results_are_fully_written(monkeypatch):
@@ -169,12 +233,13 @@ def test_dropout_matches_the_oracle_with_the_restated_mask(p):
     check(17, 15, 3, 1, 4, p=p, seed=-7, what="p %s" % p)
 
 
+@pytest.mark.parametrize("D", [64, 20, 48])
 @pytest.mark.parametrize("p", [0.1, 0.5, 1.0])
-def test_the_mask_is_read_back_exactly(p):
-    """q = 0 gives uniform probabilities 1 / S, and with v_h the identity (S = D = 64) out[i, n, h * D + j] is
-    keep(n, h, i, j) * scale / S."""
+def test_the_mask_is_read_back_exactly(p, D):
+    """q = 0 gives uniform probabilities 1 / S, and with v_h the identity (S = D) out[i, n, h * D + j] is
+    keep(n, h, i, j) * scale / S.  S = D = 64 is four full tiles, 20 ends in a Philox quad past a tile edge, 48 is CT = 3."""
     import devis_amd
-    L, N, H, D = 37, 2, 2, 64
+    L, N, H = 37, 2, 2
     S, value = D, -0x123456789ABCDEF
     v = torch.eye(D, device=DEV)[:, None, None, :].expand(S, N, H, D).reshape(S, N, H * D).contiguous()
     out = devis_amd.multihead_attention(torch.zeros(L, N, H * D, device=DEV), torch.randn(S, N, H * D, device=DEV), v, H, p=p,
@@ -182,7 +247,8 @@ def test_the_mask_is_read_back_exactly(p):
     got = out.view(L, N, H, D).permute(1, 2, 0, 3).cpu()
     keep = O.keep_mask(value, N, H, L, S, p)
     assert torch.equal(got != 0, keep)
-    kept = torch.tensor(O.scale_of(p), dtype=F32) / S
+    # the sum of a row's S ones is exact; the kernels multiply by its float32 reciprocal (exact for S = 64, not for 20 and 48)
+    kept = torch.tensor(O.scale_of(p), dtype=F32) * (torch.ones((), dtype=F32) / S)
     assert torch.equal(got, torch.where(keep, kept, torch.zeros(())))
 
 
@@ -274,30 +340,31 @@ def test_nan_poisons_its_row_or_its_head_and_the_call_returns():
 
 # ---- the module ------------------------------------------------------------------------------------------------------------------
 
-def stock_and_fused(E, H, state=None, dropout=0.0, unit_biases=True):
+def stock_and_fused(E, H, state=None, dropout=0.0, unit_biases=True, batch_first=False):
     """(float64 stock module on the CPU, fused module on the GPU) with equal parameters: ``state``, or torch's initialisation
     with, unless ``unit_biases`` is false, unit-normal biases in place of its zeros."""
     import devis_amd
     torch.manual_seed(2)
-    stock = nn.MultiheadAttention(E, H, dropout=dropout).double().eval()
+    stock = nn.MultiheadAttention(E, H, dropout=dropout, batch_first=batch_first).double().eval()
     if state is not None:
         stock.load_state_dict(state)
     elif unit_biases:
         with torch.no_grad():
             stock.in_proj_bias.normal_()
             stock.out_proj.bias.normal_()
-    fused = devis_amd.FusedMultiheadAttention(E, H, dropout=dropout).eval()
+    fused = devis_amd.FusedMultiheadAttention(E, H, dropout=dropout, batch_first=batch_first).eval()
     fused.load_state_dict(stock.state_dict())
     return stock, fused.to(DEV)
 
 
-def module_results(module, x, value, grad_out):
-    x, value = x.detach().requires_grad_(True), value.detach().requires_grad_(True)
-    out, weights = module(x, x, value, need_weights=False)
+def module_results(module, x, value, grad_out, key=None):
+    """The module on (x, x, value), or on (x, key, value) with a separate key, whose gradient is then "grad.key"."""
+    leaves = [t.detach().requires_grad_(True) for t in ((x, value) if key is None else (x, value, key))]
+    out, weights = module(leaves[0], leaves[0] if key is None else leaves[2], leaves[1], need_weights=False)
     assert weights is None
-    names = [n for n, _ in module.named_parameters()]
-    grads = torch.autograd.grad(out, [x, value] + list(module.parameters()), grad_out)
-    return dict(zip(["out", "grad.x", "grad.value"] + names, (out.detach(),) + grads))
+    names = ["out", "grad.x", "grad.value"] + ["grad.key"] * (key is not None) + [n for n, _ in module.named_parameters()]
+    grads = torch.autograd.grad(out, leaves + list(module.parameters()), grad_out)
+    return dict(zip(names, (out.detach(),) + grads))
 
 
 def test_fused_module_matches_the_stock_module_in_float64_at_the_reference_shape():
@@ -307,6 +374,57 @@ def test_fused_module_matches_the_stock_module_in_float64_at_the_reference_shape
     got = module_results(fused, x.float().to(DEV), value.float().to(DEV), go.float().to(DEV))
     for name in want:
         assert_close(got[name], want[name], TOL[F32], name)
+
+
+def recorded_operator_calls(monkeypatch):
+    """The keyword arguments of every call the module makes to the operator from here on."""
+    from devis_amd.functions import self_attention
+    calls, real = [], self_attention.multihead_attention
+    monkeypatch.setattr(self_attention, "multihead_attention", lambda *a, **k: calls.append(k) or real(*a, **k))
+    return calls
+
+
+def test_fused_module_in_training_mode_matches_the_oracle_under_the_seed_it_drew(monkeypatch):
+    """dropout = 0.5 in training mode at [33, 2, 64], 4 heads of 16: the module draws the seed, the test records the tensor it
+    hands to the operator, restates the mask from it and compares with the float64 restatement of the module -- the stock
+    projections around the oracle's attention with that mask -- output, input gradients and every parameter gradient."""
+    import torch.nn.functional as F
+    E, H, L, N, p = 64, 4, 33, 2, 0.5
+    stock, fused = stock_and_fused(E, H, dropout=p)
+    fused.train()
+    x, value, _, go = (t.float().double() for t in make_inputs(L, L, N, H, E // H, torch.float64))
+    calls = recorded_operator_calls(monkeypatch)
+    got = module_results(fused, x.float().to(DEV), value.float().to(DEV), go.float().to(DEV))
+    assert len(calls) == 1 and calls[0]["p"] == p
+    seed = calls[0]["seed"]
+    assert seed.dtype == torch.int64 and seed.numel() == 1 and seed.is_cuda
+    keep = O.keep_mask(int(seed.item()), N, H, L, L, p)
+    assert 0.4 < float(keep.double().mean()) < 0.6
+    params = {name: t.detach().clone().requires_grad_(True) for name, t in stock.named_parameters()}
+    xs, vs = x.requires_grad_(True), value.requires_grad_(True)
+    weight, bias = params["in_proj_weight"], params["in_proj_bias"]
+    q, k, v = (F.linear(t, weight[i * E:(i + 1) * E], bias[i * E:(i + 1) * E]) for i, t in enumerate((xs, xs, vs)))
+    out = F.linear(O.attention(q, k, v, H, keep, O.scale_of(p)), params["out_proj.weight"], params["out_proj.bias"])
+    grads = torch.autograd.grad(out, [xs, vs] + list(params.values()), go)
+    want = dict(zip(["out", "grad.x", "grad.value"] + list(params), (out.detach(),) + grads))
+    assert sorted(want) == sorted(got) and len(want) == 7
+    for name in want:
+        assert_close(got[name], want[name], TOL[F32], "training " + name)
+
+
+def test_fused_module_matches_the_stock_module_with_a_separate_key_and_batch_first(monkeypatch):
+    """Eval mode, [N, L, E] inputs, L = 21 queries on S = 50 keys, 2 heads of 48 (CT = 3): three projections, operands that are
+    transposed views."""
+    E, H, L, S, N = 96, 2, 21, 50, 2
+    stock, fused = stock_and_fused(E, H, batch_first=True)
+    x, key, value, go = (t.transpose(0, 1).contiguous() for t in make_inputs(L, S, N, H, E // H, torch.float64))
+    assert tuple(x.shape) == (N, L, E) and tuple(key.shape) == (N, S, E)
+    want = module_results(stock, x, value, go, key)
+    calls = recorded_operator_calls(monkeypatch)
+    got = module_results(fused, *(t.float().to(DEV) for t in (x, value, go, key)))
+    assert len(calls) == 1 and calls[0]["p"] == 0.0 and sorted(want) == sorted(got) and len(want) == 8
+    for name in want:
+        assert_close(got[name], want[name], TOL[F32], "separate key, batch_first: " + name)
 
 
 def decoder_case(device, dtype):
