@@ -396,15 +396,9 @@ def bwd_workspace(device, batch, num_query, num_heads, virtual_levels):
 
 
 def backward(value, shapes, lsi, loc, aw, grad_out, grad_value, grad_loc, grad_aw):
-    N, S, M, D = value.shape
-    _, Lq, _, L, P, _ = loc.shape
-    with _on(value.device):
-        ws = bwd_workspace(value.device, N, Lq, M, L)
-        rc = load().msda_backward(type_code(value.dtype, loc.dtype), _p(value), _p(shapes), _p(lsi), _p(loc), _p(aw),
-                                  _p(grad_out), N, S, M, D, L, Lq, P,
-                                  _p(grad_value), dtype_code(grad_value.dtype), _p(grad_loc), _p(grad_aw), _p(ws), ws.numel() * 4,
-                                  value_strides(value), shapes_hint(shapes), _stream(value))
-    _check(rc, "msda_backward")
+    """The full backward: :func:`backward_grads` with GRAD_ALL (looked up when called, so that a replaced
+    ``backward_grads`` sees this call too)."""
+    return backward_grads(GRAD_ALL, value, shapes, lsi, loc, aw, grad_out, grad_value, grad_loc, grad_aw)
 
 
 def bwd_workspace_det(device, clips, frames, S, M, D):
@@ -444,12 +438,18 @@ def backward_grads(grads, value, shapes, lsi, loc, aw, grad_out, grad_value, gra
     _check(rc, "msda_backward_grads")
 
 
-def temporal_forward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, clips, out):
-    G, S, M, D = value.shape
-    frames = G // clips
+def _temporal_sizes(value, clips, ftab, loc_c, loc_t):
+    """(frames, Lq, L, Pc, window, Pt) of a fused temporal call on ``value [clips*frames, S, M, D]``."""
+    frames = value.shape[0] // clips
     _, Lq, _, L, Pc, _ = loc_c.shape
     window = ftab.shape[1] if ftab is not None else 0
     Pt = loc_t.shape[4] if window else 1
+    return frames, Lq, L, Pc, window, Pt
+
+
+def temporal_forward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, clips, out):
+    G, S, M, D = value.shape
+    frames, Lq, L, Pc, window, Pt = _temporal_sizes(value, clips, ftab, loc_c, loc_t)
     with _on(value.device):
         rc = load().msda_temporal_forward(
             type_code(value.dtype, loc_c.dtype), _p(value), _p(shapes), _p(lsi), _p(ftab), _p(loc_c), _p(aw_c),
@@ -460,30 +460,17 @@ def temporal_forward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, clips, 
 
 def temporal_backward(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_out, clips,
                       grad_value, gloc_c, gaw_c, gloc_t, gaw_t, workspace=None):
-    G, S, M, D = value.shape
-    frames = G // clips
-    _, Lq, _, L, Pc, _ = loc_c.shape
-    window = ftab.shape[1] if ftab is not None else 0
-    Pt = loc_t.shape[4] if window else 1
-    with _on(value.device):
-        ws = workspace if workspace is not None else bwd_workspace(value.device, G, Lq, M, L * (1 + window))
-        rc = load().msda_temporal_backward(
-            type_code(value.dtype, loc_c.dtype), _p(value), _p(shapes), _p(lsi), _p(ftab), _p(loc_c), _p(aw_c),
-            _p(loc_t), _p(aw_t), _p(grad_out), clips, frames, window, S, M, D, L, Lq, Pc, Pt,
-            _p(grad_value), dtype_code(grad_value.dtype), _p(gloc_c), _p(gaw_c), _p(gloc_t), _p(gaw_t), _p(ws), ws.numel() * 4,
-            value_strides(value, frames), shapes_hint(shapes), _stream(value))
-    _check(rc, "msda_temporal_backward")
+    """The full backward: :func:`temporal_backward_grads` with GRAD_ALL (looked up when called, as in :func:`backward`)."""
+    return temporal_backward_grads(GRAD_ALL, value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_out, clips,
+                                   grad_value, gloc_c, gaw_c, gloc_t, gaw_t, workspace)
 
 
 def temporal_backward_grads(grads, value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_out, clips,
                             grad_value, gloc_c, gaw_c, gloc_t, gaw_t, workspace=None):
-    """msda_temporal_backward_grads: as temporal_backward, for the gradient groups in `grads` only (GRAD_SAMPLING: the
-    four grad_loc / grad_aw outputs).  The outputs of a group that is not asked for may be None."""
+    """msda_temporal_backward_grads: the gradient groups in `grads` only (GRAD_VALUE: grad_value; GRAD_SAMPLING: the
+    four grad_loc / grad_aw outputs).  The outputs of a group that is not asked for may be None and are not written."""
     G, S, M, D = value.shape
-    frames = G // clips
-    _, Lq, _, L, Pc, _ = loc_c.shape
-    window = ftab.shape[1] if ftab is not None else 0
-    Pt = loc_t.shape[4] if window else 1
+    frames, Lq, L, Pc, window, Pt = _temporal_sizes(value, clips, ftab, loc_c, loc_t)
     with _on(value.device):
         ws = _grads_workspace(grads, workspace, value.device, G, Lq, M, L * (1 + window), value.shape, clips)
         rc = load().msda_temporal_backward_grads(

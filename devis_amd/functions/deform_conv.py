@@ -255,3 +255,25 @@ def _backward(grad_out, input, offset, weight, mask, stride, padding, dilation, 
     if want_b:
         grad_bias = grad_out.sum(dim=(0, 2, 3), dtype=acc).to(dt)
     return (grad_input, goff if grads & NEED_OFFSET else None, gmsk if grads & NEED_MASK else None, grad_weight, grad_bias)
+
+
+def setup_context(ctx, inputs, output):
+    # inputs: the 8 of ``deform_conv2d``, or the 9 of ``deform_conv2d_pinned`` (reproducible_grad_input last).
+    # ctx.pinned exists only in the second case: backward() tells the two ops apart by it.
+    input, offset, weight, bias, stride, padding, dilation, mask = inputs[:8]
+    ctx.geometry = (stride, padding, dilation)
+    if len(inputs) > 8:
+        ctx.pinned = bool(inputs[8])
+    ctx.save_for_backward(input, offset, weight, mask)
+
+
+def backward(run, ctx, grad_out):
+    """The autograd formula of both forward ops; ``run`` has the signature of :func:`_backward`: the backward op with its
+    empty gradients mapped to None.  One gradient slot per input the op was given."""
+    input, offset, weight, mask = ctx.saved_tensors
+    needs = ctx.needs_input_grad
+    pinned = getattr(ctx, "pinned", None)
+    grads = grads_mask(needs[0], needs[1], needs[7] and mask is not None, needs[2], needs[3]) | pin_bits(pinned)
+    gi, go, gm, gw, gb = run(grad_out, input, offset, weight, mask, *ctx.geometry, grads)
+    slots = (gi, go, gw, gb, None, None, None, gm)
+    return slots if pinned is None else slots + (None,)

@@ -11,14 +11,16 @@ An operator's autograd formula is written once, next to its host code in ``devis
 ``setup_context(ctx, inputs, output)`` and a ``backward(run, ctx, *grads)`` whose ``run`` computes the gradients.  The eager
 Function binds ``run`` to the host function; ``register_autograd`` here binds it to the backward op (``op_runner``: the
 0-element tensors that stand for gradients not computed become None again).  Nothing in this module says what is saved or
-where a gradient goes -- except for the deformable convolution, whose only formula is here.  The ops:
+where a gradient goes.  The ops:
 
 =============================  ==========================================================================================
 ``ms_deform_attn_forward``     ``MSDeformAttnFunction`` forward (the im2col chunk loop), + the module's ``sum(H*W) == S``
-``ms_deform_attn_backward``    ``MSDeformAttnFunction`` backward -> (grad_value, grad_loc, grad_aw)
-``*_backward_grads``           the two backwards for a partial ``grads`` mask (``_native.GRAD_VALUE`` / ``GRAD_SAMPLING``):
-                               a group not asked for comes back as a tensor with 0 elements
-``temporal_forward/backward``  ``MSDeformAttnTemporalFunction``
+``ms_deform_attn_backward``    ``MSDeformAttnFunction`` backward with every gradient -> (grad_value, grad_loc, grad_aw)
+``temporal_forward/backward``  ``MSDeformAttnTemporalFunction``, likewise
+``*_backward_grads``           the same two backwards with a ``grads`` mask (``_native.GRAD_VALUE`` / ``GRAD_SAMPLING``):
+                               a group not asked for comes back as a tensor with 0 elements.  A formula names the full op
+                               for ``GRAD_ALL`` and this one for a partial mask; both run the one host function, which
+                               reaches the library through ``_native.backward_grads`` / ``temporal_backward_grads`` alone
 ``prep_forward/backward``      ``MSDeformPrepFunction`` (no temporal part: ``loc_t`` / ``aw_t`` come back with 0 slots)
 ``prep_fused_forward/backward``  ``MSDeformPrepFusedFunction``
 ``frame_table``                the temporal modules' frame table ``[T, W]`` int32 (cache and deferred range checks)
@@ -421,22 +423,8 @@ def _fake_deform_conv2d_backward(grad_out, input, offset, weight, mask, stride, 
             _empty(weight, (weight.shape[0],) if grads & _D.NEED_BIAS else (0,)))
 
 
-def _setup_deform_conv2d(ctx, inputs, output):
-    input, offset, weight, bias, stride, padding, dilation, mask = inputs
-    ctx.geometry = (stride, padding, dilation)
-    ctx.save_for_backward(input, offset, weight, mask)
-
-
-def _backward_deform_conv2d(ctx, grad_out):
-    input, offset, weight, mask = ctx.saved_tensors
-    needs = ctx.needs_input_grad
-    grads = _D.grads_mask(needs[0], needs[1], needs[7] and mask is not None, needs[2], needs[3])
-    grads |= _D.pin_bits(getattr(ctx, "pinned", None))
-    gi, go, gm, gw, gb = none_slots(deform_conv2d_backward(grad_out, input, offset, weight, mask, *ctx.geometry, grads))
-    return gi, go, gw, gb, None, None, None, gm
-
-
-deform_conv2d_op.register_autograd(_backward_deform_conv2d, setup_context=_setup_deform_conv2d)
+deform_conv2d_op.register_autograd(functools.partial(_D.backward, op_runner(deform_conv2d_backward)),
+                                   setup_context=_D.setup_context)
 
 
 # The process-wide switch of reproducible_grad_input is read inside the backward op, when it runs.  What ONE call pins has to
@@ -456,16 +444,8 @@ def _(input, offset, weight, bias, stride, padding, dilation, mask, reproducible
     return _empty(input, (input.shape[0], weight.shape[0], Ho, Wo))
 
 
-def _setup_deform_conv2d_pinned(ctx, inputs, output):
-    _setup_deform_conv2d(ctx, inputs[:8], output)
-    ctx.pinned = bool(inputs[8])
-
-
-def _backward_deform_conv2d_pinned(ctx, grad_out):
-    return _backward_deform_conv2d(ctx, grad_out) + (None,)
-
-
-deform_conv2d_pinned_op.register_autograd(_backward_deform_conv2d_pinned, setup_context=_setup_deform_conv2d_pinned)
+deform_conv2d_pinned_op.register_autograd(functools.partial(_D.backward, op_runner(deform_conv2d_backward)),
+                                          setup_context=_D.setup_context)
 
 
 def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), mask=None, *,

@@ -195,6 +195,7 @@ def test_deterministic_mode_raises_or_warns_only_when_grad_input_is_asked_for():
 def test_needs_input_grad_maps_to_the_gradient_mask(monkeypatch):
     from devis_amd import ops
     from devis_amd.functions import deform_conv as D
+    from devis_amd.functions._common import op_runner
     assert D.grads_mask(True, False, False, False, False) == D.NEED_INPUT == 1
     assert D.grads_mask(False, True, True, False, False) == D.NEED_OFFSET | D.NEED_MASK == 6
     assert D.grads_mask(True, True, True, True, True) == D.NEED_ALL == 31
@@ -213,7 +214,7 @@ def test_needs_input_grad_maps_to_the_gradient_mask(monkeypatch):
                               ((True, False, False, False, False, False, False, False), a["mask"], 1)):
         ctx = types.SimpleNamespace(saved_tensors=(a["input"], a["offset"], a["weight"], mask), needs_input_grad=needs,
                                     geometry=([1, 1], [1, 1], [1, 1]))
-        out = ops._backward_deform_conv2d(ctx, torch.zeros(2, 3, 5, 6))
+        out = D.backward(op_runner(ops.deform_conv2d_backward), ctx, torch.zeros(2, 3, 5, 6))
         assert seen[-1] == want and len(out) == 8 and out[4:7] == (None, None, None)
 
 

@@ -163,6 +163,7 @@ def test_the_module_attribute_reaches_the_backward_op_as_a_pin_bit(monkeypatch, 
     """The layer's override travels forward op -> setup_context -> `grads` of the 9-argument backward op; None adds no bit."""
     from devis_amd import ops
     from devis_amd.functions import deform_conv as D
+    from devis_amd.functions._common import op_runner
     from devis_amd.modules import ModulatedDeformableConv2d
     seen = []
 
@@ -177,13 +178,14 @@ def test_the_module_attribute_reaches_the_backward_op_as_a_pin_bit(monkeypatch, 
         ctx = types.SimpleNamespace(needs_input_grad=(True, True, True, True, False, False, False, True))
         inputs = (x, off, w, None, [1, 1], [1, 1], [1, 1], m)
         ctx.save_for_backward = lambda *t: setattr(ctx, "saved_tensors", t)
+        run = op_runner(ops.deform_conv2d_backward)
         if pinned is None:
-            ops._setup_deform_conv2d(ctx, inputs, None)
-            out = ops._backward_deform_conv2d(ctx, torch.zeros(2, 3, 5, 6))
+            D.setup_context(ctx, inputs, None)
+            out = D.backward(run, ctx, torch.zeros(2, 3, 5, 6))
             assert len(out) == 8
         else:
-            ops._setup_deform_conv2d_pinned(ctx, inputs + (pinned,), None)
-            out = ops._backward_deform_conv2d_pinned(ctx, torch.zeros(2, 3, 5, 6))
+            D.setup_context(ctx, inputs + (pinned,), None)
+            out = D.backward(run, ctx, torch.zeros(2, 3, 5, 6))
             assert len(out) == 9 and out[8] is None
         assert seen[-1] == want
     # the module hands its attribute to the operator; the default is None, and it is in no state dict

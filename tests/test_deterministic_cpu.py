@@ -1,7 +1,7 @@
 """torch.use_deterministic_algorithms(True) on the host side (no GPU): the Functions and ops hand the library
 MSDA_GRAD_DETERMINISTIC exactly when the flag is set and grad_value is asked for, the binding then sizes the workspace with
 msda_backward_workspace_bytes_det, and the custom ops still pass opcheck.  The library is stood in for by the oracle-backed
-tests/fake_native.py plus recording doubles of the two grads bindings."""
+tests/fake_native.py, which records every call of the two grads bindings."""
 import contextlib
 
 import pytest
@@ -25,42 +25,9 @@ def flag():
 
 @pytest.fixture
 def calls(monkeypatch):
-    """fake_native plus doubles of backward_grads / temporal_backward_grads that honour the contract and record
-    (binding, grads) of every backward call."""
-    from devis_amd import _native
-    fake_native.install(monkeypatch)
+    """tests/fake_native.py, recording (binding, grads) of every backward call."""
     seen = []
-    full, temporal_full = _native.backward, _native.temporal_backward
-
-    def backward(*a):
-        seen.append(("backward", ALL))
-        full(*a)
-
-    def temporal_backward(*a, **k):
-        seen.append(("temporal_backward", ALL))
-        temporal_full(*a, **k)
-
-    def backward_grads(grads, value, shapes, lsi, loc, aw, grad_out, grad_value, grad_loc, grad_aw, workspace=None):
-        seen.append(("backward_grads", grads))
-        outs = [torch.empty(value.shape, dtype=value.dtype), torch.empty_like(loc), torch.empty_like(aw)]
-        full(value, shapes, lsi, loc, aw, grad_out, *outs)
-        for dst, src in zip((grad_value, grad_loc, grad_aw), outs):
-            if dst is not None:
-                dst.copy_(src)
-
-    def temporal_backward_grads(grads, value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_out, clips, grad_value,
-                                gloc_c, gaw_c, gloc_t, gaw_t, workspace=None):
-        seen.append(("temporal_backward_grads", grads))
-        outs = [torch.empty(value.shape, dtype=value.dtype)] + [torch.empty_like(x) for x in (loc_c, aw_c, loc_t, aw_t)]
-        temporal_full(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_out, clips, *outs)
-        for dst, src in zip((grad_value, gloc_c, gaw_c, gloc_t, gaw_t), outs):
-            if dst is not None:
-                dst.copy_(src)
-
-    monkeypatch.setattr(_native, "backward", backward)
-    monkeypatch.setattr(_native, "temporal_backward", temporal_backward)
-    monkeypatch.setattr(_native, "backward_grads", backward_grads)
-    monkeypatch.setattr(_native, "temporal_backward_grads", temporal_backward_grads)
+    fake_native.install(monkeypatch, calls=seen)
     return seen
 
 
@@ -94,10 +61,7 @@ def test_plain_function_passes_the_bit_iff_the_flag_is_set(calls, flag, mode):
     torch.use_deterministic_algorithms(mode != "off", warn_only=mode == "warn_only")
     t = _plain()
     got = _plain_backward(t)
-    if mode == "off":
-        assert calls == [("backward", ALL)] * 2                      # im2col_step 1, N = 2: unchanged
-    else:
-        assert calls == [("backward_grads", ALL | DET)] * 2
+    assert calls == [("backward_grads", ALL if mode == "off" else ALL | DET)] * 2      # im2col_step 1, N = 2
     torch.use_deterministic_algorithms(False)
     ref = _plain_backward(t)
     for a, b in zip(got, ref):
@@ -108,8 +72,7 @@ def test_plain_function_passes_the_bit_iff_the_flag_is_set(calls, flag, mode):
 def test_temporal_function_passes_the_bit_iff_the_flag_is_set(calls, flag, mode):
     torch.use_deterministic_algorithms(mode != "off", warn_only=mode == "warn_only")
     _temporal_backward(_temporal())
-    want = ("temporal_backward", ALL) if mode == "off" else ("temporal_backward_grads", ALL | DET)
-    assert calls == [want]
+    assert calls == [("temporal_backward_grads", ALL if mode == "off" else ALL | DET)]
 
 
 def test_no_bit_without_grad_value(calls, flag):
@@ -175,6 +138,48 @@ def test_binding_sizes_the_workspace_with_the_deterministic_query(fake_lib):
     _native.temporal_backward_grads(VALUE | DET, tt["value"], tt["shapes"], tt["lsi"], tt["ftab"], tt["loc_c"], tt["aw_c"],
                                     tt["loc_t"], tt["aw_t"], tt["grad_out"], 1, *outs)
     assert fake_lib.log == [("ws_det", (1, G, S, M, D)), ("temporal_backward_grads", VALUE | DET, 4096)]
+
+
+def test_full_backward_wrappers_delegate_to_the_grads_bindings(fake_lib):
+    """_native.backward / temporal_backward (the benchmark's, the tuner's and the scripts' entry points) are the grads
+    bindings with GRAD_ALL: one library call each, the workspace queried when none is given, else the caller's taken as it
+    is -- as a keyword and as the 16th positional argument."""
+    from devis_amd import _native
+    t = _plain(torch.float32)
+    gv = torch.empty(t["value"].shape)
+    gl, ga = torch.empty_like(t["loc"]), torch.empty_like(t["aw"])
+    _native.backward(t["value"], t["shapes"], t["lsi"], t["loc"], t["aw"], t["grad_out"], gv, gl, ga)
+    N, S, M, D = t["value"].shape
+    Lq, L = t["loc"].shape[1], t["loc"].shape[3]
+    assert fake_lib.log == [("ws", (N, Lq, M, L)), ("backward_grads", ALL, 1000)]
+
+    tt = _temporal(torch.float32)
+    G, W = tt["value"].shape[0], tt["ftab"].shape[1]
+    args = [tt[k] for k in ("value", "shapes", "lsi", "ftab", "loc_c", "aw_c", "loc_t", "aw_t", "grad_out")] + [1]
+    outs = [torch.empty(tt["value"].shape)] + [torch.empty_like(tt[k]) for k in ("loc_c", "aw_c", "loc_t", "aw_t")]
+    fake_lib.log.clear()
+    _native.temporal_backward(*args, *outs)
+    assert fake_lib.log == [("ws", (G, Lq, M, L * (1 + W))), ("temporal_backward_grads", ALL, 1000)]
+    ws = torch.empty(300, dtype=torch.int32)
+    fake_lib.log.clear()
+    _native.temporal_backward(*args, *outs, workspace=ws)
+    _native.temporal_backward(*args, *outs, ws)
+    assert fake_lib.log == [("temporal_backward_grads", ALL, 1200)] * 2
+
+
+def test_full_backward_wrappers_reach_a_replaced_grads_binding(calls):
+    """The wrappers look their target up when called: with the grads bindings replaced (here by tests/fake_native.py) a call
+    through _native.backward / temporal_backward arrives at the replacement."""
+    from devis_amd import _native
+    t = _plain()
+    outs = [torch.full_like(t[k], float("nan")) for k in ("value", "loc", "aw")]
+    _native.backward(t["value"], t["shapes"], t["lsi"], t["loc"], t["aw"], t["grad_out"], *outs)
+    tt = _temporal()
+    touts = [torch.full_like(tt[k], float("nan")) for k in ("value", "loc_c", "aw_c", "loc_t", "aw_t")]
+    _native.temporal_backward(*(tt[k] for k in ("value", "shapes", "lsi", "ftab", "loc_c", "aw_c", "loc_t", "aw_t", "grad_out")),
+                              1, *touts)
+    assert calls == [("backward_grads", ALL), ("temporal_backward_grads", ALL)]
+    assert not any(torch.isnan(x).any() for x in outs + touts)
 
 
 def test_deterministic_symbols_and_bit_are_declared():

@@ -1,5 +1,5 @@
-"""Which gradients the backward computes (grads mask), on the oracle-backed CPU double: no GPU needed.  The double of
-the two new bindings (msda_backward_grads / msda_temporal_backward_grads) is defined here, on top of tests/fake_native."""
+"""Which gradients the backward computes (grads mask), on the oracle-backed CPU double of the two bindings
+(msda_backward_grads / msda_temporal_backward_grads) in tests/fake_native.py: no GPU needed."""
 import numpy as np
 import pytest
 import torch
@@ -7,53 +7,14 @@ import torch
 import fake_native
 from helpers import make_inputs, make_temporal_inputs
 
-VALUE, SAMPLING, ALL = 1, 2, 3
+VALUE, SAMPLING = 1, 2
 
 
 @pytest.fixture
 def calls(monkeypatch):
-    """fake_native plus a double of backward_grads / temporal_backward_grads that honours the contract (only the groups
-    asked for are written; the others may be None) and records (binding, mask) of every backward call."""
-    from devis_amd import _native
-    fake_native.install(monkeypatch)
+    """tests/fake_native.py, recording (binding, grads) of every backward call."""
     seen = []
-    full, temporal_full = _native.backward, _native.temporal_backward
-
-    def backward(*a):
-        seen.append(("backward", ALL))
-        full(*a)
-
-    def temporal_backward(*a, **k):
-        seen.append(("temporal_backward", ALL))
-        temporal_full(*a, **k)
-
-    def backward_grads(grads, value, shapes, lsi, loc, aw, grad_out, grad_value, grad_loc, grad_aw, workspace=None):
-        assert grads in (VALUE, SAMPLING)
-        assert (grad_value is not None) == bool(grads & VALUE) and (grad_loc is not None) == bool(grads & SAMPLING)
-        seen.append(("backward_grads", grads))
-        outs = [torch.empty(value.shape, dtype=grad_value.dtype if grad_value is not None else value.dtype),
-                torch.empty_like(loc), torch.empty_like(aw)]
-        full(value, shapes, lsi, loc, aw, grad_out, *outs)
-        for dst, src in zip((grad_value, grad_loc, grad_aw), outs):
-            if dst is not None:
-                dst.copy_(src)
-
-    def temporal_backward_grads(grads, value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_out, clips, grad_value,
-                                gloc_c, gaw_c, gloc_t, gaw_t, workspace=None):
-        assert grads in (VALUE, SAMPLING)
-        assert (grad_value is not None) == bool(grads & VALUE) and (gloc_c is not None) == bool(grads & SAMPLING)
-        seen.append(("temporal_backward_grads", grads))
-        outs = [torch.empty(value.shape, dtype=grad_value.dtype if grad_value is not None else value.dtype)] + \
-            [torch.empty_like(x) for x in (loc_c, aw_c, loc_t, aw_t)]
-        temporal_full(value, shapes, lsi, ftab, loc_c, aw_c, loc_t, aw_t, grad_out, clips, *outs)
-        for dst, src in zip((grad_value, gloc_c, gaw_c, gloc_t, gaw_t), outs):
-            if dst is not None:
-                dst.copy_(src)
-
-    monkeypatch.setattr(_native, "backward", backward)
-    monkeypatch.setattr(_native, "temporal_backward", temporal_backward)
-    monkeypatch.setattr(_native, "backward_grads", backward_grads, raising=False)
-    monkeypatch.setattr(_native, "temporal_backward_grads", temporal_backward_grads, raising=False)
+    fake_native.install(monkeypatch, calls=seen)
     return seen
 
 
@@ -78,7 +39,7 @@ def test_plain_function_reaches_the_binding_and_mask_its_needs_give(calls, subse
     out = MSDeformAttnFunction.apply(leaves[0], t["shapes"], t["lsi"], leaves[1], leaves[2], 1)
     got = out.grad_fn.apply(t["grad_out"])
     want = (VALUE if subset[0] else 0) | (SAMPLING if subset[1] or subset[2] else 0)
-    assert calls == [("backward" if want == ALL else "backward_grads", want)] * 2      # im2col_step 1, N = 2
+    assert calls == [("backward_grads", want)] * 2      # im2col_step 1, N = 2
     for g, s in zip((got[0], got[3], got[4]), subset):
         assert (g is not None) == bool(s)
     # the gradients that are computed are the full backward's
@@ -100,7 +61,7 @@ def test_temporal_function_reaches_the_binding_and_mask_its_needs_give(calls, su
     out = MSDeformAttnTemporalFunction.apply(v, t["shapes"], t["lsi"], t["ftab"], lc, ac, lt, at, 1)
     got = out.grad_fn.apply(t["grad_out"])
     want = (VALUE if subset[0] else 0) | (SAMPLING if subset[1] or subset[2] else 0)
-    assert calls == [("temporal_backward" if want == ALL else "temporal_backward_grads", want)]
+    assert calls == [("temporal_backward_grads", want)]
     assert (got[0] is not None) == bool(subset[0])
     for g, s in zip(got[4:8], (subset[1], subset[2], subset[1], subset[2])):
         assert (g is not None) == bool(s)

@@ -25,7 +25,7 @@ def _routes_of_backward(fn):
     """Run `fn` (a forward + backward through autograd) and return what msda_last_route() said on the backward's thread."""
     from devis_amd import _native
     seen = []
-    orig = _native.temporal_backward, _native.backward
+    orig = _native.temporal_backward_grads, _native.backward_grads     # (the bindings every backward call goes through)
 
     def tb(*a, **k):
         orig[0](*a, **k)
@@ -34,11 +34,11 @@ def _routes_of_backward(fn):
     def pb(*a, **k):
         orig[1](*a, **k)
         seen.append(_native.last_route())
-    _native.temporal_backward, _native.backward = tb, pb
+    _native.temporal_backward_grads, _native.backward_grads = tb, pb
     try:
         out = fn()
     finally:
-        _native.temporal_backward, _native.backward = orig
+        _native.temporal_backward_grads, _native.backward_grads = orig
     return out, seen
 
 
