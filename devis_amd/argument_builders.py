@@ -755,3 +755,22 @@ def unpatch_self_attention(previous):
     """Undo :func:`patch_self_attention`."""
     from .modules import self_attention
     self_attention.unpatch(previous)
+
+
+def patch_window_attention(swin_backbone_module):
+    """Opt-in: make ``forward`` of the reference's ``SwinTransformerBlock`` (``src.models.swin_backbone``) run its cyclic shift,
+    window partition, attention with relative-position bias and shift mask, window merge and reverse shift as one
+    :func:`devis_amd.window_attention` call between ``self.attn.qkv`` and ``self.attn.proj``
+    (:mod:`devis_amd.modules.window_attention`, which lists when the replaced forward runs instead: while compiling, on the CPU,
+    in float64, with attention dropout in training, with a window or head dimension the kernels do not take).  The
+    ``mask_matrix`` argument is accepted and not read.  Takes effect at once, also for blocks that already exist (the method is
+    looked up on the class) and under ``use_checkpoint``; no module is replaced, so state dicts are untouched.  Independent of
+    every other patch.  Returns what was replaced (:func:`unpatch_window_attention`)."""
+    from .modules import window_attention
+    return window_attention.patch(swin_backbone_module)
+
+
+def unpatch_window_attention(swin_backbone_module, previous):
+    """Undo :func:`patch_window_attention`."""
+    from .modules import window_attention
+    window_attention.unpatch(swin_backbone_module, previous)
