@@ -25,7 +25,10 @@ layers -- residual, dropout and LayerNorm, and the FFN's relu and dropout (``dev
 of its decoder layers between the projections of ``nn.MultiheadAttention`` (``devis_amd.multihead_attention``; the module
 ``devis_amd.modules.FusedMultiheadAttention``; ``devis_amd.patch_self_attention``; C ABI ``include/selfattn.h``) and the
 (shifted-)window attention of its Swin backbone between the ``qkv`` and ``proj`` Linears of a ``SwinTransformerBlock``
-(``devis_amd.window_attention``; ``devis_amd.patch_window_attention``; C ABI ``include/winattn.h``).
+(``devis_amd.window_attention``; ``devis_amd.patch_window_attention``; C ABI ``include/winattn.h``) and the glue around
+that attention and the blocks' Linears -- the residual add with its drop-path scale, the pre-norm LayerNorm written into the
+zero-padded window map, and the patch merge's gather with its norm (``devis_amd.residual_layer_norm``,
+``devis_amd.patch_merge_norm``; ``devis_amd.patch_swin_glue``; C ABI ``include/prenorm.h``).
 
 Arithmetic lives in hand-written HIP kernels behind the C ABI of ``include/msda.h``
 (``devis_amd/csrc/*.hip``, one translation unit per kernel family -> ``devis_amd/libmsda_hip.so``); the Python here is the host side.
@@ -61,9 +64,11 @@ from .functions.self_attention import multihead_attention  # noqa: F401  (eager 
 from .modules import FusedMultiheadAttention  # noqa: F401
 from .argument_builders import patch_window_attention, unpatch_window_attention  # noqa: F401
 from .functions.window_attention import window_attention  # noqa: F401  (eager kernels; the torch composite while compiling)
+from .argument_builders import patch_swin_glue, unpatch_swin_glue  # noqa: F401
+from .functions.pre_norm import patch_merge_norm, residual_layer_norm  # noqa: F401  (eager kernels; the torch composite while compiling)
 from .tracking import LogitMask  # noqa: F401
 from .graphs import graphed, graph_stream, GraphedLayer  # noqa: F401
 from .tuning import tune  # noqa: F401
 
 __all__ = ["MSDeformAttnFunction", "MSDeformAttnTemporalFunction", "ms_deform_attn_core_pytorch",
-           "MSDeformAttn", "TemporalMSDeformAttnEncoder", "TemporalMSDeformAttnDecoder", "ModulatedDeformableConv2d", "MultiScaleMHAttentionMap", "deform_conv2d", "attention_maps", "patch_attention_maps", "unpatch_attention_maps", "mask_head_stage", "MaskHeadConv", "patch_mask_head_stages", "unpatch_mask_head_stages", "mask_loss_terms", "mask_losses", "patch_mask_losses", "unpatch_mask_losses", "mask_soft_iou", "mask_soft_iou_terms", "binarize_masks", "mask_run_lengths", "mask_binary_iou", "mask_binary_iou_terms", "LogitMask", "patch_tracker", "unpatch_tracker", "match_cost", "box_loss_terms", "box_losses", "patch_criterion", "unpatch_criterion", "linear_assignment", "raise_on_match_status", "label_loss_terms", "label_losses", "patch_label_loss", "unpatch_label_loss", "sine_position_embedding", "encoder_position_embedding", "DeferredPositionEmbedding", "patch_position_encoding", "unpatch_position_encoding", "add_layer_norm", "relu_dropout", "patch_transformer_layers", "unpatch_transformer_layers", "multihead_attention", "FusedMultiheadAttention", "patch_self_attention", "unpatch_self_attention", "window_attention", "patch_window_attention", "unpatch_window_attention", "reproducible_grad_input", "reproducible_grad_input_enabled", "ops", "patch_transformer", "patch_mask_head", "graphed", "graph_stream", "GraphedLayer", "tune"]
+           "MSDeformAttn", "TemporalMSDeformAttnEncoder", "TemporalMSDeformAttnDecoder", "ModulatedDeformableConv2d", "MultiScaleMHAttentionMap", "deform_conv2d", "attention_maps", "patch_attention_maps", "unpatch_attention_maps", "mask_head_stage", "MaskHeadConv", "patch_mask_head_stages", "unpatch_mask_head_stages", "mask_loss_terms", "mask_losses", "patch_mask_losses", "unpatch_mask_losses", "mask_soft_iou", "mask_soft_iou_terms", "binarize_masks", "mask_run_lengths", "mask_binary_iou", "mask_binary_iou_terms", "LogitMask", "patch_tracker", "unpatch_tracker", "match_cost", "box_loss_terms", "box_losses", "patch_criterion", "unpatch_criterion", "linear_assignment", "raise_on_match_status", "label_loss_terms", "label_losses", "patch_label_loss", "unpatch_label_loss", "sine_position_embedding", "encoder_position_embedding", "DeferredPositionEmbedding", "patch_position_encoding", "unpatch_position_encoding", "add_layer_norm", "relu_dropout", "patch_transformer_layers", "unpatch_transformer_layers", "multihead_attention", "FusedMultiheadAttention", "patch_self_attention", "unpatch_self_attention", "window_attention", "patch_window_attention", "unpatch_window_attention", "residual_layer_norm", "patch_merge_norm", "patch_swin_glue", "unpatch_swin_glue", "reproducible_grad_input", "reproducible_grad_input_enabled", "ops", "patch_transformer", "patch_mask_head", "graphed", "graph_stream", "GraphedLayer", "tune"]

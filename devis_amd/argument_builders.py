@@ -774,3 +774,24 @@ def unpatch_window_attention(swin_backbone_module, previous):
     """Undo :func:`patch_window_attention`."""
     from .modules import window_attention
     window_attention.unpatch(swin_backbone_module, previous)
+
+
+def patch_swin_glue(swin_backbone_module):
+    """Opt-in: make ``forward`` of the reference's ``SwinTransformerBlock``, ``BasicLayer`` and ``PatchMerging``
+    (``src.models.swin_backbone``) run the glue around their Linears and the window attention on the fused kernels of
+    :func:`devis_amd.residual_layer_norm` and :func:`devis_amd.patch_merge_norm` (:mod:`devis_amd.modules.swin_glue`, which lists
+    when the replaced forwards run instead): ``norm1`` with the copy into the padded window map, the shortcut add with its
+    drop-path scale and ``norm2``, a block's last add folded into the next block's first pass, no shift mask, and the patch
+    gather with its norm.  The fused blocks call :func:`devis_amd.window_attention` themselves, whether
+    :func:`patch_window_attention` is applied or not; where a block is not fusable the forward installed before this patch
+    runs.  Takes effect at once, also for modules that already exist; no module is replaced, so state dicts are untouched.
+    Returns what was replaced (:func:`unpatch_swin_glue`); undo patches of one module in the reverse of the order they were
+    applied in."""
+    from .modules import swin_glue
+    return swin_glue.patch(swin_backbone_module)
+
+
+def unpatch_swin_glue(swin_backbone_module, previous):
+    """Undo :func:`patch_swin_glue`."""
+    from .modules import swin_glue
+    swin_glue.unpatch(swin_backbone_module, previous)
