@@ -795,3 +795,23 @@ def unpatch_swin_glue(swin_backbone_module, previous):
     """Undo :func:`patch_swin_glue`."""
     from .modules import swin_glue
     swin_glue.unpatch(swin_backbone_module, previous)
+
+
+def patch_resnet_glue(module, keep_input_dtype=False):
+    """Opt-in: make the blocks and the stem of a ResNet with frozen BatchNorm under ``module`` -- a torchvision ``ResNet``, the
+    reference's ``Backbone`` or ``Joiner`` (``src.models.backbone``) or the ``IntermediateLayerGetter`` inside -- run everything
+    between their convolutions on the fused kernels of :func:`devis_amd.frozen_batch_norm` and
+    :func:`devis_amd.frozen_batch_norm_relu_pool` (:mod:`devis_amd.modules.resnet_glue`, which says what matches, by structure,
+    and when the forward a block had runs instead): one call per convolution, the ``downsample`` branch's norm folded into the
+    block's tail, and the stem's norm, ReLU and max-pool as one pass.  Instances get a subclass of their own class; no module is
+    replaced, so state dicts and ``named_parameters`` are untouched and checkpoints load as before.
+    ``keep_input_dtype=True`` is a stated deviation: every fused output takes the dtype of the convolution output it reads
+    (16-bit throughout under autocast) where the stock modules return float32.  Returns what :func:`unpatch_resnet_glue` needs."""
+    from .modules import resnet_glue
+    return resnet_glue.patch(module, keep_input_dtype)
+
+
+def unpatch_resnet_glue(module, previous):
+    """Undo :func:`patch_resnet_glue`."""
+    from .modules import resnet_glue
+    resnet_glue.unpatch(module, previous)

@@ -134,9 +134,10 @@ def counts_of(fn):
             "peak_bytes": peak}
 
 
-def compare(sides, windows, seconds):
+def compare(sides, windows, seconds, counts=None):
     """{name: fn} -> {name: {"ms": median, "host_ms": median, "windows_ms": [...], "iters": n, counts}}, the sides' windows
-    alternating."""
+    alternating.  ``counts`` replaces :func:`counts_of` for another operator's calls."""
+    counts = counts or counts_of
     iters = {}
     for k, fn in sides.items():
         for _ in range(3):
@@ -152,7 +153,7 @@ def compare(sides, windows, seconds):
         for k, fn in sides.items():
             host[k].append(host_window(fn, iters[k]))
     return {k: dict({"ms": statistics.median(times[k]), "host_ms": statistics.median(host[k]), "windows_ms": times[k],
-                     "host_windows_ms": host[k], "iters": iters[k]}, **counts_of(fn)) for k, fn in sides.items()}
+                     "host_windows_ms": host[k], "iters": iters[k]}, **counts(fn)) for k, fn in sides.items()}
 
 
 def subjects(shape, dtype, training, dev, g):
