@@ -797,6 +797,25 @@ def unpatch_swin_glue(swin_backbone_module, previous):
     swin_glue.unpatch(swin_backbone_module, previous)
 
 
+def patch_swin_ends(swin_backbone_module):
+    """Opt-in: make ``forward`` of the reference's ``PatchEmbed`` and ``SwinTransformer`` (``src.models.swin_backbone``) run the
+    entry and the exits of the backbone on the fused kernels of :func:`devis_amd.patch_embed_norm` and
+    :func:`devis_amd.layer_norm_to_map` (:mod:`devis_amd.modules.swin_ends`, which lists when the replaced forwards run instead):
+    padding, patch projection and norm as one pass into token order -- returned as the reference's NCHW-shaped view, which the
+    backbone flattens back without a copy --, and each output norm as one pass into the NCHW map.  Takes effect at once, also for
+    modules that already exist; no module is replaced, so state dicts are untouched.  Independent of
+    :func:`patch_window_attention` and :func:`patch_swin_glue`, in any order.  Returns what was replaced
+    (:func:`unpatch_swin_ends`); undo patches of one module in the reverse of the order they were applied in."""
+    from .modules import swin_ends
+    return swin_ends.patch(swin_backbone_module)
+
+
+def unpatch_swin_ends(swin_backbone_module, previous):
+    """Undo :func:`patch_swin_ends`."""
+    from .modules import swin_ends
+    swin_ends.unpatch(swin_backbone_module, previous)
+
+
 def patch_resnet_glue(module, keep_input_dtype=False):
     """Opt-in: make the blocks and the stem of a ResNet with frozen BatchNorm under ``module`` -- a torchvision ``ResNet``, the
     reference's ``Backbone`` or ``Joiner`` (``src.models.backbone``) or the ``IntermediateLayerGetter`` inside -- run everything

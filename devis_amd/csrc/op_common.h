@@ -165,4 +165,6 @@ template <typename F> int dispatch(int dtype, bool wide, F &&f)
 }
 
 }  // namespace devis
+
+#include "norm_row.h"        // devis::normrow: the row of the wave-per-row LayerNorm kernels (prenorm.hip, swinends.hip)
 #endif  // OP_COMMON_H_

@@ -1,14 +1,15 @@
 // prenorm.hip -- the glue of the Swin backbone's blocks (include/prenorm.h): the residual add with its
 // drop-path scale, the pre-norm LayerNorm, the store into the zero-padded window map and the 2 x 2 patch gather, forward and
 // backward, each one pass.  gfx950, wave64, plain HIP.  addnorm.hip's design at up to 3072 channels: one wave owns a row and
-// holds it in registers; there is no LDS, no atomic and nothing is zeroed by a pass of its own.  (Quad, load4 and store4 are
-// private copies of addnorm.hip's.)
+// holds it in registers; there is no LDS, no atomic and nothing is zeroed by a pass of its own.  The row itself -- a lane's
+// quads and the sums over the channels -- is norm_row.h's (devis::normrow, a part of op_common.h), which swinends.hip shares.
 #include "op_common.h"       // (fp contraction off)
 #include "prenorm.h"
 
 namespace prenorm {
 
 using namespace devis;
+using namespace devis::normrow;
 
 static_assert(PRENORM_OK == kOk && PRENORM_ERR_ARGUMENT == kErrArgument && PRENORM_ERR_HIP == kErrHip, "status codes");
 static_assert(PRENORM_F32 == kF32 && PRENORM_BF16 == kBF16 && PRENORM_F16 == kF16, "dtype codes");
@@ -17,7 +18,6 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxC = PRENORM_MAX_CHANNELS;
 constexpr int kChunkRows = 32;              // rows of one chunk of the backward's column sums
-constexpr int kSpan = 256;                  // channels one group of four per lane covers: a row is G = ceil(C / kSpan) groups
 
 thread_local Status err;     // prenorm_last_error()
 
@@ -31,56 +31,6 @@ struct Geo {
     int H2, W2;             // the merged map (source == MERGE)
     int source, dest;
 };
-
-// ---- four consecutive elements --------------------------------------------------------------------------------------------
-template <typename T> struct alignas(sizeof(T) * 4 > 16 ? 16 : sizeof(T) * 4) Quad {
-    T v[4];
-};
-
-// p[0..3] -> out, elements at or beyond `n` as 0; one 8 / 16-byte access when `vec` (nothing is dereferenced when n <= 0)
-template <typename T> __device__ __forceinline__ void load4(const T *p, int n, bool vec, float (&out)[4])
-{
-    if (vec) {
-        if (n > 0) {
-            const Quad<T> q = *reinterpret_cast<const Quad<T> *>(p);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) out[j] = to_acc(q.v[j]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) out[j] = 0.0f;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) out[j] = j < n ? to_acc(p[j]) : 0.0f;
-    }
-}
-
-template <typename T> __device__ __forceinline__ void store4(T *p, int n, bool vec, const float (&in)[4])
-{
-    if (vec) {
-        if (n > 0) {
-            Quad<T> q;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) from_acc(q.v[j], in[j]);
-            *reinterpret_cast<Quad<T> *>(p) = q;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < n) from_acc(p[j], in[j]);
-    }
-}
-
-// v rounded to T, as the arithmetic type
-template <typename T> __device__ __forceinline__ float rounded(float v)
-{
-    T t;
-    from_acc(t, v);
-    return to_acc(t);
-}
-
-// the first channel of group g of this lane
-__device__ __forceinline__ int channel_of(int g, int lane) { return (g * 64 + lane) * 4; }
 
 // ---- the 2 x 2 gather -----------------------------------------------------------------------------------------------------
 // the merged row's position
@@ -159,31 +109,6 @@ __device__ __forceinline__ void scatter4(TX *__restrict__ grad_x, const Geo &geo
             if (at >= 0) from_acc(grad_x[at], dz[j]);
         }
     }
-}
-
-// the sum over the row's channels < C of v, in every lane: g, then j, ascending, then butterflies
-template <int G> __device__ __forceinline__ float row_sum(const float (&v)[G][4], int C, int lane)
-{
-    float s = 0.0f;
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s += channel_of(g, lane) + j < C ? v[g][j] : 0.0f;
-    return wave_sum(s);
-}
-
-// the same of the products a * b, each rounded on its own
-template <int G> __device__ __forceinline__ float row_dot(const float (&a)[G][4], const float (&b)[G][4], int C, int lane)
-{
-    float s = 0.0f;
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float t = a[g][j] * b[g][j];
-            s += channel_of(g, lane) + j < C ? t : 0.0f;
-        }
-    return wave_sum(s);
 }
 
 // the element offset of row `row`'s y (and grad_y)
@@ -427,8 +352,6 @@ int geo_of(const prenorm_shape *s, Geo *geo)
     return PRENORM_OK;
 }
 
-template <int N> struct Groups { static constexpr int value = N; };
-
 // f(Groups<G>) for the smallest G of {1, 2, 3, 4, 6, 8, 12} that covers C channels
 template <typename F> int dispatch_groups(int C, F &&f)
 {
@@ -455,8 +378,6 @@ template <typename F> int dispatch_types(const prenorm_types &t, F &&f)
     const int half = t.x != kF32 ? t.x : (t.delta != kF32 ? t.delta : t.y);
     return half == kBF16 ? dispatch16<__hip_bfloat16>(t, f) : dispatch16<__half>(t, f);
 }
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }       // (NULL is aligned)
 
 int chunks_of(const Geo &geo) { return (int)cdiv(geo.R, kChunkRows); }
 

@@ -1,4 +1,4 @@
-"""Host checks the operator modules of the mask path share (deform_conv, attention_maps, mask_head_stage, mask_losses, mask_iou, mask_rle, mask_binary_iou, box_matching, assignment, label_loss, position_embedding, add_norm, self_attention, window_attention, pre_norm, frozen_norm)."""
+"""Host checks the operator modules of the mask path share (deform_conv, attention_maps, mask_head_stage, mask_losses, mask_iou, mask_rle, mask_binary_iou, box_matching, assignment, label_loss, position_embedding, add_norm, self_attention, window_attention, pre_norm, frozen_norm, swin_ends)."""
 import functools
 
 import torch
