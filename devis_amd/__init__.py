@@ -33,7 +33,9 @@ its norm written in token order and the per-stage output norms written as NCHW m
 ``devis_amd.layer_norm_to_map``; ``devis_amd.patch_swin_ends``; C ABI ``include/swinends.h``) and the glue between the
 convolutions of its ResNet backbone -- the frozen BatchNorm's affine map with the ReLU, the shortcut add with the downsample
 branch's norm folded in, and the stem's max-pool (``devis_amd.frozen_batch_norm``, ``devis_amd.frozen_batch_norm_relu_pool``;
-``devis_amd.patch_resnet_glue``; C ABI ``include/frozennorm.h``).
+``devis_amd.patch_resnet_glue``; C ABI ``include/frozennorm.h``) and the seam between the backbone and the encoder -- the
+GroupNorm of every input projection written once as the encoder's flat token tensor ``src_flatten``
+(``devis_amd.group_norm_tokens``; ``devis_amd.patch_input_proj``; C ABI ``include/inputproj.h``).
 
 Arithmetic lives in hand-written HIP kernels behind the C ABI of ``include/msda.h``
 (``devis_amd/csrc/*.hip``, one translation unit per kernel family -> ``devis_amd/libmsda_hip.so``); the Python here is the host side.
@@ -74,10 +76,13 @@ from .functions.pre_norm import patch_merge_norm, residual_layer_norm  # noqa: F
 from .argument_builders import patch_swin_ends, unpatch_swin_ends  # noqa: F401
 from .functions.swin_ends import layer_norm_to_map, patch_embed_norm  # noqa: F401  (eager kernels; the torch composite while compiling)
 from .argument_builders import patch_resnet_glue, unpatch_resnet_glue  # noqa: F401
+from .argument_builders import patch_input_proj, unpatch_input_proj  # noqa: F401
+from .functions.input_projection import group_norm_tokens  # noqa: F401  (eager kernels; the torch composite while compiling)
+from .modules.input_projection import DeferredInputProjection  # noqa: F401
 from .functions.frozen_norm import frozen_batch_norm, frozen_batch_norm_relu_pool  # noqa: F401  (eager kernels; the torch composite while compiling)
 from .tracking import LogitMask  # noqa: F401
 from .graphs import graphed, graph_stream, GraphedLayer  # noqa: F401
 from .tuning import tune  # noqa: F401
 
 __all__ = ["MSDeformAttnFunction", "MSDeformAttnTemporalFunction", "ms_deform_attn_core_pytorch",
-           "MSDeformAttn", "TemporalMSDeformAttnEncoder", "TemporalMSDeformAttnDecoder", "ModulatedDeformableConv2d", "MultiScaleMHAttentionMap", "deform_conv2d", "attention_maps", "patch_attention_maps", "unpatch_attention_maps", "mask_head_stage", "MaskHeadConv", "patch_mask_head_stages", "unpatch_mask_head_stages", "mask_loss_terms", "mask_losses", "patch_mask_losses", "unpatch_mask_losses", "mask_soft_iou", "mask_soft_iou_terms", "binarize_masks", "mask_run_lengths", "mask_binary_iou", "mask_binary_iou_terms", "LogitMask", "patch_tracker", "unpatch_tracker", "match_cost", "box_loss_terms", "box_losses", "patch_criterion", "unpatch_criterion", "linear_assignment", "raise_on_match_status", "label_loss_terms", "label_losses", "patch_label_loss", "unpatch_label_loss", "sine_position_embedding", "encoder_position_embedding", "DeferredPositionEmbedding", "patch_position_encoding", "unpatch_position_encoding", "add_layer_norm", "relu_dropout", "patch_transformer_layers", "unpatch_transformer_layers", "multihead_attention", "FusedMultiheadAttention", "patch_self_attention", "unpatch_self_attention", "window_attention", "patch_window_attention", "unpatch_window_attention", "residual_layer_norm", "patch_merge_norm", "patch_swin_glue", "unpatch_swin_glue", "patch_embed_norm", "layer_norm_to_map", "patch_swin_ends", "unpatch_swin_ends", "frozen_batch_norm", "frozen_batch_norm_relu_pool", "patch_resnet_glue", "unpatch_resnet_glue", "reproducible_grad_input", "reproducible_grad_input_enabled", "ops", "patch_transformer", "patch_mask_head", "graphed", "graph_stream", "GraphedLayer", "tune"]
+           "MSDeformAttn", "TemporalMSDeformAttnEncoder", "TemporalMSDeformAttnDecoder", "ModulatedDeformableConv2d", "MultiScaleMHAttentionMap", "deform_conv2d", "attention_maps", "patch_attention_maps", "unpatch_attention_maps", "mask_head_stage", "MaskHeadConv", "patch_mask_head_stages", "unpatch_mask_head_stages", "mask_loss_terms", "mask_losses", "patch_mask_losses", "unpatch_mask_losses", "mask_soft_iou", "mask_soft_iou_terms", "binarize_masks", "mask_run_lengths", "mask_binary_iou", "mask_binary_iou_terms", "LogitMask", "patch_tracker", "unpatch_tracker", "match_cost", "box_loss_terms", "box_losses", "patch_criterion", "unpatch_criterion", "linear_assignment", "raise_on_match_status", "label_loss_terms", "label_losses", "patch_label_loss", "unpatch_label_loss", "sine_position_embedding", "encoder_position_embedding", "DeferredPositionEmbedding", "patch_position_encoding", "unpatch_position_encoding", "add_layer_norm", "relu_dropout", "patch_transformer_layers", "unpatch_transformer_layers", "multihead_attention", "FusedMultiheadAttention", "patch_self_attention", "unpatch_self_attention", "window_attention", "patch_window_attention", "unpatch_window_attention", "residual_layer_norm", "patch_merge_norm", "patch_swin_glue", "unpatch_swin_glue", "patch_embed_norm", "layer_norm_to_map", "patch_swin_ends", "unpatch_swin_ends", "frozen_batch_norm", "frozen_batch_norm_relu_pool", "patch_resnet_glue", "unpatch_resnet_glue", "group_norm_tokens", "DeferredInputProjection", "patch_input_proj", "unpatch_input_proj", "reproducible_grad_input", "reproducible_grad_input_enabled", "ops", "patch_transformer", "patch_mask_head", "graphed", "graph_stream", "GraphedLayer", "tune"]

@@ -1,4 +1,4 @@
-"""What the ctypes bindings of the mask-path operators share (``_mdcn``, ``_attmap``, ``_mhstage``, ``_maskloss``, ``_maskiou``, ``_maskrle``, ``_maskbiou``, ``_boxmatch``, ``_assign``, ``_labelloss``, ``_posembed``, ``_addnorm``, ``_selfattn``, ``_winattn``, ``_prenorm``, ``_frozennorm``, ``_swinends``): how an
+"""What the ctypes bindings of the mask-path operators share (``_mdcn``, ``_attmap``, ``_mhstage``, ``_maskloss``, ``_maskiou``, ``_maskrle``, ``_maskbiou``, ``_boxmatch``, ``_assign``, ``_labelloss``, ``_posembed``, ``_addnorm``, ``_selfattn``, ``_winattn``, ``_prenorm``, ``_frozennorm``, ``_swinends``, ``_inputproj``): how an
 operator's entry points of libmsda_hip.so are checked and given their prototypes once, and how a failing call raises.
 """
 import ctypes

@@ -108,18 +108,26 @@ def interned_pyramid(shapes, device):
     return hit
 
 
+def flatten_sources(srcs):
+    """``src_flatten`` of both ``prepare_data`` variants: ``cat([src.flatten(2).transpose(1, 2) for src in srcs], 1)``.  With plain
+    tensors exactly that, bit for bit; when every level is a :class:`devis_amd.DeferredInputProjection`
+    (:func:`patch_input_proj`) of one ``N``, ``C``, ``num_groups``, ``eps`` and dtype, ONE :func:`devis_amd.group_norm_tokens`
+    call, each level then bound to its ``[N, C, H, W]`` view of the result; a mix materialises the deferred ones first."""
+    from .modules import input_projection
+    return input_projection.flatten_sources(list(srcs))
+
+
 def prepare_data(self, srcs, masks, pos_embeds):
     """Replacement for ``DeformableTransformer.prepare_data`` (deformable_transformer.py:69-94; same arguments, same six results):
     per level the feature map, its padding mask and its positional embedding (+ the level embedding) flattened and concatenated
     over the levels, the valid ratios of every frame -- and the pyramid's ``spatial_shapes`` / ``level_start_index`` taken from
     :func:`interned_pyramid` instead of being pushed to the device again (the reference's ``torch.as_tensor(..., device=...)`` of a
     Python list is a blocking host-to-device copy: it waits for everything queued on the stream)."""
-    feats, pads, embeds = [], [], []
-    for lvl, (src, mask, pos_embed) in enumerate(zip(srcs, masks, pos_embeds)):
-        feats.append(src.flatten(2).transpose(1, 2))
+    pads, embeds = [], []
+    for lvl, (mask, pos_embed) in enumerate(zip(masks, pos_embeds)):
         pads.append(mask.flatten(1))
         embeds.append(pos_embed.flatten(2).transpose(1, 2) + self.level_embed[lvl].view(1, 1, -1))
-    src_flatten, mask_flatten, lvl_pos_embed_flatten = torch.cat(feats, 1), torch.cat(pads, 1), torch.cat(embeds, 1)
+    src_flatten, mask_flatten, lvl_pos_embed_flatten = flatten_sources(srcs), torch.cat(pads, 1), torch.cat(embeds, 1)
     spatial_shapes, level_start_index = interned_pyramid([src.shape[-2:] for src in srcs], src_flatten.device)
     valid_ratios = torch.stack([self.get_valid_ratio(m) for m in masks], 1)
     return src_flatten, mask_flatten, lvl_pos_embed_flatten, spatial_shapes, level_start_index, valid_ratios
@@ -672,7 +680,7 @@ def prepare_data_deferred(self, srcs, masks, pos_embeds):
     if module is None:
         return prepare_data(self, srcs, masks, [p.materialize() if isinstance(p, DeferredPositionEmbedding) else p for p in pos_embeds])
     dtype = pos_embeds[0].dtype
-    src_flatten = torch.cat([src.flatten(2).transpose(1, 2) for src in srcs], 1)
+    src_flatten = flatten_sources(srcs)
     lvl_pos_embed_flatten, mask_flatten, valid_ratios = ops.encoder_position_embedding(
         list(masks), self.level_embed[:len(masks)], getattr(module, "temporal_embed", None), num_pos_feats=module.num_pos_feats,
         temperature=module.temperature, normalize=module.normalize, scale=module.scale if module.normalize else None,
@@ -834,3 +842,27 @@ def unpatch_resnet_glue(module, previous):
     """Undo :func:`patch_resnet_glue`."""
     from .modules import resnet_glue
     resnet_glue.unpatch(module, previous)
+
+
+def patch_input_proj(model):
+    """Opt-in, EAGER ONLY (a :class:`devis_amd.DeferredInputProjection` is a Python object, not a tensor): make the ``GroupNorm``
+    of every ``Sequential(Conv2d, GroupNorm)`` in ``model.input_proj`` -- the reference's ``DeformableDETR``
+    (``src.models.deformable_detr``), or anything with such a ``ModuleList`` -- return a deferred projection, which
+    :func:`prepare_data` and :func:`prepare_data_deferred` turn into ``src_flatten`` with one fused
+    :func:`devis_amd.group_norm_tokens` call for all levels (:mod:`devis_amd.modules.input_projection`).  A 3 x 3 / stride-2
+    projection that is followed by another one (five or more levels) feeds the next convolution and is not deferred: it runs
+    the one-level kernel at once.  The ``GroupNorm`` instances get a subclass; no module is replaced, so state dicts are
+    untouched.
+
+    Order: the fused path needs one of this package's ``prepare_data`` -- call :func:`patch_transformer` (and, for the fused
+    positional input, :func:`patch_position_encoding` after it) as well, in any order relative to this patch.  Under the stock
+    ``prepare_data`` the deferred projections materialise on ``.flatten(2)``, level by level through the one-level kernel:
+    results are right and nothing is fused.  Independent of every other patch.  Returns what :func:`unpatch_input_proj` needs."""
+    from .modules import input_projection
+    return input_projection.patch(model)
+
+
+def unpatch_input_proj(model, previous):
+    """Undo :func:`patch_input_proj`."""
+    from .modules import input_projection
+    input_projection.unpatch(model, previous)

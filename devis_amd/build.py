@@ -42,7 +42,7 @@ HIPCC_FLAGS = [
 
 
 def include_dir():
-    """Directory of msda.h, mdcn.h, attmap.h, mhstage.h, maskloss.h, maskiou.h, maskrle.h, maskbiou.h, boxmatch.h, assign.h, labelloss.h, posembed.h, addnorm.h, selfattn.h, winattn.h, prenorm.h, frozennorm.h and swinends.h: <repo>/include (the canonical copy, next to the package) or, for a relocated package,
+    """Directory of msda.h, mdcn.h, attmap.h, mhstage.h, maskloss.h, maskiou.h, maskrle.h, maskbiou.h, boxmatch.h, assign.h, labelloss.h, posembed.h, addnorm.h, selfattn.h, winattn.h, prenorm.h, frozennorm.h, swinends.h and inputproj.h: <repo>/include (the canonical copy, next to the package) or, for a relocated package,
     a copy shipped inside it (devis_amd/include)."""
     for d in (os.path.join(ROOT, "include"), os.path.join(HERE, "include")):
         if os.path.exists(os.path.join(d, "msda.h")):

@@ -18,7 +18,7 @@ class BuildWithHip(build_py):
         hip_build.ensure()                                      # raises when hipcc is missing and no library is there
         inc = os.path.join(ROOT, "devis_amd", "include")        # the headers travel inside the package (build.include_dir)
         os.makedirs(inc, exist_ok=True)
-        for header in ("msda.h", "mdcn.h", "attmap.h", "mhstage.h", "maskloss.h", "maskiou.h", "maskrle.h", "maskbiou.h", "boxmatch.h", "assign.h", "labelloss.h", "posembed.h", "addnorm.h", "selfattn.h", "winattn.h", "prenorm.h", "frozennorm.h", "swinends.h"):
+        for header in ("msda.h", "mdcn.h", "attmap.h", "mhstage.h", "maskloss.h", "maskiou.h", "maskrle.h", "maskbiou.h", "boxmatch.h", "assign.h", "labelloss.h", "posembed.h", "addnorm.h", "selfattn.h", "winattn.h", "prenorm.h", "frozennorm.h", "swinends.h", "inputproj.h"):
             shutil.copy2(os.path.join(ROOT, "include", header), os.path.join(inc, header))
         try:
             super().run()
